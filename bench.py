@@ -14,8 +14,10 @@ encoder, ego tail -- around the lane's collective), the same object the parity t
 127.0.0.1) and refuses to run when fewer than N devices are visible.  With R ranks a step
 processes R frames in the agent-sharded "frame ring" of coalign_amd/sharded.py (weak scaling): every rank encodes the
 agents the ring assigns to it out of the SAME frame pool, so the per-frame detection checksums printed here are equal
-for every --gpus value.  Rank 0 prints ONE JSON line; it carries the roofline of the dominant hand-written kernel, the
-north-star HBM figure of the pillar-scatter + warp path, and, at N=1, the CPU oracle timed on the host cores.
+for every --gpus value.  Rank 0 prints ONE JSON line: frames/s and ms per step of the timed steps.  With --full the run goes on to
+the side reports, and the line also carries the roofline of the dominant hand-written kernel, the north-star HBM figure of the
+pillar-scatter + warp path, latency, the other arithmetics and, at N=1, the CPU oracle timed on the host cores.
+--dump-outputs DIR writes the last timed step's detections as .npy files (inputs and weights are seeded: equal arguments, equal inputs).
 """
 import argparse
 import json
@@ -31,10 +33,12 @@ if int(os.environ.get("WORLD_SIZE", "1")) > 1:
 
 
 def self_launch(n: int) -> None:
-    """``python bench.py --gpus N`` (N > 1) without a launcher: become ``torch.distributed.run --nproc-per-node N`` of this very command line (the reference's
-    own bring-up is a launcher too: opencood/tools/multi_gpu_utils.py:31-37).  Never returns.  Fewer than N visible devices: exit 2 with the reason -- an
-    N = 1 line for an N = 8 request would be worse than no line."""
+    """``python bench.py --gpus N`` (N > 1) without a launcher: run ``torch.distributed.run --nproc-per-node N`` of this very command line as a child process and
+    exit with its status (the reference's own bring-up is a launcher too: opencood/tools/multi_gpu_utils.py:31-37).  Never returns.  Fewer than N visible
+    devices: exit 2 with the reason -- an N = 1 line for an N = 8 request would be worse than no line.  (A child, not exec: counting the devices has started
+    the GPU runtime in this process, and such a process is not replaced.)"""
     import socket
+    import subprocess
     import torch
     one_gpu = os.environ.get("COALIGN_BENCH_ONE_GPU") == "1" or "--launch-check" in sys.argv      # functional tests: ranks share device 0 / need no device
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
@@ -49,7 +53,7 @@ def self_launch(n: int) -> None:
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.abspath(__file__)] + sys.argv[1:]
     print("bench: self-launch: " + " ".join(cmd), file=sys.stderr, flush=True)
-    os.execvpe(sys.executable, cmd, env)
+    raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 import torch
 import torch.distributed as dist
@@ -78,6 +82,17 @@ def checksum(boxes, scores):
     if boxes is None:
         return [0, 0.0, 0.0]
     return [int(boxes.shape[0]), round(float(scores.double().sum()), 9), round(float(boxes.double().abs().sum()), 6)]
+
+
+def dump_outputs(out_dir, results, steps):
+    """--dump-outputs: the detections FramePipeline handed back for the LAST timed step (frame index steps - 1 of the timed loop) -- corners [K, 8, 3] and
+    scores [K] -- as out_dir/boxes.npy and out_dir/scores.npy in float32; a frame without detections (None, None) is written with K = 0."""
+    import numpy as np
+    idx, boxes, scores = results[-1]
+    assert idx == steps - 1, (idx, steps)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "boxes.npy"), np.zeros((0, 8, 3), np.float32) if boxes is None else boxes.detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, "scores.npy"), np.zeros((0,), np.float32) if scores is None else scores.detach().float().cpu().numpy())
 
 
 def hip_time(fn, iters=10, warm=3):
@@ -297,14 +312,14 @@ def main():
     ap.add_argument("--queue-depth", type=int, default=0, help="frames queued per lane stream: lanes x depth pipeline lanes share `lanes` HIP streams -- a stream's next frames are enqueued before its current one has finished, so no stream waits for the host between frames (0: 3 for the single-GPU graph pipeline, else 1)")
     ap.add_argument("--no-miopen-find", action="store_true", help="leave torch.backends.cudnn.benchmark off (MIOpen immediate mode)")
     ap.add_argument("--no-graph", action="store_true", help="~150 eager launches per frame (1.5 ms of host time) instead of one HIP graph replay per frame "
-                    "(0.1 ms; single-GPU default: measured +1 ... +4 % frames/s on the channels-last route; multi-rank runs are always eager)")
+                    "(0.1 ms; single-GPU default: measured +1 ... +4 %% frames/s on the channels-last route; multi-rank runs are always eager)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-numerics", action="store_true", help="skip the float64 end-to-end error report (`numerics`: two float64 CPU forwards of the benchmarked frame, ~20-40 s)")
     ap.add_argument("--conv-emu", type=int, default=None, choices=(0, 2, 3, 16),
                     help="override the 3x3 convolution arithmetic: 0 = native fp32 MFMA / MIOpen, 3 / 2 = split-bf16 products (default: the package default)")
     ap.add_argument("--no-side-modes", action="store_true", help="skip the extra timed passes of the other convolution modes")
     ap.add_argument("--from-points", action="store_true", help="ALSO time the loop fed from raw point clouds in pinned host memory (async H2D + device "
-                    "voxeliser + encoder in every frame: `from_points` in the JSON line; `value` stays the from-pillars metric of BASELINE.json); on by default at --gpus 1")
+                    "voxeliser + encoder in every frame: `from_points` in the JSON line; `value` stays the from-pillars metric of BASELINE.json); on by default with --full at --gpus 1")
     ap.add_argument("--no-from-points", action="store_true")
     ap.add_argument("--no-latency", action="store_true", help="skip the one-frame-in-flight latency pass")
     ap.add_argument("--no-size-sweep", action="store_true", help="skip the `size_sweep` report (pillar op / fusion at 8 000 / 32 000 / 70 000 pillars per agent, cfg 2, cfg 4)")
@@ -323,6 +338,11 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=10)
     ap.add_argument("--cpu-threads", type=int, default=0, help="torch CPU threads for the oracle (0 = best of the committed sweep, else 16)")
     ap.add_argument("--cpu-budget-s", type=float, default=30.0)
+    ap.add_argument("--full", action="store_true", help="also run every side report: isolated kernels and rooflines (timed before the warm-up), the multi-rank exchange "
+                    "timing, and after the timed steps the per-kernel profile pass, latency, from_points, other_modes, size_sweep, cpu_baseline and numerics (the --no-* "
+                    "options above select among them).  Without it a run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what FramePipeline handed back for the last timed step: "
+                    "DIR/boxes.npy (corners [K, 8, 3]) and DIR/scores.npy ([K]), float32, K = 0 for a frame without detections")
     args = ap.parse_args()
     if args.dry_run:
         from coalign_amd.sharded import preflight
@@ -582,7 +602,7 @@ def main():
         rccl["fallbacks"] += taken
         rccl["mode_run"] = mode
         # what one exchange costs on this node: the feature maps of one step through the schedule's collective, HIP events, max over ranks
-        if exchanges is not None:
+        if args.full and exchanges is not None:
             try:
                 with torch.no_grad():
                     feats_x, _ = model.encode(step_batches[0])
@@ -608,7 +628,7 @@ def main():
             pipe = make_pipe(False)
     # ---- kernels alone on the GPU (outside the timed region): the roofline figures comparable to a rocprofv3 kernel trace
     iso = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         with torch.no_grad():
             f0 = frames[0]
             pl_in = dict(f0["processed_lidar"], record_len=f0["record_len"])
@@ -657,6 +677,8 @@ def main():
     sync()
 
     dt, t_issue, results = timed_run(pipe, args.steps, warm)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results, args.steps)
     lat_default = list(pipe.latencies_ms)
     range_hit = pipe.range_exceeded()          # (outside the bracket) did any SplitMap value leave the fp16 split's operating range?
     if multi:
@@ -683,18 +705,20 @@ def main():
     last_boxes = results[-1][1] if results else None
 
     # ---- per-kernel HIP-event profile inside ordinary (eager) steps right after the region (graph replays bypass the op hooks)
-    ops.PROFILE = {}
-    prof_pipe = pipe if not use_graph else make_pipe(False)
-    for s in range(2 * n_lanes):
-        prof_pipe.submit(step_batches[s % len(step_batches)])
-    prof_pipe.drain()
-    sync()
-    prof, ops.PROFILE = ops.PROFILE, None
+    prof = {}
+    if args.full:
+        ops.PROFILE = {}
+        prof_pipe = pipe if not use_graph else make_pipe(False)
+        for s in range(2 * n_lanes):
+            prof_pipe.submit(step_batches[s % len(step_batches)])
+        prof_pipe.drain()
+        sync()
+        prof, ops.PROFILE = ops.PROFILE, None
 
     # ---- per-frame latency: ONE frame in flight, detections collected before the next frame is submitted (the reference's strictly
     #      serial loop, opencood/tools/inference.py:125-179) -- what a 10 Hz LiDAR consumer sees
     latency = None
-    if (not multi) and not args.no_latency:
+    if args.full and (not multi) and not args.no_latency:
         latency = {"default_pipeline": dict(latency_stats(lat_default), frames_in_flight=n_lanes, streams=n_streams, frames_queued_per_stream=n_lanes // n_streams, result_lag_frames=pipe.result_lag)}
         try:
             p1 = FramePipeline(model, pp, anchors, lanes=1, result_lag=0, graph=use_graph, device=dev, streams=lane_streams)
@@ -709,7 +733,7 @@ def main():
     # ---- the loop fed from RAW POINTS in host memory: pinned staging -> async H2D -> coalign_voxelize -> encoder (count on the device)
     #      -> the same frame.  A second reported mode; `value` stays the from-pillars metric BASELINE.json names.
     from_points = None
-    if (not multi) and (args.from_points or not args.no_from_points):
+    if args.full and (not multi) and (args.from_points or not args.no_from_points):
         try:
             from coalign_amd.preprocess import build_preprocessor
             pre = build_preprocessor(hypes["preprocess"], False, dev)
@@ -757,7 +781,7 @@ def main():
 
     # ---- the same bracket with the other convolution arithmetics (reported beside `value`, never as `value`)
     side = None
-    if (not multi) and not args.no_side_modes:
+    if args.full and (not multi) and not args.no_side_modes:
         side = {}
         try:
             for terms in (0, 3, 16, 2):
@@ -787,6 +811,7 @@ def main():
         ms_step = dt / args.steps * 1e3
         frames_per_step = world if mode in ("ring", "replicas") else 1        # gather mode: the ranks share ONE frame per step
         fps = frames_per_step * args.steps / dt
+    if rank == 0 and args.full:       # the side reports of the line: kernels alone on the GPU against their rooflines, the per-kernel profile pass
         M = int(frames[0]["processed_lidar"]["voxel_features"].shape[0])
         scales = [(64, ny // 2, nx // 2), (128, ny // 4, nx // 4), (256, ny // 8, nx // 8)]
         alg_bytes = {"pillar_vfe_scatter": M * (32 * 4 * 4 + 4 * 4 + 4 + 64 * 4) + N * 64 * ny * nx * 4}
@@ -925,6 +950,7 @@ def main():
         roofline["isolated_ms"] = {k: round(v, 5) for k, v in iso.items() if k.endswith("_ms")}
         roofline["hbm_bound_kernel"] = pillar
 
+    if rank == 0:
         if default_terms == 16:
             dtype = ("f32 (3x3 convolutions: every operand rounded to 22 significant bits and split into two fp16 terms, the low term scaled by 2^10 and the "
                      "weights by a per-output-channel power of two so that both terms are normal fp16 numbers at any scale; three fp16 matrix products per fp32 "
@@ -950,7 +976,7 @@ def main():
                                        (", one communicator per lane" if args.comm_per_lane else ", one communicator"),
                        "detections_last_frame": 0 if last_boxes is None else int(last_boxes.shape[0]),
                        "candidates_last_frame": pp.last_counts["candidates"]},
-            "roofline": roofline, "roofline_by_layer": layer_rows, "north_star_hbm": north, "kernels": kernels,
+            **({"roofline": roofline, "roofline_by_layer": layer_rows, "north_star_hbm": north, "kernels": kernels} if args.full else {}),
             "host_enqueue_ms_per_step": round(t_issue / args.steps * 1e3, 4),
             "frame_digests": {str(k): digests[k] for k in sorted(digests)}, "frame_digests_reproducible": bool(consistent),
             "frame_digest_mismatches": mismatches[:8],
@@ -966,14 +992,14 @@ def main():
             result["from_points"] = from_points
         if side is not None:
             result["other_modes"] = side
-        if (not multi) and not args.no_size_sweep:
+        if args.full and (not multi) and not args.no_size_sweep:
             pipe.close()
             del pipe
             torch.cuda.empty_cache()
             result["size_sweep"] = size_sweep(dev, streams=lane_streams, lanes=n_streams if use_graph else 3, result_lag=result_lag if use_graph else 1, queue_depth=queue_depth if use_graph else 1)
-        if (not multi) and not args.no_cpu_baseline:
+        if args.full and (not multi) and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(hypes, model, frames_cpu, anchors, args.cpu_frames, args.cpu_threads, args.cpu_budget_s)
-        if (not multi) and not args.no_numerics:
+        if args.full and (not multi) and not args.no_numerics:
             # checker leg (like cpu_baseline: rank 0, N = 1, outside every timed region): the benchmarked geometry end to end against a FLOAT64 evaluation of the
             # reference's forward, in the default arithmetic, bf16 x 3 and native fp32, beside the reference's own fp32 (tests/numerics_table.py)
             try:

@@ -126,14 +126,20 @@ def test_anchors_and_derived_config_match_reference(golden):
         assert [h["postprocess"]["anchor_args"][k] for k in "WHD"] == list(g[tag + "_WHD"])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/opencood/hypes_yaml"), reason="reference checkout not present on this machine")
-def test_unchanged_reference_yamls_load_and_build():
-    base = "/root/reference/opencood/hypes_yaml/"
+def test_unchanged_reference_yamls_load_and_build(tmp_path):
+    """Three of the reference's hypes yamls as load_yaml read them (tests/golden/reference_yamls.json, tests/golden/make_reference_yamls.py) against the shipped configs."""
+    import json
+    p = tmp_path / "optimizer.yaml"
+    p.write_text("optimizer:\n  core_method: Adam\n  lr: 0.002\n  args:\n    eps: 1e-10\n    weight_decay: 1e-4\n")
+    eps = load_yaml(str(p))["optimizer"]["args"]["eps"]
+    assert isinstance(eps, float) and eps == 1e-10                          # float resolver fix ("1e-10" parses as float)
+    golden = json.load(open(os.path.join(REPO, "tests", "golden", "reference_yamls.json")))
     for rel, cfg in (("opv2v/lidar_only_with_noise/coalign/pointpillar_coalign.yaml", "opv2v_coalign"),
                      ("opv2v/lidar_only_with_noise/pointpillar_single.yaml", "opv2v_pointpillar_late"),
                      ("dairv2x/lidar_only_with_noise/coalign/pointpillar_coalign.yaml", "dairv2x_coalign")):
-        ref, mine = load_yaml(base + rel), builtin_config(cfg)
-        assert ref["optimizer"]["args"]["eps"] == 1e-10                      # float resolver fix ("1e-10" parses as float)
+        ref, mine = golden[rel], builtin_config(cfg)
+        ref["model"]["args"]["point_pillar_scatter"]["grid_size"] = np.asarray(ref["model"]["args"]["point_pillar_scatter"]["grid_size"], dtype=np.int64)
+        assert ref["optimizer_eps"] == 1e-10
         assert ref["model"]["core_method"] == mine["model"]["core_method"]
         ra, ma = ref["model"]["args"], mine["model"]["args"]
         for k in ("voxel_size", "lidar_range", "anchor_number", "pillar_vfe", "base_bev_backbone", "shrink_header", "dir_args"):
@@ -271,7 +277,10 @@ def dataset_scenario(g, tag):
     return sc
 
 
-def check_batch_against_reference(batch, g, tag, exact_voxels=True):
+def check_batch_against_reference(batch, g, tag, exact_voxels=True, xyz_atol=0.0):
+    """``xyz_atol`` > 0: the clouds were projected on the host before voxelisation (proj_first), so x, y, z of the pillars' points are float32 4-term matrix products
+    whose rounding follows the host's BLAS kernel (MKL's AVX-512, AVX2 and SSE4.2 kernels differ by up to 1.5e-5 on this golden); they are held to ``xyz_atol``,
+    everything else stays bit-exact."""
     import numpy as np
     ego = batch["ego"]
     assert [str(c) for c in ego["cav_id_list"]] == [str(c) for c in g[f"{tag}_cav_id_list"]]
@@ -285,7 +294,12 @@ def check_batch_against_reference(batch, g, tag, exact_voxels=True):
     assert np.array_equal(ego["transformation_matrix"].numpy(), g[f"{tag}_transformation_matrix"])
     pl = {k: v.cpu().numpy() for k, v in ego["processed_lidar"].items()}
     assert np.array_equal(pl["voxel_coords"], g[f"{tag}_voxel_coords"]) and np.array_equal(pl["voxel_num_points"], g[f"{tag}_voxel_num_points"])
-    assert np.array_equal(pl["voxel_features"], g[f"{tag}_voxel_features"])
+    feats, want = pl["voxel_features"], g[f"{tag}_voxel_features"]
+    if xyz_atol == 0.0:
+        assert np.array_equal(feats, want)
+    else:
+        assert feats.shape == want.shape and np.array_equal(feats[..., 3:], want[..., 3:])
+        np.testing.assert_allclose(feats[..., :3], want[..., :3], rtol=0, atol=xyz_atol)
 
 
 def test_batch_dict_producer_matches_reference_dataset(golden):
@@ -352,7 +366,8 @@ def test_dataset_side_branches_match_reference(golden):
     batcher = IntermediateFusionBatcher(h, train=False, device="cpu", preprocessor=OracleVoxels(h["preprocess"]))
     np.random.seed(int(g["np_seed"]))
     batch = batcher(dataset_scenario(gg, "c"))
-    check_batch_against_reference(batch, gg, "c")
+    # the terms each projected coordinate sums stay below 128 m here: two float32 evaluations of the 4-term sum differ by at most ~6 unit roundoffs of that
+    check_batch_against_reference(batch, gg, "c", xyz_atol=6 * 2.0 ** -24 * 128)
     pw = batch["ego"]["pairwise_t_matrix"].numpy()
     assert np.array_equal(pw, np.tile(np.eye(4), pw.shape[:3] + (1, 1)))
     assert float(np.abs(g["lidar_pose"] - g["lidar_pose_clean"]).max()) > 0.01      # the noise really was drawn

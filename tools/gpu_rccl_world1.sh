@@ -6,10 +6,10 @@ set -u
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$ROOT/gpurun_out/rccl; rm -rf $OUT; mkdir -p $OUT; export TMPDIR=/tmp
 cd $ROOT
 for mode in ring gather; do
-  timeout 300 python bench.py --force-dist --mode $mode --steps 20 --warmup 5 --no-cpu-baseline --no-numerics > $OUT/bench_force_dist_$mode.json 2> $OUT/bench_force_dist_$mode.err
+  timeout 300 python bench.py --full --force-dist --mode $mode --steps 20 --warmup 5 --no-cpu-baseline --no-numerics > $OUT/bench_force_dist_$mode.json 2> $OUT/bench_force_dist_$mode.err
   cut -c1-200 $OUT/bench_force_dist_$mode.json
 done
-( cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python $ROOT/bench.py --force-dist --steps 10 --warmup 3 --no-cpu-baseline --no-numerics > $OUT/trace.log 2>&1 )
+( cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python $ROOT/bench.py --full --force-dist --steps 10 --warmup 3 --no-cpu-baseline --no-numerics > $OUT/trace.log 2>&1 )
 cp $(find $OUT/trace -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_force_dist.csv
 python - $OUT <<'PY'
 import csv, glob, sys, os

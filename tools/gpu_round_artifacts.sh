@@ -5,8 +5,8 @@
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$ROOT/gpurun_out/round; rm -rf $OUT; mkdir -p $OUT; export TMPDIR=/tmp
 cd $ROOT
-timeout 600 python bench.py 2> $OUT/bench.err | tee $OUT/bench_n1.json | cut -c1-300
-( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python $ROOT/bench.py --no-cpu-baseline --no-numerics --no-side-modes --no-size-sweep --no-from-points --no-latency > $OUT/stats.log 2>&1 )
+timeout 600 python bench.py --full 2> $OUT/bench.err | tee $OUT/bench_n1.json | cut -c1-300
+( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python $ROOT/bench.py --full --no-cpu-baseline --no-numerics --no-side-modes --no-size-sweep --no-from-points --no-latency > $OUT/stats.log 2>&1 )
 cp $(find $OUT/stats -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv
 cp $(find $OUT/stats -name "*domain_stats.csv" | head -1) $OUT/domain_stats.csv
 grep -h '"metric"' $OUT/stats.log > $OUT/bench_n1_under_rocprof.json
