@@ -116,6 +116,18 @@ def split_maps_active() -> bool:
     return SPLIT_MAPS and CONV_EMU_TERMS == 16 and NHWC_STAGE_OUTPUTS and CONV_EMU_TAP_MAJOR and POINTWISE_EMU
 
 
+# The channel limits of the SplitMap convolutions (csrc/conv3x3_sp.hip, csrc/conv3x3_sp_s2.hip): 64-channel output tiles, 16-channel input chunks, and every
+# output channel's bias and 2^-k_c words (the fused skip's 2^-k_c words too) in the 8 KB of LDS behind the operand buffers.  The layers' route predicates and
+# routes.plan all ask sp_channels_ok, so that no copy of these numbers can drift from the kernels' own checks.
+SP_MAX_COUT, SP_MAX_COUT_SKIP = 1024, 512
+
+
+def sp_channels_ok(cin: Optional[int], cout: int, skip: bool = False) -> bool:
+    """A 3x3 layer of (cin, cout) fits the SplitMap kernels (``cin`` None: the output side only); ``skip``: with the block's 1 x 1 / stride-2 skip convolution
+    fused as a tenth tap."""
+    return cout % 64 == 0 and 0 < cout <= (SP_MAX_COUT_SKIP if skip else SP_MAX_COUT) and (cin is None or (cin > 0 and cin % 16 == 0))
+
+
 def winograd_active() -> bool:
     return CONV_WINOGRAD and CONV_EMU_TERMS == 3 and NHWC_STAGE_OUTPUTS      # (COALIGN_NHWC_STAGES=0 is the all-NCHW measurement route)
 
@@ -303,19 +315,20 @@ class BasicBlock(nn.Module):
         if self.training or not FAST_INFERENCE or not split_maps_active():
             return False
         c1, c2 = self.conv1, self.conv2
-        if c1.out_channels % 64 or c2.out_channels % 64 or c2.in_channels % 16 or tuple(c1.kernel_size) != (3, 3) or tuple(c2.kernel_size) != (3, 3) or max(c1.out_channels, c2.out_channels) > 1024:      # (the kernels keep a layer's bias / scale words in 8 KB of LDS)
+        if tuple(c1.kernel_size) != (3, 3) or tuple(c2.kernel_size) != (3, 3) or not sp_channels_ok(c2.in_channels, c2.out_channels):
             return False
-        if self.stride == 2:
+        if self.stride == 2:            # (conv1 reads Cin % 8 on the consumer-split kernel when Cin % 16 != 0: _forward_split)
             d = self.downsample
-            return d is not None and c1.in_channels % 8 == 0 and d[0].stride[0] == 2 and d[0].in_channels % 16 == 0 and d[0].in_channels <= 256 and d[0].out_channels % 32 == 0
-        return self.stride == 1 and self.downsample is None and c1.in_channels % 16 == 0
+            return (d is not None and sp_channels_ok(None, c1.out_channels) and c1.in_channels % 8 == 0 and d[0].stride[0] == 2 and d[0].in_channels % 16 == 0
+                    and d[0].in_channels <= 256 and d[0].out_channels % 32 == 0)
+        return self.stride == 1 and self.downsample is None and sp_channels_ok(c1.in_channels, c1.out_channels)
 
     def _forward_split(self, x, out_channels_last: bool, out_both: bool = False, x_split=None):
         """conv1 -> SplitMap -> conv2 (+ skip) -> SplitMap, or channels-last float32 at the end of a stage (resblock.py:53-69)."""
         w1, b1, w2, b2, wd, p1, p2, pd = self._folded()
         if self.stride == 2:
             s2 = S2_SPLIT if p1.cin % 16 == 0 else "0"
-            fused = S2_SKIP and wd.shape[0] == p1.cout and p1.cout <= 512 and tuple(wd.shape[2:]) == (1, 1)      # the skip as a tenth tap of the strided launch
+            fused = S2_SKIP and wd.shape[0] == p1.cout and sp_channels_ok(p1.cin, p1.cout, skip=True) and tuple(wd.shape[2:]) == (1, 1)      # the skip as a tenth tap of the strided launch
             if isinstance(x, ops.SparseCanvas):
                 skip = None
                 if s2 in ("sparse", "all") and p1.cin >= 32:
@@ -646,7 +659,7 @@ class DoubleConv(nn.Module):
         """Both layers are 3x3 / stride 1 / pad 1 with channel counts the SplitMap kernel serves, and the fp16 route is on: forward() then accepts an
         ``ops.SplitMap`` (the up-sampling heads' output, round 5) and runs BOTH convolutions on ``conv3x3_sp``."""
         c1, c2 = self.double_conv[0], self.double_conv[2]
-        ok = lambda c: c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1) and c.out_channels % 64 == 0 and c.in_channels % 16 == 0
+        ok = lambda c: c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1) and sp_channels_ok(c.in_channels, c.out_channels)
         return bool(HEAD_SPLIT_MAPS and split_maps_active() and not self.training and ok(c1) and ok(c2) and c1.weight.is_cuda)
 
     def forward(self, x, out_split: bool = False):
@@ -667,7 +680,7 @@ class DoubleConv(nn.Module):
                 return (Conv3x3Pack(c1.weight.detach()) if ok(c1) else None, Conv3x3Pack(c2.weight.detach()) if ok(c2) else None)
             p1, p2 = _cache_of(self).get([c1.weight, c2.weight], build)
             x = x.contiguous()
-            if split_maps_active() and p1 is not None and p2 is not None and p1.cin % 16 == 0 and p2.cin % 16 == 0:
+            if split_maps_active() and p1 is not None and p2 is not None and sp_channels_ok(p1.cin, p1.cout) and sp_channels_ok(p2.cin, p2.cout):
                 # round 5: the first convolution splits its own (float32, concatenated) input and writes a SplitMap, the second one reads it by LDS-DMA and
                 # writes the channels-last float32 map the 1x1 heads read
                 y = ops.conv3x3_emu_bias_act(x, p1.emu(16, True), c1.bias, p1.cout, None, True, 16, out_split=True)

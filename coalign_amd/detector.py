@@ -68,9 +68,14 @@ def heads_take_split_map(model: nn.Module, x=None) -> bool:
     from . import backbone as _bb
     if not _bb.HEADS_SPLIT_IN or model.training or not _bb.split_maps_active():
         return False
+    return heads_sp_shape_ok(model) and model.cls_head.weight.is_cuda
+
+
+def heads_sp_shape_ok(model: nn.Module) -> bool:
+    """The merged heads' shape fits ``coalign_heads_sp``: 1 x 1 heads of at most 32 rows in all (``ops.HEADS_SP_MAX_ROWS``) over Cin % 16 == 0 channels."""
     heads = [model.cls_head, model.reg_head] + ([model.unc_head] if getattr(model, "unc_head", None) is not None else []) + ([model.dir_head] if model.use_dir else [])
     rows = sum(h.out_channels for h in heads)
-    return rows <= 32 and model.cls_head.in_channels % 16 == 0 and all(tuple(h.kernel_size) == (1, 1) for h in heads) and model.cls_head.weight.is_cuda
+    return rows <= ops.HEADS_SP_MAX_ROWS and model.cls_head.in_channels % 16 == 0 and all(tuple(h.kernel_size) == (1, 1) for h in heads)
 
 
 def _single_agent_batch(data_dict: dict) -> dict:

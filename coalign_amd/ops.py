@@ -49,6 +49,20 @@ def _stream() -> ctypes.c_void_p:
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _device_tensor(a) -> Optional[torch.Tensor]:
+    """The GPU tensor that places an op's argument ``a`` (``_device_op``): a CUDA tensor itself, the storage of this module's map / buffer types, the first
+    such tensor in a list or tuple (``pointwise_heads_split``'s layers, ``warp_fuse_nhwc``'s maps); None for anything on the host."""
+    if isinstance(a, DecodeBuffers):
+        a = a.counts
+    elif isinstance(a, SparseCanvas):
+        a = a.feats
+    elif isinstance(a, SplitMap):
+        a = a.data
+    elif isinstance(a, (list, tuple)):
+        return next((t for t in map(_device_tensor, a) if t is not None), None)
+    return a if torch.is_tensor(a) and a.is_cuda else None
+
+
 def _device_op(fn):
     """Run ``fn`` with the device of its first GPU tensor argument current: outputs / workspaces are allocated there, and the
     kernels go to THAT device's current stream (not to the stream of whatever device happens to be current in the caller)."""
@@ -57,11 +71,8 @@ def _device_op(fn):
     @functools.wraps(fn)
     def wrapper(*args, **kwargs):
         for a in args:
-            if isinstance(a, DecodeBuffers):
-                a = a.counts
-            elif isinstance(a, SparseCanvas):
-                a = a.feats
-            if torch.is_tensor(a) and a.is_cuda:
+            a = _device_tensor(a)
+            if a is not None:
                 if a.device.index != torch.cuda.current_device():
                     with torch.cuda.device(a.device):
                         return fn(*args, **kwargs)
@@ -1215,7 +1226,6 @@ def pointwise_conv(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, 
 
 
 @_device_op
-@_device_op
 def pointwise_heads_split(layers, out: "SplitMap", relu: bool = True) -> "SplitMap":
     """The up-sampling heads of all scales in ONE launch (``coalign_pointwise_conv_emu_sp_multi``, include/coalign_amd.h (10d)): ``layers`` = [(x, w_emu, bias, cout,
     up, c_off), ...] (at most four), each writing its channel slice of the SplitMap ``out``.  Bit-identical to one ``pointwise_conv(..., out=out)`` per layer."""
@@ -1242,10 +1252,13 @@ def pointwise_heads_split(layers, out: "SplitMap", relu: bool = True) -> "SplitM
     return out
 
 
+HEADS_SP_MAX_ROWS = 32                             # coalign_heads_sp: the merged heads' rows fill half of one 64-row weight tile
+
+
 def pack_heads_sp_weight(weight: torch.Tensor) -> torch.Tensor:
     """[M <= 32, Cin(, 1, 1)] merged head weights -> the image ``heads_sp`` reads (include/coalign_amd.h (10e)): ``pack_conv1x1_sp_weight`` of the weights padded to 64 rows."""
     w = weight.detach().float().reshape(weight.shape[0], weight.shape[1])
-    if w.shape[0] > 32:
+    if w.shape[0] > HEADS_SP_MAX_ROWS:
         raise ValueError("heads_sp serves at most 32 head channels")
     pad = torch.zeros((64, w.shape[1]), dtype=torch.float32, device=w.device)
     pad[: w.shape[0]] = w
@@ -1268,6 +1281,7 @@ def heads_sp(x: "SplitMap", w_sp: torch.Tensor, bias: torch.Tensor, M: int) -> t
     return y
 
 
+@_device_op
 def boxes_overlap_bev(boxes_a: torch.Tensor, boxes_b: torch.Tensor) -> torch.Tensor:
     """OpenPCDet-semantics fp32 BEV overlap AREA matrix [Na, Nb] of (x, y, z, dx, dy, dz, heading) boxes."""
     _need_gpu(boxes_a, boxes_b)

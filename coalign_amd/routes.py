@@ -103,7 +103,7 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS) -> Dict[str, object]:
                     layers[f"{n}.conv2"] = SP
             elif isinstance(m, bb.DoubleConv):
                 c1, c2 = m.double_conv[0], m.double_conv[2]
-                ok = all(tuple(c.kernel_size) == (3, 3) and c.stride == (1, 1) and c.out_channels % 64 == 0 and c.in_channels % 16 == 0 for c in (c1, c2))
+                ok = all(tuple(c.kernel_size) == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1) and bb.sp_channels_ok(c.in_channels, c.out_channels) for c in (c1, c2))
                 if ok and f"{n}.double_conv.0" in layers:
                     from_heads = (m is first_shrink and bb.HEAD_SPLIT_MAPS and heads_ok and len(backbone.deblocks) == backbone.num_levels
                                   and all(backbone.deblocks[i][0].in_channels % 16 == 0 and backbone.deblocks[i][0].out_channels % 16 == 0 for i in range(backbone.num_levels)))

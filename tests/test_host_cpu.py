@@ -51,6 +51,8 @@ def test_argument_validation_without_a_gpu():
     assert lib.coalign_conv3x3_sp(null, one, one, null, 0, one, 1, 1, 64, 64, 8, 8, 1, 0, null, null, 0, null) == -1                    # no input map
     assert lib.coalign_conv3x3_sp(one, one, one, null, 0, one, 1, 1, 24, 64, 8, 8, 1, 0, null, null, 0, null) == -3                     # Cin % 16: unsupported
     assert lib.coalign_conv3x3_sp(one, one, one, null, 0, one, 3, 1, 64, 64, 8, 8, 1, 0, null, null, 0, null) == -3                     # unknown output kind
+    assert lib.coalign_conv3x3_sp(one, one, one, null, 0, one, 1, 1, 64, 1088, 8, 8, 1, 0, null, null, 0, null) == -3                   # Cout > 1024: its bias / scale words exceed the LDS
+    assert lib.coalign_conv3x3_sp(one, one, one, null, 0, one, 1, 0, 64, 1024, 8, 8, 1, 0, null, null, 0, null) == 0                    # Cout 1024, no images: nothing to do
     assert lib.coalign_sp_map_bytes(5, 256, 25, 88) == 5 * 256 * 25 * 88 * 4 and lib.coalign_sp_map_bytes(5, 24, 25, 88) == 0
     assert lib.coalign_pointwise_conv_emu_sp(one, one, one, one, 1, 64, 8, 8, 1, 120, 1, 128, 384, 0, 1, 1, null, null) == -3          # Cout % 16
     assert lib.coalign_pointwise_conv_emu_sp(one, one, one, one, 1, 64, 8, 8, 1, 128, 1, 128, 384, 8, 1, 1, null, null) == -3          # c_off % 16

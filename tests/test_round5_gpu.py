@@ -18,6 +18,7 @@ from coalign_amd.config import builtin_config
 from coalign_amd.detector import build_model, to_device
 from coalign_amd.postprocess import build_postprocessor
 from coalign_amd.synthetic import calibrate_heads_, fill_parameters_trained_like_, make_frame
+from sp_helpers import assert_split_map_holds, round22  # noqa: F401  (round22: also read by tests/test_round6_gpu.py)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -182,19 +183,6 @@ def test_trained_like_parameters_vs_oracle_default_arithmetic(case):
 
 
 # ------------------------------------------------------------------------------------------------ SplitMaps and the producer-split convolution
-def round22(x):
-    return ((x.contiguous().view(torch.int32) + 2) & -4).view(torch.float32)
-
-
-def assert_split_map_holds(sm, want, what=""):
-    """A SplitMap holds `want` rounded to 22 significant bits: exactly for |value| >= 2^-13, to an absolute 2^-33 below (csrc/common.h)."""
-    got, w22 = sm.dense(), round22(want)
-    big = want.abs() >= 2.0 ** -13
-    assert torch.equal(got[big], w22[big]), what
-    if bool((~big).any()):
-        assert float((got[~big] - want[~big]).abs().max()) <= 2.0 ** -33, what
-
-
 def test_split_map_pack_unpack_and_layout():
     """unpack(pack(x)) = x rounded to 22 significant bits (ties away), from NCHW and channels-last inputs, to both output layouts; the unpack kernel agrees
     with the layout's definition evaluated in torch (SplitMap.dense_reference); re-packing a packed map reproduces it bit for bit (pairs are canonical)."""
@@ -250,7 +238,20 @@ def test_conv3x3_sp_equals_consumer_split_kernel_bit_for_bit(shape, geometry):
     assert not ops.sp_range_exceeded(DEV)
 
 
-@pytest.mark.parametrize("shape", [(5, 64, 64, 100, 352), (5, 128, 128, 50, 176), (5, 256, 256, 25, 88), (1, 256, 256, 100, 352), (2, 64, 64, 100, 252), (2, 256, 256, 25, 63)])
+# dispatch_sp's geometry = 0 rule (csrc/conv3x3_sp.hip) on the backbone shapes (ids shape0 ... shape5: 121, 124, 148, 81 + the automatic stream-K cut, 121 -> 81,
+# the remaining 81) and on shapes that reach its other branches.  The 12-wavefront fallbacks depend on the CU count: the ids assume the MI355X's 256.
+SP_GEO0_SHAPES = [pytest.param(s, id=f"shape{i}") for i, s in enumerate([(5, 64, 64, 100, 352), (5, 128, 128, 50, 176), (5, 256, 256, 25, 88), (1, 256, 256, 100, 352),
+                                                                          (2, 64, 64, 100, 252), (2, 256, 256, 25, 63)])] + [
+    pytest.param((1, 64, 64, 30, 48), id="124_to_148_few_tiles"),
+    pytest.param((1, 64, 64, 64, 40), id="121_to_148_few_tiles"),
+    pytest.param((1, 128, 64, 64, 64), id="81_one_image_long_tiles_whole"),
+    pytest.param((3, 64, 128, 5, 40), id="81_short_maps"),
+    pytest.param((1, 256, 1024, 64, 72), id="81_one_image_stream_k_cut_cout1024"),
+]
+SP_GEO0_CUT = {(1, 256, 256, 100, 352), (1, 256, 1024, 64, 72)}      # the shapes whose tiles the product's launch cuts (stream-K) on 256 CUs
+
+
+@pytest.mark.parametrize("shape", SP_GEO0_SHAPES)
 def test_conv3x3_sp_backbone_shapes_bit_equal_and_against_float64(shape):
     """The stride-1 backbone shapes with the geometry the product picks: bit-equal to the consumer-split kernel, error against float64 <= 2e-6 of the scale."""
     N, Ci, Co, H, W = shape
@@ -267,10 +268,12 @@ def test_conv3x3_sp_backbone_shapes_bit_equal_and_against_float64(shape):
     ref = conv64(x, w, b, r)
     scale = float(ref.abs().max())
     whole = ops.conv3x3_sp(xs, w16, b, Co, rs, True, out_split=False, geometry=100000)
-    if shape != (1, 256, 256, 100, 352):                          # (there the consumer-split kernel itself hands long tiles over between workgroups: another summation order)
+    consumer_cut = ops.hip.lib().coalign_conv3x3_emu_workspace_bytes_ex(N, Ci, Co, H, W, 16, ops.LAYOUT_W_TAPMAJOR) > 0
+    if not consumer_cut:                                          # (where the consumer-split kernel itself hands tiles over between workgroups: another summation order)
         assert torch.equal(whole, want)
     assert float((whole - want).abs().max()) / scale < 1e-6
-    if ops.conv3x3_sp_is_split(N, Ci, Co, H, W):                  # the product's launch cuts this shape's tiles (stream-K): same sums, another order, deterministic
+    assert ops.conv3x3_sp_is_split(N, Ci, Co, H, W) == (shape in SP_GEO0_CUT), shape
+    if shape in SP_GEO0_CUT:                                      # the product's launch cuts this shape's tiles (stream-K): same sums, another order, deterministic
         assert float((got - whole).abs().max()) / scale < 1e-6
         assert torch.equal(got, ops.conv3x3_sp(xs, w16, b, Co, rs, True, out_split=False))
     else:

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from coalign_amd import backbone, ops
+from sp_helpers import sparse_canvas as _sparse_canvas
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -60,29 +61,6 @@ def test_strided_split_convolution_against_float64():
     err = float((got - ref).abs().max()) / float(ref.abs().max())
     print(f"\nconv3x3_sp_s2 vs float64: {err:.2e} of the scale")
     assert err <= 2e-6
-
-
-def _sparse_canvas(n_agents, ny, nx, pillars, seed, count_below_capacity=False):
-    """A SparseCanvas from the one-launch pillar op on random pillars (duplicate cells included: the larger row wins)."""
-    from coalign_amd.config import builtin_config
-    from coalign_amd.detector import build_model
-    from coalign_amd.synthetic import fill_parameters_, make_frame
-    h = builtin_config("opv2v_coalign")
-    model = build_model(h)
-    fill_parameters_(model, seed=seed)
-    model = model.to(DEV).eval()
-    margs = h["model"]["args"]
-    pl = make_frame(h, n_agents, pillars_per_agent=pillars, seed=seed)["processed_lidar"]
-    pfn = model.pillar_vfe.pfn_layers[0]
-    bn = (pfn.norm.weight, pfn.norm.bias, pfn.norm.running_mean, pfn.norm.running_var)
-    gx, gy, _ = [int(v) for v in margs["point_pillar_scatter"]["grid_size"]]
-    assert (gy, gx) == (ny, nx)
-    count_dev = None
-    vf, npts, coords = pl["voxel_features"].to(DEV), pl["voxel_num_points"].to(DEV), pl["voxel_coords"].to(DEV)
-    if count_below_capacity:
-        count_dev = torch.tensor([vf.shape[0] - 1234], dtype=torch.int32, device=DEV)
-    return ops.pillar_encode_sparse(vf, npts, coords, pfn.linear.weight, None, bn, 1e-3, True, margs["voxel_size"], margs["lidar_range"][:3], n_agents, ny, nx, canvas_cache={},
-                                    count_dev=count_dev)
 
 
 @pytest.mark.parametrize("pillars,below", [(8000, False), (3000, True), (40000, False)])
@@ -161,28 +139,49 @@ def test_32_channel_tiles_are_bit_equal_to_the_64_channel_geometries_and_both_ou
             assert torch.equal(y, cl) and torch.equal(ysp.data, ops.SplitMap.pack(y).data) and torch.equal(ysp.data, want.data), (shape, geo)
 
 
-@pytest.mark.parametrize("N,hw", [(1, (100, 352)), (2, (48, 72))])
-def test_heads_in_one_launch_equal_one_launch_per_scale(N, hw):
-    """Round 6: ``coalign_pointwise_conv_emu_sp_multi`` -- the three up-sampling heads (base_bev_backbone_resnet.py:121-138) as one launch write the same SplitMap,
-    bit for bit, as one ``coalign_pointwise_conv_emu_sp`` launch per scale."""
+# (Cin, up, Cout) per layer, and the order of their channel slices in the concatenated map: the shipped three scales, one layer, two and four (kMultiMax)
+# layers with their slices out of order, channels-last and NCHW inputs
+HEAD_SETS = {"shipped": (((64, 1, 128), (128, 2, 128), (256, 4, 128)), (0, 1, 2)),
+             "one": (((64, 1, 128),), (0,)),
+             "two_reversed": (((128, 2, 64), (64, 1, 128)), (1, 0)),
+             "four_permuted": (((64, 1, 64), (128, 2, 32), (256, 4, 16), (32, 1, 96)), (2, 0, 3, 1))}
+
+
+@pytest.mark.parametrize("N,hw,heads", [pytest.param(1, (100, 352), None, id="1-hw0"), pytest.param(2, (48, 72), None, id="2-hw1")]
+                         + [pytest.param(n, hw, k, id=f"{n}-{hw[0]}x{hw[1]}-{k}") for k in ("one", "two_reversed", "four_permuted") for n, hw in ((1, (100, 352)), (2, (48, 72)))])
+def test_heads_in_one_launch_equal_one_launch_per_scale(N, hw, heads):
+    """Round 6: ``coalign_pointwise_conv_emu_sp_multi`` -- the up-sampling heads (base_bev_backbone_resnet.py:121-138) as one launch write the same SplitMap,
+    bit for bit, as one ``coalign_pointwise_conv_emu_sp`` launch per scale, for 1 ... 4 layers with their slices in any order, ReLU on and off; each slice within 3e-6 of
+    its channel's scale (+ the pairs' absolute 2^-33) of a float64 ConvTranspose2d of the layer's input."""
     from coalign_amd.backbone import PointwisePack
     H, W = hw
-    g = torch.Generator(device=DEV).manual_seed(N + H)
-    layers, c_off = [], 0
-    for cin, up in ((64, 1), (128, 2), (256, 4)):
-        x = torch.relu(torch.randn((N, cin, H // up, W // up), generator=g, device=DEV)).contiguous(memory_format=torch.channels_last)
-        wt = torch.randn((cin, 128, up, up), generator=g, device=DEV) / cin ** 0.5            # ConvTranspose2d weight [Cin, Cout, k, k]
-        b = torch.randn(128, generator=g, device=DEV) * 0.1
-        layers.append((x, PointwisePack(wt, True).get(), b, 128, up, c_off))
-        c_off += 128
-    want = ops.SplitMap.empty(N, c_off, H, W, DEV)
-    for (x, im, b, cout, up, off) in layers:
-        ops.pointwise_conv(x, im, b, cout, up=up, relu=True, out=want, c_off=off)
-    got = ops.SplitMap.empty(N, c_off, H, W, DEV)
-    got.data.fill_(float("nan"))
-    ops.pointwise_heads_split(layers, got)
-    assert torch.equal(got.data, want.data)
-    assert float(got.dense().abs().max()) > 0
+    specs, order = HEAD_SETS[heads or "shipped"]
+    g = torch.Generator(device=DEV).manual_seed(N + H + len(specs) * 7 * (heads is not None))
+    offs, c = [0] * len(specs), 0
+    for i in order:
+        offs[i], c = c, c + specs[i][2]
+    layers, pres = [], []
+    for i, (cin, up, cout) in enumerate(specs):
+        x = torch.relu(torch.randn((N, cin, H // up, W // up), generator=g, device=DEV))
+        x = x.contiguous(memory_format=torch.channels_last) if i % 2 == 0 or heads is None else x
+        wt = torch.randn((cin, cout, up, up), generator=g, device=DEV) / cin ** 0.5            # ConvTranspose2d weight [Cin, Cout, k, k]
+        b = torch.randn(cout, generator=g, device=DEV) * 0.1
+        layers.append((x, PointwisePack(wt, True).get(), b, cout, up, offs[i]))
+        pres.append(torch.nn.functional.conv_transpose2d(x.double(), wt.double(), b.double(), stride=up))
+    for relu in (True, False):                                   # (ReLU off: the negative outputs are compared too)
+        want = ops.SplitMap.empty(N, c, H, W, DEV)
+        for (x, im, b, cout, up, off) in layers:
+            ops.pointwise_conv(x, im, b, cout, up=up, relu=relu, out=want, c_off=off)
+        got = ops.SplitMap.empty(N, c, H, W, DEV)
+        got.data.fill_(float("nan"))
+        ops.pointwise_heads_split(layers, got, relu=relu)
+        assert torch.equal(got.data, want.data), relu
+        dense = got.dense().double()
+        assert float(dense.abs().max()) > 0 and (relu or float(dense.min()) < 0)
+        for (x, im, b, cout, up, off), pre in zip(layers, pres):
+            scale = pre.abs().amax(dim=(0, 2, 3), keepdim=True)
+            err = (dense[:, off:off + cout] - (torch.relu(pre) if relu else pre)).abs()
+            assert not bool((err > 3e-6 * scale + 2.0 ** -33).any()), (heads, relu, off, float((err / scale).max()))
 
 
 @pytest.mark.parametrize("shape", [(5, 64, 128, 100, 352), (5, 128, 256, 50, 176), (2, 32, 64, 37, 45), (1, 64, 64, 9, 70)])
@@ -238,16 +237,20 @@ def test_skip_as_a_tenth_tap_on_the_sparse_canvas_and_in_the_model():
         assert e <= 2e-6
 
 
-@pytest.mark.parametrize("shape", [(1, 256, 20, 100, 352), (2, 64, 32, 37, 45), (1, 128, 6, 9, 70)])
+@pytest.mark.parametrize("shape", [(1, 256, 20, 100, 352), (2, 64, 32, 37, 45), (1, 128, 6, 9, 70), (2, 16, 1, 9, 70), (1, 1024, 31, 13, 131), (2, 1024, 32, 9, 40),
+                                   (1, 16, 32, 1, 3)])
 def test_merged_heads_on_a_split_map(shape):
     """Round 6 (10e): ``coalign_heads_sp`` -- the merged 1 x 1 heads (point_pillar_baseline_multiscale.py:123-133) on the shrink header's SplitMap against a float64
-    product of the same 22-bit values: within 2e-6 of the scale."""
+    product of the same 22-bit values: within 2e-6 of the scale, per head row; M = 1 ... 32 (its maximum), Cin 16 ... 1024, rows on scales four decades apart."""
     N, Ci, M, H, W = shape
     g = torch.Generator(device=DEV).manual_seed(sum(shape))
     x = ops.SplitMap.pack(torch.relu(torch.randn((N, Ci, H, W), generator=g, device=DEV)))
     w = torch.randn((M, Ci, 1, 1), generator=g, device=DEV) / Ci ** 0.5
     w[M // 2] *= 1e-3                                            # a head channel three decades below the others: the per-row power-of-two scale
     b = torch.randn(M, generator=g, device=DEV)
+    if Ci in (16, 1024):                                          # every row on its own scale, 1e-4 ... 1, bias included (the per-row scale words)
+        rs = torch.logspace(-4, 0, M, device=DEV)[torch.randperm(M, generator=g, device=DEV)]
+        w, b = w * rs.view(-1, 1, 1, 1), b * rs
     got = ops.heads_sp(x, ops.pack_heads_sp_weight(w), b, M)
     ref = torch.einsum("oc,nchw->nohw", w[:, :, 0, 0].double(), x.dense().double()) + b.double().view(1, -1, 1, 1)
     assert got.shape == ref.shape and got.is_contiguous()
