@@ -154,8 +154,10 @@ __global__ __launch_bounds__(MAXT, (NA > 5 && MAXT <= 512) ? 2 : ((CPT == 8 && N
         const int big = 1 << 28;
         const int xmin = wave_min(live ? x0 : big), xmax = wave_max(live ? x0 + 1 : -big);
         const int ymin = wave_min(live ? y0 : big), ymax = wave_max(live ? y0 + 1 : -big);
+        // An agent with no live pixel in the tile still stages a 2 x 4 box at the plane's origin: its taps (patch index 0, weight 0) then
+        // read values of the map, not whatever an earlier workgroup left in the slab (0 * NaN = NaN, 0 * Inf = NaN).
         Origin o;
-        o.ax0 = 0; o.py0 = 0; o.nc4 = 1; o.nrows = 0; o.fit = 1;
+        o.ax0 = 0; o.py0 = 0; o.nc4 = 1; o.nrows = 2; o.fit = 1;
         if (xmin != big) {
             o.ax0 = (xmin >> 2) << 2;                  // floor to a multiple of 4 (also for -1)
             o.py0 = ymin;

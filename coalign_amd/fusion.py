@@ -55,10 +55,11 @@ def fuse_multiscale(xs: Sequence[torch.Tensor], record_len, affine: torch.Tensor
     """All feature scales of a batch in ONE launch per frame when every map is channels-last (the route the split-bf16 backbone
     produces): -> list of fused maps [B, C_s, H_s, W_s] (channels-last), or None when the maps do not qualify (caller falls back
     to one ``coalign_warp_fuse`` launch per scale)."""
-    if len(xs) > 3 or not all(ops.warp_fuse_nhwc_ok(x) for x in xs):
+    # (the map predicate on the first 8 rows: the 8-agent limit is per frame, checked below; a batch may hold more agents in all)
+    if len(xs) > 3 or not all(ops.warp_fuse_nhwc_ok(x[:8]) for x in xs):
         return None
     groups = host_ints(record_len)
-    if sum(groups) != xs[0].shape[0] or max(groups) > 8:
+    if any(x.shape[0] != xs[0].shape[0] for x in xs) or sum(groups) != xs[0].shape[0] or max(groups) > 8:
         return None
     outs, off = [], 0
     for b, n in enumerate(groups):

@@ -77,6 +77,24 @@ def test_argument_validation_without_a_gpu():
     assert lib.coalign_heads_sp(null, one, one, one, 1, 256, 20, 8, 8, null) == -1 and lib.coalign_heads_sp(one, one, one, one, 1, 256, 40, 8, 8, null) == -3      # no map; more than 32 head channels
     assert lib.coalign_heads_sp(one, one, one, one, 1, 250, 20, 8, 8, null) == -3 and lib.coalign_heads_sp(one, one, one, one, 0, 256, 20, 8, 8, null) == 0
     assert lib.coalign_conv3x3_sp_both(one, one, one, null, 0, one, ctypes.c_void_p(24), 1, 64, 64, 8, 8, 1, 0, null, null, 0, null) == -3      # ... not 16-byte aligned
+    # the fusion entry points' refusals that fusion.py's routes rely on (group / row / per-scale arguments are host arrays the entry points read)
+    i32 = lambda *v: (ctypes.c_int32 * len(v))(*v)                                                                    # noqa: E731
+    fuse_rows = lambda n, C, groups, rows: lib.coalign_warp_fuse_rows(one, n, C, 8, 8, one, groups, len(groups), rows, 0, one, 8, 8, null)  # noqa: E731
+    assert fuse_rows(4, 257, i32(4), None) == -3                                 # C > 256
+    assert fuse_rows(9, 64, i32(9), None) == -3                                  # a frame of 9 agents
+    assert fuse_rows(7, 64, i32(4, 2), None) == -2                               # group_len does not sum to n_total
+    assert fuse_rows(6, 64, i32(4, 2), i32(0, 2, 2, 1, 1, 0)) == -2              # a row repeated inside the first frame
+    assert fuse_rows(6, 64, i32(4, 2), i32(3, 0, 2, 1, 2, 0)) == -2              # a row outside its frame
+    vp = lambda k: (ctypes.c_void_p * k)(*([16] * k))                                                               # noqa: E731
+    fuse_nhwc = lambda k, C, n: lib.coalign_warp_fuse_nhwc(k, vp(k), i32(*[C] * k), i32(*[8] * k), i32(*[8] * k), vp(k), i32(*[8] * k),  # noqa: E731
+                                                           i32(*[8] * k), n, one, None, 0, null)
+    assert fuse_nhwc(1, 96, 4) == -3                                             # C not in {64, 128, 256}
+    assert fuse_nhwc(1, 64, 9) == -3                                             # 9 agents
+    assert fuse_nhwc(4, 64, 4) == -2                                             # 4 scales
+    from coalign_amd import fusion
+    aff = torch.zeros(1, 4, 4, 2, 3, dtype=torch.float64)
+    assert fusion.fuse_multiscale([torch.zeros(4, 96, 8, 8).contiguous(memory_format=torch.channels_last)], [4], aff, ops.FUSE_ATT) is None    # no channels-last device map: the caller falls back
+    assert fusion.fuse_multiscale([torch.zeros(4, 64, 8, 8)], [4], aff, ops.FUSE_MAX) is None
 
 
 def test_ops_have_no_cpu_fallback():
