@@ -9,7 +9,9 @@ layer routed to a hand-written gfx950 kernel where one takes its shape.
 * the stride-2 1x1 skip convolutions and the up-sampling heads (ConvTranspose2d with kernel = stride, written straight into their
   slice of the concatenated map): ``coalign_pointwise_conv_emu`` / ``coalign_pointwise_conv`` (``csrc/pointwise.hip``, ``PointwisePack``).
 * the last convolution of every ResNet stage writes channels-last for the one-launch fusion kernel (``NHWC_STAGE_OUTPUTS``).
-* what no kernel takes (``Cout % 64``, ``Cin % 8``, the NaiveCompressor, the 1x1 heads) runs on MIOpen / rocBLAS with ``bias_act_`` as the
+* the NaiveCompressor (row D): its 64 -> 64 / r encoder on ``coalign_conv3x3_sp_narrow`` (``csrc/conv3x3_narrow.hip``: 16 or 32 output channels, SplitMap out),
+  its two decoder layers on ``coalign_conv3x3_sp`` (``NaiveCompressor._forward_split``).
+* what no kernel takes (``Cout % 64``, ``Cin % 8``, a compressor outside the SplitMap route, the 1x1 heads) runs on MIOpen / rocBLAS with ``bias_act_`` as the
   epilogue; ``coalign_amd.routes.plan(hypes)`` lists the route of every layer of a config without a GPU.
 
 Parameter / buffer names are kept identical to the reference so that its
@@ -126,6 +128,13 @@ def sp_channels_ok(cin: Optional[int], cout: int, skip: bool = False) -> bool:
     """A 3x3 layer of (cin, cout) fits the SplitMap kernels (``cin`` None: the output side only); ``skip``: with the block's 1 x 1 / stride-2 skip convolution
     fused as a tenth tap."""
     return cout % 64 == 0 and 0 < cout <= (SP_MAX_COUT_SKIP if skip else SP_MAX_COUT) and (cin is None or (cin > 0 and cin % 16 == 0))
+
+
+# The limits of the narrow-output SplitMap convolution (csrc/conv3x3_narrow.hip, include/coalign_amd_narrow.h): one 16- or 32-channel output tile, 16-channel
+# input chunks.  NaiveCompressor's route and routes.plan ask narrow_channels_ok, as the 64-channel kernels' callers ask sp_channels_ok.
+def narrow_channels_ok(cin: int, cout: int) -> bool:
+    """A 3x3 / stride 1 layer of (cin, cout) fits ``coalign_conv3x3_sp_narrow`` (``cout``: the padded width the kernel is called with)."""
+    return cout in ops.NARROW_COUTS and cin > 0 and cin % 16 == 0
 
 
 def winograd_active() -> bool:
@@ -342,7 +351,7 @@ class BasicBlock(nn.Module):
                     skip = ops.pointwise_conv_sparse(x, pd[0].get(), pd[1], wd.shape[0], False, out_channels_last=True)
             else:
                 xs = x if isinstance(x, ops.SplitMap) else x_split
-                if isinstance(x, ops.SplitMap):
+                if isinstance(x, ops.SplitMap) and not (s2 == "all" and fused):      # (the fused strided launch reads the SplitMap alone: NaiveCompressor's output)
                     x = x.dense(channels_last=True)
                 skip = None
                 if s2 == "all":
@@ -716,7 +725,13 @@ class DownsampleConv(nn.Module):
 
 
 class NaiveCompressor(nn.Module):
-    """Channel auto-encoder emulating feature compression (naive_compress.py:5-31)."""
+    """Channel auto-encoder emulating feature compression (naive_compress.py:5-31).
+
+    SplitMap route (eval mode, ``split_maps_active()``, a float32 CUDA tensor or a SplitMap in; SURVEY 8a row D): with mid = input_dim // ratio and Cp = mid
+    rounded up to 16, the encoder runs on ``ops.conv3x3_sp_narrow`` when Cp <= 32 (weights and bias zero-padded from mid to Cp output channels: the padded
+    channels of the mid map are exactly 0) and both decoder layers on ``ops.conv3x3_sp`` (the first one at Cin = Cp, weights zero-padded on the input side);
+    a wider mid is padded to a multiple of 64 and all three layers run on ``ops.conv3x3_sp``.  Everything else -- input_dim % 64 != 0, another arithmetic mode,
+    training, CPU, half / float64 -- keeps the library route below."""
 
     def __init__(self, input_dim: int, compress_ratio: int):
         super().__init__()
@@ -728,7 +743,54 @@ class NaiveCompressor(nn.Module):
         self.encoder = nn.Sequential(*cbr(input_dim, mid))
         self.decoder = nn.Sequential(*cbr(mid, input_dim), *cbr(input_dim, input_dim))
 
-    def forward(self, x):
+    def split_widths(self) -> Optional[tuple]:
+        """(kind, padded mid width) of the SplitMap route from the channel counts alone: ("narrow", 16 | 32), ("wide", a multiple of 64), or None when a layer
+        fits no SplitMap kernel."""
+        cin, mid = self.encoder[0].in_channels, self.encoder[0].out_channels
+        if mid < 1 or not sp_channels_ok(cin, cin):               # (both decoder layers write `cin` channels with the 64-channel tile)
+            return None
+        cp = (mid + 15) // 16 * 16
+        if narrow_channels_ok(cin, cp):
+            return ("narrow", cp) if sp_channels_ok(cp, cin) else None
+        cw = (mid + 63) // 64 * 64
+        return ("wide", cw) if sp_channels_ok(cin, cw) and sp_channels_ok(cw, cin) else None
+
+    def takes_split_maps(self) -> bool:
+        return bool(FAST_INFERENCE and not self.training and split_maps_active() and self.split_widths() is not None)
+
+    def _split_images(self):
+        """BatchNorm folded, mid padded: (encoder image or pack, its bias, decoder packs and biases), cached until a parameter or buffer changes."""
+        c = self.__dict__.get("_coalign_split_cache")
+        if c is None:
+            c = self.__dict__["_coalign_split_cache"] = _FoldCache()
+
+        def build():
+            kind, cp = self.split_widths()
+            (we, be), (w1, b1), (w2, b2) = [fold_bn(q[0].weight, q[0].bias, q[1]) for q in (self.encoder, self.decoder[0:3], self.decoder[3:6])]
+            mid, cin = we.shape[0], we.shape[1]
+            wep, bep, w1p = we.new_zeros((cp, cin, 3, 3)), be.new_zeros(cp), w1.new_zeros((w1.shape[0], cp, 3, 3))
+            wep[:mid], bep[:mid], w1p[:, :mid] = we, be, w1
+            enc = ops.pack_conv3x3_narrow_weight(wep) if kind == "narrow" else Conv3x3Pack(wep)
+            return kind, cp, enc, bep, Conv3x3Pack(w1p), b1, Conv3x3Pack(w2), b2
+        return c.get(self, build)
+
+    def _forward_split(self, x, out_split: bool):
+        kind, cp, enc, be, p1, b1, p2, b2 = self._split_images()
+        if kind == "narrow":                                       # a channels-last canvas is split by the kernel's loader, an NCHW one packed by the op
+            y = ops.conv3x3_sp_narrow(x, enc, be, cp, True)
+        else:
+            xs = x if isinstance(x, ops.SplitMap) else ops.SplitMap.pack(x)
+            y = ops.conv3x3_sp(xs, enc.emu(16, True), be, cp, None, True, out_split=True)
+        y = ops.conv3x3_sp(y, p1.emu(16, True), b1, p1.cout, None, True, out_split=True)
+        return ops.conv3x3_sp(y, p2.emu(16, True), b2, p2.cout, None, True, out_split=out_split)
+
+    def forward(self, x, out_split: bool = False):
+        """``out_split``: the caller's next layer reads a SplitMap (the first ResNet block, ``detector.encode``) -- granted on the SplitMap route only; a plain
+        ``module(x)`` always gets a tensor (channels-last memory on the SplitMap route)."""
+        if self.takes_split_maps() and (isinstance(x, ops.SplitMap) or _fast_ok(self, x)):
+            return self._forward_split(x, out_split)
+        if isinstance(x, ops.SplitMap):
+            x = x.dense()
         if _fast_ok(self, x):
             x = x.contiguous()                       # a channels-last canvas is converted once; the convolutions below are NCHW
 

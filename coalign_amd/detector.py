@@ -15,7 +15,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .backbone import BaseBEVBackbone, DownsampleConv, NaiveCompressor, ResNetBEVBackbone, _cache_of, _fast_ok
+from .backbone import BaseBEVBackbone, BasicBlock, DownsampleConv, NaiveCompressor, ResNetBEVBackbone, _cache_of, _fast_ok
 from .encoder import PillarVFE, PointPillarScatter, host_ints
 from .fusion import AttFusion, MaxFusion, fuse_multiscale
 from .pose import normalize_pairwise_tfm
@@ -167,7 +167,10 @@ class PointPillarBaselineMultiscale(nn.Module):
         if affine is None:
             affine = normalize_pairwise_tfm(data_dict["pairwise_t_matrix"], H0, W0, self.voxel_size[0])
         if self.compression:
-            spatial_features = self.naive_compressor(spatial_features)
+            # the compressor hands the first ResNet block a SplitMap when that block reads one: its strided opener + skip then run as one launch on it
+            opener = resnet.layer0[0] if resnet is not None and hasattr(resnet, "layer0") else None
+            want_split = bool(not self.training and isinstance(opener, BasicBlock) and opener.takes_split_maps() and opener.conv1.in_channels % 16 == 0)
+            spatial_features = self.naive_compressor(spatial_features, out_split=True) if want_split else self.naive_compressor(spatial_features)
         return self.backbone.get_multiscale_feature(spatial_features), affine
 
     def _fuse_scales(self, feature_list, record_len, affine, rows=None):

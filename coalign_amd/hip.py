@@ -104,6 +104,12 @@ LAB_SIGNATURES = {
     "coalign_conv3x3_wino": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
 }
 
+# include/coalign_amd_narrow.h: the extension header of ABI version 2 (product library; coalign_amd.h keeps its 68 names): the narrow-output 3x3 convolution
+NARROW_SIGNATURES = {
+    "coalign_conv3x3_narrow_weight_bytes": (c_size_t, [c_int, c_int]),
+    "coalign_conv3x3_sp_narrow": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+}
+
 _LAB_LIB = None
 
 
@@ -130,7 +136,7 @@ def lib() -> ctypes.CDLL:
             raise CoalignHipError(
                 f"{path} is missing and could not be built ({exc}); the CoAlign hot path has no CPU fallback") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES}.items():
         fn = getattr(handle, name)  # AttributeError here == header / library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -154,7 +160,7 @@ def lab_lib() -> ctypes.CDLL:
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(f"{path} is missing and could not be built ({exc})") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **LAB_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **LAB_SIGNATURES}.items():
         fn = getattr(handle, name)
         fn.restype = res
         fn.argtypes = args

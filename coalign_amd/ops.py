@@ -1023,6 +1023,62 @@ def conv3x3_sp(x: "SplitMap", w_split: torch.Tensor, bias: torch.Tensor, cout: i
     return out
 
 
+NARROW_COUTS = (16, 32)                            # output widths of coalign_conv3x3_sp_narrow (include/coalign_amd_narrow.h)
+NARROW_IN_SP, NARROW_IN_NHWC = 0, 1                # in_kind
+
+
+def pack_conv3x3_narrow_weight(weight: torch.Tensor) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] fp32 (Cout 16 or 32, Cin % 16 == 0) -> the weight image of ``coalign_conv3x3_sp_narrow`` as uint8 (include/coalign_amd_narrow.h):
+    [Cin / 16][9 taps][2 terms][2 channel halves][Cout][8 cin] fp16 sp16 pairs of the per-output-channel scaled weights (the scaling and rounding of
+    ``pack_conv3x3_emu_weight``'s terms-16 image: the two images hold the same pairs), 16 zero bytes, [Cout] float32 2^-k_c, [Cout] float32 2^k_c."""
+    co, ci, kh, kw = weight.shape
+    if (kh, kw) != (3, 3) or co not in NARROW_COUTS or ci % 16 or ci < 16:
+        raise ValueError(f"conv3x3_sp_narrow needs 3x3 weights with Cout in {NARROW_COUTS} and Cin % 16 == 0, got {tuple(weight.shape)}")
+    wf = weight.detach().float()
+    w = wf.reshape(co, ci // 16, 2, 8, 9).permute(1, 4, 2, 0, 3)          # [interval, tap, channel half, cout, cin]
+    amax = wf.abs().reshape(co, -1).amax(dim=1)
+    k = torch.where(amax > 0, 14 - torch.frexp(amax)[1], torch.zeros_like(amax, dtype=torch.int32)).clamp(-60, 60).to(torch.int32)
+    scale = torch.ldexp(torch.ones_like(amax), k)
+    ws = (w * scale.reshape(1, 1, 1, co, 1)).contiguous()
+    ws = ((ws.view(torch.int32) + 2) & -4).view(torch.float32)             # 22 significant bits, ties away from zero (sp16_round)
+    hi = ws.half()
+    lo = ((ws - hi.float()) * 1024.0).half()
+    flat = torch.stack([hi, lo], dim=2).contiguous().view(torch.uint8).reshape(-1)      # [interval, tap, term, channel half, cout, cin]
+    tail = [torch.ldexp(torch.ones_like(amax), -k).contiguous().view(torch.uint8).reshape(-1), scale.contiguous().view(torch.uint8).reshape(-1)]
+    out = torch.cat([flat, torch.zeros(16, dtype=torch.uint8, device=flat.device)] + tail)
+    assert out.numel() == hip.lib().coalign_conv3x3_narrow_weight_bytes(ci, co)
+    return out
+
+
+@_device_op
+def conv3x3_sp_narrow(x, w_narrow: torch.Tensor, bias: torch.Tensor, cout: int, relu: bool = True) -> "SplitMap":
+    """y = act(conv3x3(x, w, stride 1, padding 1) + bias) with 16 or 32 output channels, written as a ``SplitMap`` (include/coalign_amd_narrow.h,
+    csrc/conv3x3_narrow.hip: NaiveCompressor's encoder).  ``x``: a SplitMap, or a float32 tensor of logical shape [N, C, H, W] -- read in place when its
+    memory is channels-last (the kernel's loader splits it), packed with ``SplitMap.pack`` first when it is NCHW.  ``w_narrow``: ``pack_conv3x3_narrow_weight``."""
+    if isinstance(x, SplitMap):
+        kind, xt = NARROW_IN_SP, x.data
+        N, Cin, H, W = x.shape
+    else:
+        _need_gpu(x)
+        if x.dim() != 4:
+            raise ValueError("conv3x3_sp_narrow reads a SplitMap or a [N, C, H, W] tensor")
+        N, Cin, H, W = x.shape
+        if nhwc_memory(x):
+            kind, xt = NARROW_IN_NHWC, x
+        else:
+            x = SplitMap.pack(x)
+            kind, xt = NARROW_IN_SP, x.data
+    _need_gpu(xt, w_narrow, bias)
+    L = hip.lib()
+    if cout not in NARROW_COUTS or Cin % 16 or w_narrow.numel() != L.coalign_conv3x3_narrow_weight_bytes(Cin, cout):
+        raise ValueError("conv3x3_sp_narrow needs the narrow weight image of (Cin, Cout), Cout 16 or 32, Cin % 16 == 0")
+    out = SplitMap.empty(N, cout, H, W, xt.device)
+    with _Timed("conv3x3_sp_narrow"):
+        hip.check(L.coalign_conv3x3_sp_narrow(_ptr(xt), kind, _ptr(w_narrow), _ptr(_f32c(bias)), _ptr(out.data), N, Cin, cout, H, W, int(relu),
+                                              _ptr(sp_range_flag(xt.device)), _stream()), "coalign_conv3x3_sp_narrow")
+    return out
+
+
 @_device_op
 def sp_pack_rows(sc: "SparseCanvas") -> torch.Tensor:
     """The feature rows of a ``SparseCanvas`` as sp16 rows [M, C / 16, 4, 8] float16 (``coalign_sp_pack_rows``, include/coalign_amd.h (9f)): what the LDS-DMA

@@ -23,6 +23,8 @@ from .detector import MODEL_REGISTRY, build_model
 EMU, F32, MIOPEN, ROCBLAS, POINTWISE = "conv3x3_emu (split 16-bit matrix cores)", "conv3x3 (fp32 matrix cores) / MIOpen by shape", "MIOpen", "rocBLAS (1x1 heads)", "pointwise"
 WINO = "conv3x3_wino (Winograd F(2x2,3x3), split-bf16 matrix cores)"
 SP = "conv3x3_sp (SplitMap input: operands by LDS-DMA, fp16 x 2)"
+NARROW = "conv3x3_sp_narrow (16 / 32 output channels, weight-stationary, SplitMap out, fp16 x 2)"
+COMPRESSOR_LIBRARY = MIOPEN + " (compressor: SURVEY 8a row D keeps it on the library)"
 DEFAULT_TERMS = 16      # backbone.CONV_EMU_TERMS: the 2-way fp16 split since round 4
 
 
@@ -65,9 +67,17 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS) -> Dict[str, object]:
 
     for n, m in model.named_modules():
         if isinstance(m, bb.NaiveCompressor):
+            # NaiveCompressor.forward: the SplitMap route (the module's own predicate, on the arithmetic `terms` stands for) puts the encoder on the narrow
+            # kernel (padded mid width <= 32) or on conv3x3_sp (wider), both decoder layers on conv3x3_sp; everything else stays on the library
+            m.eval()
+            widths = m.split_widths() if terms == 16 and m.takes_split_maps() else None
             for cn, c in m.named_modules():
                 if isinstance(c, nn.Conv2d):
-                    layers[f"{n}.{cn}"] = MIOPEN + " (compressor: SURVEY 8a row D keeps it on the library)"
+                    if widths is None:
+                        note(f"{n}.{cn}", COMPRESSOR_LIBRARY, True)
+                    else:
+                        pad = f", mid {m.encoder[0].out_channels} zero-padded to {widths[1]}" if widths[1] != m.encoder[0].out_channels else ""
+                        note(f"{n}.{cn}", (NARROW if widths[0] == "narrow" and cn == "encoder.0" else SP) + (pad if cn in ("encoder.0", "decoder.0") else ""), False)
         elif isinstance(m, nn.Conv2d) and "naive_compressor" not in n:
             if tuple(m.kernel_size) == (3, 3):
                 r = _conv3x3_route(m, terms)
