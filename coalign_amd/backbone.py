@@ -12,7 +12,10 @@ layer routed to a hand-written gfx950 kernel where one takes its shape.
 * the NaiveCompressor (row D): its 64 -> 64 / r encoder on ``coalign_conv3x3_sp_narrow`` (``csrc/conv3x3_narrow.hip``: 16 or 32 output channels, SplitMap out),
   its two decoder layers on ``coalign_conv3x3_sp`` (``NaiveCompressor._forward_split``).
 * what no kernel takes (``Cout % 64``, ``Cin % 8``, a compressor outside the SplitMap route, the 1x1 heads) runs on MIOpen / rocBLAS with ``bias_act_`` as the
-  epilogue; ``coalign_amd.routes.plan(hypes)`` lists the route of every layer of a config without a GPU.
+  epilogue.
+Which kernel serves a layer is decided ONCE, from what is known without a tensor (shapes, arithmetic mode, the switches below, read at every call): ``conv3x3_route``,
+``pointwise_split``, ``BasicBlock.route``, ``DoubleConv.on_split_maps``, ``heads_pointwise`` / ``heads_write_split``, ``NaiveCompressor.split_widths``.  ``forward`` dispatches on the
+answer and adds what the tensor says (device, dtype, layout, map size); ``coalign_amd.routes.plan(hypes)`` asks the same functions, with the mode passed in, without a GPU.
 
 Parameter / buffer names are kept identical to the reference so that its
 ``.pth`` checkpoints load (SURVEY §5 "Checkpoint / resume"):
@@ -30,9 +33,9 @@ Parameter / buffer names are kept identical to the reference so that its
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
-
 import os
+from collections import namedtuple
+from typing import List, Optional, Sequence
 
 import torch
 import torch.nn as nn
@@ -65,7 +68,8 @@ HIP_CONV_POLICY = os.environ.get("COALIGN_HIP_CONV", "stage1")      # measuremen
 # convolution than the native fp32-MFMA kernel; judge's ruling of round 1).  0: native fp32 products
 # (coalign_conv3x3_bias_act / MIOpen).  2: 2-way split (dropped <= 2^-16 |w x|), opt-in only.  The environment variable is read once
 # at import; the module attribute is read at every call (tests / bench.py set it directly).
-CONV_EMU_TERMS = int(os.environ.get("COALIGN_CONV_EMU", "16"))
+DEFAULT_CONV_EMU_TERMS = 16
+CONV_EMU_TERMS = int(os.environ.get("COALIGN_CONV_EMU", str(DEFAULT_CONV_EMU_TERMS)))
 # 16 (round 4; scale free since round 5): sp16 pairs (csrc/common.h) -- every operand rounded to 22 significant bits, x~ = x_h + 2^-10 x_l with the low term
 # scaled into fp16's normal range and the weights scaled per output channel by a power of two; three products on v_mfma_f32_32x32x16_f16 into two fp32
 # accumulators; what is dropped is w_l x_l < 2^-20 |w x| per product (the bf16 2-way split: 2^-16; the 3-way split: 2^-24).  Operating range of the activations:
@@ -73,8 +77,15 @@ CONV_EMU_TERMS = int(os.environ.get("COALIGN_CONV_EMU", "16"))
 EMU_MODES = (2, 3, 16)
 
 
-def emu_active() -> bool:
-    return CONV_EMU_TERMS in EMU_MODES
+EMU_MODE_NAMES = {2: "bf16 x 2", 3: "bf16 x 3", 16: "fp16 x 2"}
+
+
+def _terms(terms: Optional[int]) -> int:      # the arithmetic mode a decision is made for: the module attribute, read now, unless the caller (routes.plan) names one
+    return CONV_EMU_TERMS if terms is None else terms
+
+
+def emu_active(terms: Optional[int] = None) -> bool:
+    return _terms(terms) in EMU_MODES
 
 # With the split-bf16 convolutions active, the LAST convolution of every ResNet stage writes its map channels-last (logical shape
 # [N, C, H, W], NHWC memory): the fusion kernel then gathers C contiguous floats per bilinear tap (csrc/warp_fuse_nhwc.hip) and the
@@ -114,13 +125,13 @@ HEADS_ONE_LAUNCH = os.environ.get("COALIGN_HEADS_ONE_LAUNCH", "1") != "0"
 HEADS_SPLIT_IN = os.environ.get("COALIGN_HEADS_SP", "1") != "0"
 
 
-def split_maps_active() -> bool:
-    return SPLIT_MAPS and CONV_EMU_TERMS == 16 and NHWC_STAGE_OUTPUTS and CONV_EMU_TAP_MAJOR and POINTWISE_EMU
+def split_maps_active(terms: Optional[int] = None) -> bool:
+    return SPLIT_MAPS and _terms(terms) == 16 and NHWC_STAGE_OUTPUTS and CONV_EMU_TAP_MAJOR and POINTWISE_EMU
 
 
 # The channel limits of the SplitMap convolutions (csrc/conv3x3_sp.hip, csrc/conv3x3_sp_s2.hip): 64-channel output tiles, 16-channel input chunks, and every
-# output channel's bias and 2^-k_c words (the fused skip's 2^-k_c words too) in the 8 KB of LDS behind the operand buffers.  The layers' route predicates and
-# routes.plan all ask sp_channels_ok, so that no copy of these numbers can drift from the kernels' own checks.
+# output channel's bias and 2^-k_c words (the fused skip's 2^-k_c words too) in the 8 KB of LDS behind the operand buffers.  The layers' route decisions
+# all ask sp_channels_ok, so that no copy of these numbers can drift from the kernels' own checks.
 SP_MAX_COUT, SP_MAX_COUT_SKIP = 1024, 512
 
 
@@ -131,14 +142,14 @@ def sp_channels_ok(cin: Optional[int], cout: int, skip: bool = False) -> bool:
 
 
 # The limits of the narrow-output SplitMap convolution (csrc/conv3x3_narrow.hip, include/coalign_amd_narrow.h): one 16- or 32-channel output tile, 16-channel
-# input chunks.  NaiveCompressor's route and routes.plan ask narrow_channels_ok, as the 64-channel kernels' callers ask sp_channels_ok.
+# input chunks.  NaiveCompressor's route asks narrow_channels_ok, as the 64-channel kernels' callers ask sp_channels_ok.
 def narrow_channels_ok(cin: int, cout: int) -> bool:
     """A 3x3 / stride 1 layer of (cin, cout) fits ``coalign_conv3x3_sp_narrow`` (``cout``: the padded width the kernel is called with)."""
     return cout in ops.NARROW_COUTS and cin > 0 and cin % 16 == 0
 
 
-def winograd_active() -> bool:
-    return CONV_WINOGRAD and CONV_EMU_TERMS == 3 and NHWC_STAGE_OUTPUTS      # (COALIGN_NHWC_STAGES=0 is the all-NCHW measurement route)
+def winograd_active(terms: Optional[int] = None) -> bool:
+    return CONV_WINOGRAD and _terms(terms) == 3 and NHWC_STAGE_OUTPUTS      # (COALIGN_NHWC_STAGES=0 is the all-NCHW measurement route)
 
 
 class Conv3x3Pack:
@@ -195,31 +206,54 @@ class PointwisePack:
         return self._sp
 
     def get(self) -> torch.Tensor:
-        """The image for the arithmetic in force: 3-way split when the 3x3 layers use it and Cin is a multiple of 16, else fp32."""
-        if POINTWISE_EMU and CONV_EMU_TERMS in (3, 16) and self.f32.shape[0] % 16 == 0:       # (the fp16 mode keeps the pointwise layers on the 3-way bf16 split)
+        """The image for the arithmetic in force (``pointwise_split``)."""
+        if pointwise_split(self.f32.shape[0]):
             if self._emu is None:
                 self._emu = ops.pack_pointwise_emu_weight(self.f32)
             return self._emu
         return self.f32
 
 
+def pointwise_split(cin: int, terms: Optional[int] = None) -> bool:
+    """The weight image (and kernel) of a pointwise layer: the 3-way bf16 split when the 3x3 layers run split (the fp16 mode keeps it) and Cin % 16 == 0, else fp32."""
+    return bool(POINTWISE_EMU and _terms(terms) in (3, 16) and cin % 16 == 0)
+
+
+def conv3x3_shape_ok(cin: int, cout: int, stride: int = 1) -> bool:      # a Conv3x3Pack is built for these layers and no others
+    return cout % 64 == 0 and cin % 8 == 0 and stride in (1, 2)
+
+
 def packable(w: torch.Tensor) -> bool:
-    return w.dim() == 4 and tuple(w.shape[2:]) == (3, 3) and w.shape[0] % 64 == 0 and w.shape[1] % 8 == 0
+    return w.dim() == 4 and tuple(w.shape[2:]) == (3, 3) and conv3x3_shape_ok(w.shape[1], w.shape[0])
+
+
+# kernel: C3_EMU (tap_major: its weight image, else tap pairs; wino: Winograd F(2x2, 3x3) when the input is channels-last) | C3_F32 | C3_LIBRARY
+Conv3x3Route = namedtuple("Conv3x3Route", "kernel tap_major wino", defaults=(False, False))
+C3_EMU, C3_F32, C3_LIBRARY = "emu", "f32", "library"
+
+
+def conv3x3_route(cin: int, cout: int, stride: int, terms: Optional[int] = None) -> Conv3x3Route:
+    """A 3x3 / pad 1 layer outside the SplitMap chains: consumer-split (any map size), native fp32 (stride 1; ``hip_conv3x3_wins`` picks it or MIOpen by the map size), library."""
+    terms = _terms(terms)
+    if conv3x3_shape_ok(cin, cout, stride) and terms in EMU_MODES and (terms != 16 or stride == 2 or cin % 16 == 0):      # (the fp16 split serves the tap-major and the strided images)
+        s1_16 = stride == 1 and cin % 16 == 0
+        return Conv3x3Route(C3_EMU, tap_major=bool(CONV_EMU_TAP_MAJOR and s1_16), wino=bool(winograd_active(terms) and s1_16))
+    return Conv3x3Route(C3_F32 if stride == 1 and conv3x3_shape_ok(cin, cout) else C3_LIBRARY)      # (library: no weight image for the shape, or strided in native mode)
 
 
 def conv3x3_fused(x: torch.Tensor, pack: Optional["Conv3x3Pack"], weight: torch.Tensor, bias: torch.Tensor,
                   residual: Optional[torch.Tensor], stride=1, out_channels_last: bool = False) -> torch.Tensor:
     """relu(conv3x3(x, stride, pad 1) + bias (+ residual)) through the kernel the policy selects."""
     stride = stride[0] if isinstance(stride, (tuple, list)) else stride
-    if pack is not None:
-        if emu_active() and stride in (1, 2) and (CONV_EMU_TERMS != 16 or stride == 2 or pack.cin % 16 == 0):              # any map size
-            cl_in = ops.is_channels_last(x)
-            if stride == 1 and winograd_active() and cl_in and pack.wino_ok:
-                return ops.conv3x3_wino(x, pack.wino(), bias, pack.cout, residual, True)
-            return ops.conv3x3_emu_bias_act(x, pack.emu(CONV_EMU_TERMS, CONV_EMU_TAP_MAJOR and stride == 1), bias, pack.cout, residual, True, CONV_EMU_TERMS, stride=stride,
-                                            out_channels_last=out_channels_last and (stride == 1 or cl_in))
-        if stride == 1 and x.shape[3] % 4 == 0 and hip_conv3x3_wins(x, pack.cin, pack.cout):
-            return ops.conv3x3_bias_act(x, pack.f32, bias, residual, True)
+    route = conv3x3_route(pack.cin, pack.cout, stride) if pack is not None else Conv3x3Route(C3_LIBRARY)
+    if route.kernel == C3_EMU:
+        cl_in = ops.is_channels_last(x)
+        if route.wino and cl_in:
+            return ops.conv3x3_wino(x, pack.wino(), bias, pack.cout, residual, True)
+        return ops.conv3x3_emu_bias_act(x, pack.emu(CONV_EMU_TERMS, route.tap_major), bias, pack.cout, residual, True, CONV_EMU_TERMS, stride=stride,
+                                        out_channels_last=out_channels_last and (stride == 1 or cl_in))
+    if route.kernel == C3_F32 and x.shape[3] % 4 == 0 and hip_conv3x3_wins(x, pack.cin, pack.cout):
+        return ops.conv3x3_bias_act(x, pack.f32, bias, residual, True)
     return ops.bias_act_(F.conv2d(x.contiguous(), weight, None, stride, 1), bias, residual, True)
 
 
@@ -267,18 +301,17 @@ class _FoldCache:
         return self.data
 
 
-def _pw_cache_of(module: nn.Module) -> _FoldCache:
-    c = module.__dict__.get("_coalign_pw_cache")
+def _cache_of(module: nn.Module, slot: str = "_coalign_fold_cache") -> _FoldCache:
+    c = module.__dict__.get(slot)
     if c is None:
-        c = module.__dict__["_coalign_pw_cache"] = _FoldCache()
+        c = module.__dict__[slot] = _FoldCache()
     return c
 
 
-def _cache_of(module: nn.Module) -> _FoldCache:
-    c = module.__dict__.get("_coalign_fold_cache")
-    if c is None:
-        c = module.__dict__["_coalign_fold_cache"] = _FoldCache()
-    return c
+# BasicBlock.route().  kind: BLOCK_SPLIT (both convolutions hand SplitMaps on) | BLOCK_SPARSE (a sparse canvas is read in place by the consumer-split kernel) | None (conv3x3_route
+# per convolution).  A strided BLOCK_SPLIT block is opened by conv3x3_sp_s2 on a sparse canvas (s2_sparse) / a dense map (s2_dense), the skip as its tenth tap (skip_fused).
+BlockRoute = namedtuple("BlockRoute", "kind s2_sparse s2_dense skip_fused", defaults=(False, False, False))
+BLOCK_SPLIT, BLOCK_SPARSE = "split", "sparse"
 
 
 class BasicBlock(nn.Module):
@@ -307,63 +340,65 @@ class BasicBlock(nn.Module):
             p1 = Conv3x3Pack(w1) if self.stride in (1, 2) and packable(w1) else None
             p2 = Conv3x3Pack(w2) if packable(w2) else None
             pd = None                                    # 1x1 / stride-2 skip convolution through the pointwise kernel
-            if wd is not None and self.stride == 2 and wd.shape[1] % 2 == 0 and wd.shape[1] <= 256:
+            if self.skip_pointwise():
                 pd = (PointwisePack(wd, False), torch.zeros(wd.shape[0], dtype=torch.float32, device=wd.device))
             return w1, b1, w2, b2, wd, p1, p2, pd
         return _cache_of(self).get(self, build)
 
-    def takes_sparse_canvas(self) -> bool:
-        """This block reads a ``ops.SparseCanvas`` directly (round 4): strided 3x3 + pointwise skip on the split matrix cores."""
-        if self.training or self.stride != 2 or self.downsample is None or CONV_EMU_TERMS not in (3, 16) or not NHWC_STAGE_OUTPUTS or not POINTWISE_EMU:      # (the skip convolution's split-bf16 image exists in these two modes)
-            return False
-        c1 = self.conv1
-        return c1.out_channels % 64 == 0 and c1.in_channels % 16 == 0 and c1.in_channels <= 256 and self.downsample[0].stride[0] == 2 and self.downsample[0].out_channels % 32 == 0
+    def skip_pointwise(self) -> bool:
+        """The skip convolution runs on the pointwise kernel: 1 x 1 / stride 2, Cin even and <= 256 (else on the library)."""
+        d = self.downsample
+        return d is not None and self.stride == 2 and d[0].in_channels % 2 == 0 and d[0].in_channels <= 256
 
-    def takes_split_maps(self) -> bool:
-        """This block runs on the SplitMap route (round 5): producer-split 3x3 convolutions, channels-last float32 skip."""
-        if self.training or not FAST_INFERENCE or not split_maps_active():
-            return False
-        c1, c2 = self.conv1, self.conv2
-        if tuple(c1.kernel_size) != (3, 3) or tuple(c2.kernel_size) != (3, 3) or not sp_channels_ok(c2.in_channels, c2.out_channels):
-            return False
-        if self.stride == 2:            # (conv1 reads Cin % 8 on the consumer-split kernel when Cin % 16 != 0: _forward_split)
-            d = self.downsample
-            return (d is not None and sp_channels_ok(None, c1.out_channels) and c1.in_channels % 8 == 0 and d[0].stride[0] == 2 and d[0].in_channels % 16 == 0
-                    and d[0].in_channels <= 256 and d[0].out_channels % 32 == 0)
-        return self.stride == 1 and self.downsample is None and sp_channels_ok(c1.in_channels, c1.out_channels)
+    def route(self, terms: Optional[int] = None) -> BlockRoute:
+        """The route of this block from its shapes, its mode and the switches: the one decision ``forward``, ``ResNetStages``, ``detector.encode`` and ``routes.plan`` share."""
+        c1, c2, d = self.conv1, self.conv2, self.downsample
+        if self.training:
+            return BlockRoute(None)
+        # the skip on the pointwise kernel's split-bf16 form, which reads a sparse canvas or a channels-last map in place: Cin % 16 == 0, 32-row output tiles
+        skip_split = self.skip_pointwise() and d[0].stride[0] == 2 and d[0].in_channels % 16 == 0 and d[0].out_channels % 32 == 0
+        chain = (FAST_INFERENCE and split_maps_active(terms) and tuple(c1.kernel_size) == (3, 3) and tuple(c2.kernel_size) == (3, 3)
+                 and sp_channels_ok(c2.in_channels, c2.out_channels))
+        if chain and self.stride == 1 and d is None and sp_channels_ok(c1.in_channels, c1.out_channels):
+            return BlockRoute(BLOCK_SPLIT)
+        if chain and skip_split and sp_channels_ok(None, c1.out_channels) and c1.in_channels % 8 == 0:
+            s2 = S2_SPLIT if c1.in_channels % 16 == 0 else "0"              # (Cin % 16 != 0: conv1 stays on the consumer-split kernel)
+            fused = (S2_SKIP and d[0].out_channels == c1.out_channels and tuple(d[0].kernel_size) == (1, 1)
+                     and sp_channels_ok(c1.in_channels, c1.out_channels, skip=True))
+            return BlockRoute(BLOCK_SPLIT, s2_sparse=s2 in ("sparse", "all") and c1.in_channels >= 32, s2_dense=s2 == "all", skip_fused=bool(fused))
+        if skip_split and _terms(terms) in (3, 16) and NHWC_STAGE_OUTPUTS and POINTWISE_EMU and c1.out_channels % 64 == 0:
+            return BlockRoute(BLOCK_SPARSE)                                 # (the skip's split-bf16 image exists in these two modes)
+        return BlockRoute(None)
 
-    def _forward_split(self, x, out_channels_last: bool, out_both: bool = False, x_split=None):
+    def takes_sparse_canvas(self, terms: Optional[int] = None) -> bool:      # reads an ops.SparseCanvas directly (round 4): strided 3x3 + pointwise skip on the split matrix cores
+        return self.stride == 2 and self.route(terms).kind is not None
+
+    def takes_split_maps(self) -> bool:      # runs on the SplitMap route (round 5): producer-split 3x3 convolutions, channels-last float32 skip
+        return self.route().kind == BLOCK_SPLIT
+
+    def _forward_split(self, x, route: BlockRoute, out_channels_last: bool, out_both: bool = False, x_split=None):
         """conv1 -> SplitMap -> conv2 (+ skip) -> SplitMap, or channels-last float32 at the end of a stage (resblock.py:53-69)."""
         w1, b1, w2, b2, wd, p1, p2, pd = self._folded()
         if self.stride == 2:
-            s2 = S2_SPLIT if p1.cin % 16 == 0 else "0"
-            fused = S2_SKIP and wd.shape[0] == p1.cout and sp_channels_ok(p1.cin, p1.cout, skip=True) and tuple(wd.shape[2:]) == (1, 1)      # the skip as a tenth tap of the strided launch
-            if isinstance(x, ops.SparseCanvas):
-                skip = None
-                if s2 in ("sparse", "all") and p1.cin >= 32:
-                    if fused:
-                        y, skip = ops.conv3x3_sp_s2(x, p1.emu(16, True), b1, p1.cout, True, w_skip=pd[0].sp())
-                    else:
-                        y = ops.conv3x3_sp_s2(x, p1.emu(16, True), b1, p1.cout, True)
-                else:
-                    y = ops.conv3x3_emu_sparse(x, p1.emu(16, False), b1, p1.cout, True, 16, out_channels_last=False, out_split=True)
-                if skip is None:
-                    skip = ops.pointwise_conv_sparse(x, pd[0].get(), pd[1], wd.shape[0], False, out_channels_last=True)
+            sparse = isinstance(x, ops.SparseCanvas)
+            sp_s2 = route.s2_sparse if sparse else route.s2_dense
+            fused = sp_s2 and route.skip_fused                     # the skip as a tenth tap of the strided launch
+            xs = x if isinstance(x, ops.SplitMap) else x_split
+            if isinstance(x, ops.SplitMap) and not fused:          # (the fused strided launch reads the SplitMap alone: NaiveCompressor's output)
+                x = x.dense(channels_last=True)
+            skip = None
+            if sp_s2:
+                y = ops.conv3x3_sp_s2(x if sparse else xs if xs is not None else ops.SplitMap.pack(x), p1.emu(16, True), b1, p1.cout, True, w_skip=pd[0].sp() if fused else None)
+                if fused:
+                    y, skip = y
+            elif sparse:
+                y = ops.conv3x3_emu_sparse(x, p1.emu(16, False), b1, p1.cout, True, 16, out_channels_last=False, out_split=True)
             else:
-                xs = x if isinstance(x, ops.SplitMap) else x_split
-                if isinstance(x, ops.SplitMap) and not (s2 == "all" and fused):      # (the fused strided launch reads the SplitMap alone: NaiveCompressor's output)
-                    x = x.dense(channels_last=True)
-                skip = None
-                if s2 == "all":
-                    xs = xs if xs is not None else ops.SplitMap.pack(x)
-                    if fused:
-                        y, skip = ops.conv3x3_sp_s2(xs, p1.emu(16, True), b1, p1.cout, True, w_skip=pd[0].sp())
-                    else:
-                        y = ops.conv3x3_sp_s2(xs, p1.emu(16, True), b1, p1.cout, True)
-                else:
-                    y = ops.conv3x3_emu_bias_act(x, p1.emu(16, False), b1, p1.cout, None, True, 16, stride=2, out_split=True)
-                if skip is None:
-                    skip = ops.pointwise_conv(x, pd[0].get(), pd[1], wd.shape[0], in_stride=2, relu=False, out_channels_last=True)
+                y = ops.conv3x3_emu_bias_act(x, p1.emu(16, False), b1, p1.cout, None, True, 16, stride=2, out_split=True)
+            if skip is None and sparse:
+                skip = ops.pointwise_conv_sparse(x, pd[0].get(), pd[1], wd.shape[0], False, out_channels_last=True)
+            elif skip is None:
+                skip = ops.pointwise_conv(x, pd[0].get(), pd[1], wd.shape[0], in_stride=2, relu=False, out_channels_last=True)
         else:
             xs = x if isinstance(x, ops.SplitMap) else ops.SplitMap.pack(x)
             y = ops.conv3x3_sp(xs, p1.emu(16, True), b1, p1.cout, None, True, out_split=True)
@@ -382,44 +417,45 @@ class BasicBlock(nn.Module):
         skip = ops.pointwise_conv_sparse(sc, pw, pd[1], wd.shape[0], False, out_channels_last=wino)
         return conv3x3_fused(y, p2, w2, b2, skip, out_channels_last=(wino or out_channels_last) and p2 is not None and p2.cout % 4 == 0)
 
+    def _forward_fused(self, x: torch.Tensor, out_channels_last: bool) -> torch.Tensor:
+        w1, b1, w2, b2, wd, p1, p2, pd = self._folded()
+        emu = emu_active()
+        # Winograd route: the block's maps stay channels-last from its first convolution on (conv1 -> conv2 -> output, and the skip)
+        wino = winograd_active() and p1 is not None and p2 is not None and p2.wino_ok and (self.stride == 1 or pd is not None)
+        # a channels-last input (the previous stage's output / a Winograd block's output) is read in place: by the strided convolution and the
+        # pointwise skip, or by the Winograd layers
+        if not (ops.is_channels_last(x) and emu and p1 is not None and ((self.stride == 2 and pd is not None) or (wino and self.stride == 1 and p1.wino_ok))):
+            x = x.contiguous()
+        y = conv3x3_fused(x, p1, w1, b1, None, self.stride, out_channels_last=wino)
+        if wd is None:
+            skip = x
+        elif pd is not None:
+            skip = ops.pointwise_conv(x, pd[0].get(), pd[1], wd.shape[0], in_stride=2, relu=False,      # its BN shift already sits in b2
+                                      out_channels_last=wino and wd.shape[0] % 4 == 0 and ops.is_channels_last(y))
+        else:
+            skip = F.conv2d(x, wd, None, self.stride)
+        return conv3x3_fused(y, p2, w2, b2, skip, out_channels_last=(wino or out_channels_last) and emu and p2 is not None and p2.cout % 4 == 0)
+
     def forward(self, x: torch.Tensor, out_channels_last: bool = False, out_split: bool = False, out_both: bool = False, x_split=None) -> torch.Tensor:
         """``out_split``: the caller (``ResNetStages``' per-block loop) reads ``ops.SplitMap``s and wants one back.  A plain ``block(x)`` / ``nn.Sequential`` call
         always gets a tensor, and the SplitMap route is taken for float32 CUDA tensors and for this build's own map types only -- half / float64
         inputs run the reference's module sequence below."""
-        if self.takes_split_maps() and (isinstance(x, (ops.SplitMap, ops.SparseCanvas)) or _fast_ok(self, x)):
-            f = self._folded()
-            if f[5] is not None and f[6] is not None and (self.stride == 1 or f[7] is not None):
-                y = self._forward_split(x, out_channels_last, out_both=out_both and out_channels_last, x_split=x_split)
-                if out_both:                               # (round 6: the stage's last block; the caller asked for the pair)
-                    return y if isinstance(y, tuple) else (y, None)
-                return y.dense() if isinstance(y, ops.SplitMap) and not out_split else y
+        route = self.route()
+        if route.kind == BLOCK_SPLIT and (isinstance(x, (ops.SplitMap, ops.SparseCanvas)) or _fast_ok(self, x)):
+            y = self._forward_split(x, route, out_channels_last, out_both=out_both and out_channels_last, x_split=x_split)
+            if out_both:                               # (round 6: the stage's last block; the caller asked for the pair)
+                return y if isinstance(y, tuple) else (y, None)
+            return y.dense() if isinstance(y, ops.SplitMap) and not out_split else y
         if out_both:
             return self.forward(x, out_channels_last, out_split), None
         if isinstance(x, ops.SplitMap):
             x = x.dense()
         if isinstance(x, ops.SparseCanvas):
-            if self.takes_sparse_canvas() and self._folded()[5] is not None and self._folded()[7] is not None:
+            if route.kind == BLOCK_SPARSE:
                 return self._forward_sparse(x, out_channels_last)
             x = x.dense()
         if _fast_ok(self, x):
-            w1, b1, w2, b2, wd, p1, p2, pd = self._folded()
-            emu = emu_active()
-            # Winograd route: the block's maps stay channels-last from its first convolution on (conv1 -> conv2 -> output, and the skip)
-            wino = winograd_active() and p1 is not None and p2 is not None and p2.wino_ok and (self.stride == 1 or pd is not None)
-            cl = ops.is_channels_last(x)
-            # a channels-last input (the previous stage's output / a Winograd block's output) is read in place: by the strided convolution and the
-            # pointwise skip, or by the Winograd layers
-            if not (cl and emu and p1 is not None and ((self.stride == 2 and pd is not None) or (wino and self.stride == 1 and p1.wino_ok))):
-                x = x.contiguous()
-            y = conv3x3_fused(x, p1, w1, b1, None, self.stride, out_channels_last=wino)
-            if wd is None:
-                skip = x
-            elif pd is not None:
-                skip = ops.pointwise_conv(x, pd[0].get(), pd[1], wd.shape[0], in_stride=2, relu=False,      # its BN shift already sits in b2
-                                          out_channels_last=wino and wd.shape[0] % 4 == 0 and ops.is_channels_last(y))
-            else:
-                skip = F.conv2d(x, wd, None, self.stride)
-            return conv3x3_fused(y, p2, w2, b2, skip, out_channels_last=(wino or out_channels_last) and emu and p2 is not None and p2.cout % 4 == 0)
+            return self._forward_fused(x, out_channels_last)
         skip = x if self.downsample is None else self.downsample(x)
         y = self.relu(self.bn1(self.conv1(x)))
         y = self.bn2(self.conv2(y))
@@ -457,19 +493,15 @@ class ResNetStages(nn.Module):
             layer = getattr(self, f"layer{i}")
             if NHWC_STAGE_OUTPUTS and emu_active() and (isinstance(x, ops.SparseCanvas) or _fast_ok(self, x)):
                 # round 6 (S2_SPLIT = all): the stage's last block also hands the next stage's strided convolution the SplitMap of its output
-                nxt = getattr(self, f"layer{i + 1}")[0] if i + 1 < self.layernum else None
-                both = (S2_SPLIT == "all" and nxt is not None and isinstance(nxt, BasicBlock) and nxt.stride == 2 and nxt.conv1.in_channels % 16 == 0 and nxt.takes_split_maps()
-                        and len(layer) > 1)
+                nxt = getattr(self, f"layer{i + 1}")[0].route() if i + 1 < self.layernum and isinstance(getattr(self, f"layer{i + 1}")[0], BasicBlock) else None
+                both = nxt is not None and nxt.kind == BLOCK_SPLIT and nxt.s2_dense and len(layer) > 1
                 x_split = carry if not isinstance(x, (ops.SparseCanvas, ops.SplitMap)) else None
                 carry = None
                 for j, blk in enumerate(layer):
                     last = j == len(layer) - 1
+                    x = blk(x, out_channels_last=last, out_split=not last, out_both=last and both, x_split=x_split if j == 0 else None)
                     if last and both:
-                        x, carry = blk(x, out_channels_last=True, out_split=False, out_both=True)
-                    elif j == 0 and x_split is not None:
-                        x = blk(x, out_channels_last=last, out_split=not last, x_split=x_split)
-                    else:
-                        x = blk(x, out_channels_last=last, out_split=not last)
+                        x, carry = x
             else:
                 x = layer(x)
                 carry = None                         # (a SplitMap handed on by an earlier stage does not describe this stage's output)
@@ -514,21 +546,21 @@ class _MultiscaleDecodeMixin:
         y = F.conv_transpose2d(f, w, None, stride=op.stride) if transposed else F.conv2d(f, w, None, stride=op.stride)
         return ops.bias_act_(y.contiguous(), b, None, True)
 
+    def heads_pointwise(self) -> bool:
+        """All per-level heads are non-overlapping transposed convolutions the pointwise kernel serves: kernel = stride in {1, 2, 4}, Cin even, <= 256, Cout * stride^2 in tiles of 32."""
+        heads = [self.deblocks[i][0] for i in range(self.num_levels)] if len(self.deblocks) else []
+        return len(heads) > 0 and all(isinstance(op, nn.ConvTranspose2d) and op.kernel_size == op.stride and op.stride[0] == op.stride[1] and op.stride[0] in (1, 2, 4)
+                                      and op.in_channels <= 256 and op.in_channels % 2 == 0 and (op.out_channels * op.stride[0] ** 2) % 32 == 0 for op in heads)
+
+    def heads_write_split(self, terms: Optional[int] = None) -> bool:      # ... and write the concatenated map as ONE SplitMap: no trailing head, split-bf16 images, slices % 16
+        return (self.heads_pointwise() and len(self.deblocks) == self.num_levels
+                and all(pointwise_split(self.deblocks[i][0].in_channels, terms) and self.deblocks[i][0].out_channels % 16 == 0 for i in range(self.num_levels)))
+
     def _pointwise_ok(self, feats: Sequence[torch.Tensor]) -> bool:
-        """All per-level heads are non-overlapping transposed convolutions the pointwise kernel serves (kernel = stride in
-        {1, 2, 4}, Cin even and <= 256) and they all land on one output resolution."""
-        if not len(self.deblocks) or not _fast_ok(self, feats[0]):
+        """``heads_pointwise()``, float32 CUDA maps of one batch, and all heads land on one output resolution."""
+        if not self.heads_pointwise() or not _fast_ok(self, feats[0]):
             return False
-        sizes = set()
-        for i, f in enumerate(feats[: self.num_levels]):
-            op = self.deblocks[i][0]
-            if not isinstance(op, nn.ConvTranspose2d) or op.kernel_size != op.stride or op.stride[0] != op.stride[1] or op.stride[0] not in (1, 2, 4):
-                return False
-            if op.in_channels > 256 or op.in_channels % 2 or f.shape[0] != feats[0].shape[0]:
-                return False
-            if (op.out_channels * op.stride[0] ** 2) % 32:        # GEMM rows of coalign_pointwise_conv come in tiles of 32
-                return False
-            sizes.add((f.shape[2] * op.stride[0], f.shape[3] * op.stride[0]))
+        sizes = {(f.shape[0], f.shape[2] * self.deblocks[i][0].stride[0], f.shape[3] * self.deblocks[i][0].stride[0]) for i, f in enumerate(feats[: self.num_levels])}
         return len(sizes) == 1
 
     def _upsample_concat(self, feats: Sequence[torch.Tensor], out_split: bool = False):
@@ -540,13 +572,12 @@ class _MultiscaleDecodeMixin:
             for i, f in enumerate(feats[: self.num_levels]):
                 blk = self.deblocks[i]
                 op, bn = blk[0], blk[1]
-                w, b = _pw_cache_of(blk).get(blk, lambda op=op, bn=bn: (lambda wf, bf: (PointwisePack(wf, True), bf))(*fold_bn(op.weight, None, bn, out_dim=1)))
+                w, b = _cache_of(blk, "_coalign_pw_cache").get(blk, lambda op=op, bn=bn: (lambda wf, bf: (PointwisePack(wf, True), bf))(*fold_bn(op.weight, None, bn, out_dim=1)))
                 ops_.append((f, w, b, op.out_channels, op.stride[0], c_tot))
                 c_tot += op.out_channels
             f0, s0 = feats[0], self.deblocks[0][0].stride[0]
             images = [w.get() for _, w, _, _, _, _ in ops_]
-            if (out_split and len(self.deblocks) == self.num_levels and all(im.dtype == torch.int16 for im in images)
-                    and all(cout % 16 == 0 and off % 16 == 0 and im.shape[0] * 32 == cout * up * up for (_, _, _, cout, up, off), im in zip(ops_, images))):
+            if out_split and self.heads_write_split():
                 x = ops.SplitMap.empty(f0.shape[0], c_tot, f0.shape[2] * s0, f0.shape[3] * s0, f0.device)
             else:
                 x = torch.empty((f0.shape[0], c_tot, f0.shape[2] * s0, f0.shape[3] * s0), dtype=torch.float32, device=f0.device)
@@ -555,11 +586,9 @@ class _MultiscaleDecodeMixin:
             else:
                 for (f, w, b, cout, up, off), im in zip(ops_, images):
                     ops.pointwise_conv(f, im, b, cout, up=up, relu=True, out=x, c_off=off)
-            if len(self.deblocks) > self.num_levels:
-                x = self._deblock(len(self.deblocks) - 1, x)
-            return x
-        ups = [self._deblock(i, f) if len(self.deblocks) > 0 else f for i, f in enumerate(feats[: self.num_levels])]
-        x = torch.cat(ups, dim=1) if len(ups) > 1 else ups[0]
+        else:
+            ups = [self._deblock(i, f) if len(self.deblocks) > 0 else f for i, f in enumerate(feats[: self.num_levels])]
+            x = torch.cat(ups, dim=1) if len(ups) > 1 else ups[0]
         if len(self.deblocks) > self.num_levels:
             x = self._deblock(len(self.deblocks) - 1, x)
         return x
@@ -573,6 +602,12 @@ class _MultiscaleDecodeMixin:
         return data_dict
 
 
+def _backbone_cfg(model_cfg: dict):
+    layer_nums, layer_strides, num_filters, ups, upf = (list(model_cfg.get(k, [])) for k in ("layer_nums", "layer_strides", "num_filters", "upsample_strides", "num_upsample_filter"))
+    assert len(layer_nums) == len(layer_strides) == len(num_filters) and len(ups) == len(upf)
+    return layer_nums, layer_strides, num_filters, ups, upf
+
+
 class ResNetBEVBackbone(_MultiscaleDecodeMixin, nn.Module):
     """ResNet-style BEV backbone with the multiscale split used by CoAlign
     (base_bev_backbone_resnet.py:15-144)."""
@@ -580,13 +615,7 @@ class ResNetBEVBackbone(_MultiscaleDecodeMixin, nn.Module):
     def __init__(self, model_cfg: dict, input_channels: int = 64):
         super().__init__()
         self.model_cfg = model_cfg
-        layer_nums = list(model_cfg.get("layer_nums", []))
-        layer_strides = list(model_cfg.get("layer_strides", []))
-        num_filters = list(model_cfg.get("num_filters", []))
-        assert len(layer_nums) == len(layer_strides) == len(num_filters)
-        ups = list(model_cfg.get("upsample_strides", []))
-        upf = list(model_cfg.get("num_upsample_filter", []))
-        assert len(ups) == len(upf)
+        layer_nums, layer_strides, num_filters, ups, upf = _backbone_cfg(model_cfg)
         self.resnet = ResNetStages(layer_nums, layer_strides, num_filters,
                                    inplanes=model_cfg.get("inplanes", 64))
         self.num_levels = len(layer_nums)
@@ -604,13 +633,7 @@ class BaseBEVBackbone(_MultiscaleDecodeMixin, nn.Module):
     def __init__(self, model_cfg: dict, input_channels: int):
         super().__init__()
         self.model_cfg = model_cfg
-        layer_nums = list(model_cfg.get("layer_nums", []))
-        layer_strides = list(model_cfg.get("layer_strides", []))
-        num_filters = list(model_cfg.get("num_filters", []))
-        assert len(layer_nums) == len(layer_strides) == len(num_filters)
-        ups = list(model_cfg.get("upsample_strides", []))
-        upf = list(model_cfg.get("num_upsample_filter", []))
-        assert len(ups) == len(upf)
+        layer_nums, layer_strides, num_filters, ups, upf = _backbone_cfg(model_cfg)
         self.num_levels = len(layer_nums)
         cins = [input_channels, *num_filters[:-1]]
         self.blocks = nn.ModuleList()
@@ -664,42 +687,36 @@ class DoubleConv(nn.Module):
             nn.Conv2d(cin, cout, kernel_size, stride=stride, padding=padding), nn.ReLU(inplace=True),
             nn.Conv2d(cout, cout, 3, padding=1), nn.ReLU(inplace=True))
 
-    def takes_split_maps(self) -> bool:
-        """Both layers are 3x3 / stride 1 / pad 1 with channel counts the SplitMap kernel serves, and the fp16 route is on: forward() then accepts an
-        ``ops.SplitMap`` (the up-sampling heads' output, round 5) and runs BOTH convolutions on ``conv3x3_sp``."""
-        c1, c2 = self.double_conv[0], self.double_conv[2]
-        ok = lambda c: c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1) and sp_channels_ok(c.in_channels, c.out_channels)
-        return bool(HEAD_SPLIT_MAPS and split_maps_active() and not self.training and ok(c1) and ok(c2) and c1.weight.is_cuda)
+    def _layer_ok(self, conv: nn.Conv2d, fits) -> bool:      # 3x3 / stride 1 / pad 1 with channel counts `fits` accepts: sp_channels_ok (SplitMap kernel) | conv3x3_shape_ok (a weight image)
+        return conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and fits(conv.in_channels, conv.out_channels)
+
+    def on_split_maps(self, terms: Optional[int] = None) -> bool:
+        """Both layers are 3x3 / stride 1 / pad 1 with SplitMap channel counts, fp16 route on: conv 2 runs on ``conv3x3_sp``, conv 1 writes its SplitMap (or, fed one, reads it)."""
+        return bool(split_maps_active(terms) and all(self._layer_ok(c, sp_channels_ok) for c in (self.double_conv[0], self.double_conv[2])))
+
+    def takes_split_maps(self) -> bool:      # forward() accepts an ops.SplitMap (the up-sampling heads' output, round 5) and runs BOTH convolutions on conv3x3_sp
+        return bool(HEAD_SPLIT_MAPS and not self.training and self.on_split_maps() and self.double_conv[0].weight.is_cuda)
 
     def forward(self, x, out_split: bool = False):
-        """``out_split`` (round 6): the caller's next layer reads a SplitMap (the merged heads, ``ops.heads_sp``) -- granted on the SplitMap route only."""
-        if isinstance(x, ops.SplitMap):
-            if not self.takes_split_maps():
-                x = x.dense()
-            else:
-                c1, c2 = self.double_conv[0], self.double_conv[2]
-                p1, p2 = _cache_of(self).get([c1.weight, c2.weight], lambda: (Conv3x3Pack(c1.weight.detach()), Conv3x3Pack(c2.weight.detach())))
-                y = ops.conv3x3_sp(x, p1.emu(16, True), c1.bias, p1.cout, None, True, out_split=True)
-                return ops.conv3x3_sp(y, p2.emu(16, True), c2.bias, p2.cout, None, True, out_split=out_split)
-        if _fast_ok(self, x):
-            c1, c2 = self.double_conv[0], self.double_conv[2]
-
-            def build():
-                ok = lambda c: c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1) and c.out_channels % 64 == 0 and c.in_channels % 8 == 0
-                return (Conv3x3Pack(c1.weight.detach()) if ok(c1) else None, Conv3x3Pack(c2.weight.detach()) if ok(c2) else None)
-            p1, p2 = _cache_of(self).get([c1.weight, c2.weight], build)
-            x = x.contiguous()
-            if split_maps_active() and p1 is not None and p2 is not None and sp_channels_ok(p1.cin, p1.cout) and sp_channels_ok(p2.cin, p2.cout):
-                # round 5: the first convolution splits its own (float32, concatenated) input and writes a SplitMap, the second one reads it by LDS-DMA and
-                # writes the channels-last float32 map the 1x1 heads read
-                y = ops.conv3x3_emu_bias_act(x, p1.emu(16, True), c1.bias, p1.cout, None, True, 16, out_split=True)
-                return ops.conv3x3_sp(y, p2.emu(16, True), c2.bias, p2.cout, None, True, out_split=False)
-            if p1 is not None:
-                y = conv3x3_fused(x, p1, c1.weight, c1.bias, None, out_channels_last=winograd_active() and p2 is not None and p2.wino_ok)
-            else:
-                y = ops.bias_act_(F.conv2d(x, c1.weight, None, c1.stride, c1.padding), c1.bias, None, True)
-            return conv3x3_fused(y, p2, c2.weight, c2.bias, None)
-        return self.double_conv(x)
+        """``out_split`` (round 6): the caller's next layer reads a SplitMap (the merged heads, ``ops.heads_sp``) -- granted for a SplitMap input only."""
+        c1, c2 = self.double_conv[0], self.double_conv[2]
+        if isinstance(x, ops.SplitMap) and not self.takes_split_maps():
+            x = x.dense()
+        split_in = isinstance(x, ops.SplitMap)
+        if not split_in and not _fast_ok(self, x):
+            return self.double_conv(x)
+        p1, p2 = _cache_of(self).get([c1.weight, c2.weight], lambda: tuple(Conv3x3Pack(c.weight.detach()) if self._layer_ok(c, conv3x3_shape_ok) else None for c in (c1, c2)))
+        if split_in or self.on_split_maps():
+            # round 5: conv 1 reads the heads' SplitMap or splits its own float32 input and writes a SplitMap; conv 2 reads it by LDS-DMA and writes what the 1x1 heads read
+            y = (ops.conv3x3_sp(x, p1.emu(16, True), c1.bias, p1.cout, None, True, out_split=True) if split_in else
+                 ops.conv3x3_emu_bias_act(x.contiguous(), p1.emu(16, True), c1.bias, p1.cout, None, True, 16, out_split=True))
+            return ops.conv3x3_sp(y, p2.emu(16, True), c2.bias, p2.cout, None, True, out_split=out_split and split_in)
+        x = x.contiguous()
+        if p1 is not None:
+            y = conv3x3_fused(x, p1, c1.weight, c1.bias, None, out_channels_last=winograd_active() and p2 is not None and p2.wino_ok)
+        else:
+            y = ops.bias_act_(F.conv2d(x, c1.weight, None, c1.stride, c1.padding), c1.bias, None, True)
+        return conv3x3_fused(y, p2, c2.weight, c2.bias, None)
 
 
 class DownsampleConv(nn.Module):
@@ -755,14 +772,12 @@ class NaiveCompressor(nn.Module):
         cw = (mid + 63) // 64 * 64
         return ("wide", cw) if sp_channels_ok(cin, cw) and sp_channels_ok(cw, cin) else None
 
-    def takes_split_maps(self) -> bool:
-        return bool(FAST_INFERENCE and not self.training and split_maps_active() and self.split_widths() is not None)
+    def takes_split_maps(self, terms: Optional[int] = None) -> bool:
+        return bool(FAST_INFERENCE and not self.training and split_maps_active(terms) and self.split_widths() is not None)
 
     def _split_images(self):
         """BatchNorm folded, mid padded: (encoder image or pack, its bias, decoder packs and biases), cached until a parameter or buffer changes."""
-        c = self.__dict__.get("_coalign_split_cache")
-        if c is None:
-            c = self.__dict__["_coalign_split_cache"] = _FoldCache()
+        c = _cache_of(self, "_coalign_split_cache")
 
         def build():
             kind, cp = self.split_widths()

@@ -9,34 +9,37 @@ dense convolutions run on MIOpen through PyTorch-ROCm.
 """
 from __future__ import annotations
 
+import os
+from collections import namedtuple
+from typing import Optional, Sequence
+
 import torch
 import torch.nn as nn
-
 import torch.nn.functional as F
 
+from . import backbone as _bb
 from . import ops
 from .backbone import BaseBEVBackbone, BasicBlock, DownsampleConv, NaiveCompressor, ResNetBEVBackbone, _cache_of, _fast_ok
 from .encoder import PillarVFE, PointPillarScatter, host_ints
 from .fusion import AttFusion, MaxFusion, fuse_multiscale
 from .pose import normalize_pairwise_tfm
 
-
-import os as _os
-
 # Round 4: PillarVFE + PointPillarScatter as one launch with a sparse canvas (csrc/pillar_sparse.hip) feeding the first ResNet block directly.
 # "0": the dense persistent canvas of rounds 2-3 (measurement aid; module attribute, read at every call).
-SPARSE_CANVAS = _os.environ.get("COALIGN_SPARSE_CANVAS", "1") != "0"
+SPARSE_CANVAS = os.environ.get("COALIGN_SPARSE_CANVAS", "1") != "0"
+
+
+def _heads(model: nn.Module) -> list:
+    names = ["cls", "reg"] + (["unc"] if getattr(model, "unc_head", None) is not None else []) + (["dir"] if model.use_dir else [])
+    return [(k + "_preds", getattr(model, k + "_head")) for k in names]
 
 
 def _run_heads(model: nn.Module, x: torch.Tensor) -> dict:
     """cls / reg / dir 1x1 heads.  Inference fast path: one convolution with the concatenated head weights (+ one fused
     bias pass) instead of three convolutions and three bias kernels; the outputs are channel slices of one tensor."""
-    heads = [("cls_preds", model.cls_head), ("reg_preds", model.reg_head)]
-    if getattr(model, "unc_head", None) is not None:
-        heads.append(("unc_preds", model.unc_head))
-    if model.use_dir:
-        heads.append(("dir_preds", model.dir_head))
-    if isinstance(x, ops.SplitMap) and not heads_take_split_map(model, x):
+    heads = _heads(model)
+    route = heads_route(model)
+    if isinstance(x, ops.SplitMap) and not (route.split_in and model.cls_head.weight.is_cuda):
         x = x.dense()
     if not isinstance(x, ops.SplitMap) and not _fast_ok(model, x):
         return {k: h(x) for k, h in heads}
@@ -44,12 +47,11 @@ def _run_heads(model: nn.Module, x: torch.Tensor) -> dict:
     def build():
         return (torch.cat([h.weight for _, h in heads]).contiguous(), torch.cat([h.bias for _, h in heads]).contiguous())
     w, b = _cache_of(model.cls_head).get([t for _, h in heads for t in (h.weight, h.bias)], build)
-    from . import backbone as _bb
     if isinstance(x, ops.SplitMap):
         # round 6: the shrink header's last convolution handed its map over as a SplitMap: the merged heads read it with one 16-byte load per lane and operand
-        img = _bb._pw_cache_of(model.reg_head).get([t for _, h in heads for t in (h.weight, h.bias)], lambda: ops.pack_heads_sp_weight(w))      # (a cache slot of its own: reg_head's fold cache holds the pointwise image)
+        img = _cache_of(model.reg_head, "_coalign_pw_cache").get([t for _, h in heads for t in (h.weight, h.bias)], lambda: ops.pack_heads_sp_weight(w))      # (a cache slot of its own: reg_head's fold cache holds the pointwise image)
         y = ops.heads_sp(x, img, b, w.shape[0])
-    elif _bb.CONV_EMU_TERMS in (3, 16) and _bb.POINTWISE_EMU and w.shape[1] % 16 == 0 and w.shape[1] <= 512:
+    elif route.pointwise:
         # round 4: the merged 1x1 heads on the hand-written pointwise kernel (split-bf16 matrix cores; GEMM rows padded to 32), reading the shrink
         # header's map in whatever layout it has and writing the NCHW maps the decode kernel reads -- no rocBLAS / bias pass in the frame
         pk = _cache_of(model.reg_head).get([t for _, h in heads for t in (h.weight, h.bias)], lambda: _bb.PointwisePack(w, False))
@@ -63,17 +65,40 @@ def _run_heads(model: nn.Module, x: torch.Tensor) -> dict:
     return out
 
 
+# split_in: a SplitMap handed over by the shrink header is read by ops.heads_sp (else it is made dense first); pointwise: a float32 map is read by the pointwise kernel
+# (split-bf16 image, Cin <= 512; GEMM rows padded to 32), else by rocBLAS
+HeadsRoute = namedtuple("HeadsRoute", "split_in pointwise")
+
+
+def heads_route(model: nn.Module, terms: Optional[int] = None) -> HeadsRoute:
+    return HeadsRoute(split_in=bool(_bb.HEADS_SPLIT_IN and not model.training and _bb.split_maps_active(terms) and heads_sp_shape_ok(model)),
+                      pointwise=_bb.pointwise_split(model.cls_head.in_channels, terms) and model.cls_head.in_channels <= 512)
+
+
 def heads_take_split_map(model: nn.Module, x=None) -> bool:
     """The merged heads can read the shrink header's map as a SplitMap (``ops.heads_sp``): <= 32 head channels in all, Cin % 16 == 0, eval mode, the switch on."""
-    from . import backbone as _bb
-    if not _bb.HEADS_SPLIT_IN or model.training or not _bb.split_maps_active():
-        return False
-    return heads_sp_shape_ok(model) and model.cls_head.weight.is_cuda
+    return heads_route(model).split_in and model.cls_head.weight.is_cuda
+
+
+def sparse_canvas_route(model: nn.Module, terms: Optional[int] = None) -> bool:
+    """``encode`` has the pillar encoder hand a ``SparseCanvas`` to a backbone whose first block reads it (the encoder adds its own ``matrix_core_ok``)."""
+    resnet = getattr(model.backbone, "resnet", None)
+    first = resnet.layer0[0] if resnet is not None and hasattr(resnet, "layer0") and hasattr(resnet.layer0[0], "takes_sparse_canvas") else None
+    return bool(SPARSE_CANVAS and _bb.FAST_INFERENCE and isinstance(model, PointPillarBaselineMultiscale) and not model.compression and not model.training
+                and first is not None and first.takes_sparse_canvas(terms))
+
+
+def fusion_route(model: nn.Module, channels: Sequence[int]) -> bool:
+    """The static half of the one-launch channels-last fusion: plain attention (``feat_dim`` = the map's channels) or max at every scale, and scales the kernel
+    takes (<= 3 of 64 / 128 / 256 channels: ``ops.warp_fuse_nhwc_ok`` and ``ops.warp_fuse_nhwc`` are the authority and check every call; this copy serves the plan)."""
+    kinds = {type(f) for f in model.fusion_net}
+    plain = kinds == {MaxFusion} or (kinds == {AttFusion} and all(f.feature_dims == c for f, c in zip(model.fusion_net, channels)))
+    return bool(plain and not model.training and len(channels) <= 3 and all(c in (64, 128, 256) for c in channels))
 
 
 def heads_sp_shape_ok(model: nn.Module) -> bool:
     """The merged heads' shape fits ``coalign_heads_sp``: 1 x 1 heads of at most 32 rows in all (``ops.HEADS_SP_MAX_ROWS``) over Cin % 16 == 0 channels."""
-    heads = [model.cls_head, model.reg_head] + ([model.unc_head] if getattr(model, "unc_head", None) is not None else []) + ([model.dir_head] if model.use_dir else [])
+    heads = [h for _, h in _heads(model)]
     rows = sum(h.out_channels for h in heads)
     return rows <= ops.HEADS_SP_MAX_ROWS and model.cls_head.in_channels % 16 == 0 and all(tuple(h.kernel_size) == (1, 1) for h in heads)
 
@@ -90,10 +115,6 @@ def _single_agent_batch(data_dict: dict) -> dict:
         if k in pl:
             batch_dict[k] = pl[k]
     return batch_dict
-
-
-def x_is_cuda(maps) -> bool:
-    return len(maps) > 0 and all(getattr(m, "is_cuda", False) for m in maps)
 
 
 class PointPillarBaselineMultiscale(nn.Module):
@@ -145,18 +166,11 @@ class PointPillarBaselineMultiscale(nn.Module):
 
     def encode(self, data_dict: dict):
         """Per-agent part: pillars -> canvas -> multiscale features.  Returns (feature list, normalised affine)."""
-        pl = data_dict["processed_lidar"]
-        record_len = host_ints(data_dict["record_len"])
-        batch_dict = {"voxel_features": pl["voxel_features"], "voxel_coords": pl["voxel_coords"],
-                      "voxel_num_points": pl["voxel_num_points"], "record_len": record_len}
-        for k in ("voxel_count_dev", "voxel_cells_unique", "want_pillar_features", "pillar_frame"):      # the device voxeliser's streaming form (PillarVFE.forward); FramePipeline's frame record
-            if k in pl:
-                batch_dict[k] = pl[k]
+        batch_dict = _single_agent_batch(dict(data_dict, record_len=host_ints(data_dict["record_len"])))      # (with the device voxeliser's streaming keys and FramePipeline's frame record)
         # round 4: the encoder hands a SparseCanvas (one launch, no dense canvas) to a backbone whose first block reads it
         resnet = getattr(self.backbone, "resnet", None)
-        first = resnet.layer0[0] if resnet is not None and hasattr(resnet, "layer0") and hasattr(resnet.layer0[0], "takes_sparse_canvas") else None
         keep_sparse = self.pillar_vfe.sparse_canvas
-        self.pillar_vfe.sparse_canvas = bool(SPARSE_CANVAS and not self.compression and not self.training and first is not None and first.takes_sparse_canvas())
+        self.pillar_vfe.sparse_canvas = sparse_canvas_route(self)
         try:
             batch_dict = self.scatter(self.pillar_vfe(batch_dict))
         finally:
@@ -178,15 +192,12 @@ class PointPillarBaselineMultiscale(nn.Module):
         run on side streams next to the finest one instead of queueing behind it."""
         n = len(feature_list)
         x0 = feature_list[0]
-        if x0.is_cuda and not self.training:
-            kinds = {type(f) for f in self.fusion_net}
-            # (an AttFusion whose configured feat_dim differs from its map's channels -- no shipped yaml -- takes the per-scale route below,
-            #  where the module rescales its input so that the scores are divided by sqrt(feat_dim) like the reference's)
-            plain_att = kinds == {AttFusion} and all(f.feature_dims == x.shape[1] for f, x in zip(self.fusion_net, feature_list))
-            if plain_att or kinds == {MaxFusion}:
-                fused = fuse_multiscale(feature_list, record_len, affine, ops.FUSE_ATT if kinds == {AttFusion} else ops.FUSE_MAX, rows)
-                if fused is not None:
-                    return fused
+        # (an AttFusion whose configured feat_dim differs from its map's channels -- no shipped yaml -- takes the per-scale route below,
+        #  where the module rescales its input so that the scores are divided by sqrt(feat_dim) like the reference's)
+        if x0.is_cuda and fusion_route(self, [x.shape[1] for x in feature_list]):
+            fused = fuse_multiscale(feature_list, record_len, affine, ops.FUSE_ATT if isinstance(self.fusion_net[0], AttFusion) else ops.FUSE_MAX, rows)
+            if fused is not None:
+                return fused
         if n == 1 or not x0.is_cuda or self.training:
             return [f(x, record_len, affine, rows=rows) for f, x in zip(self.fusion_net, feature_list)]
         main = torch.cuda.current_stream(x0.device)
@@ -211,7 +222,7 @@ class PointPillarBaselineMultiscale(nn.Module):
         """Ego part: per-scale warp + fusion, deblocks, shrink header, heads.  ``rows``: see ``AttFusion.forward``."""
         fused = self._fuse_scales(feature_list, record_len, affine, rows)
         # round 5: a shrink header on the SplitMap route gets the concatenated map from the up-sampling heads already split
-        want_split = bool(self.shrink_flag and x_is_cuda(fused) and self.shrink_conv.takes_split_maps())
+        want_split = bool(self.shrink_flag and len(fused) > 0 and all(getattr(m, "is_cuda", False) for m in fused) and self.shrink_conv.takes_split_maps())
         x = self.backbone.decode_multiscale_feature(fused, out_split=True) if want_split else self.backbone.decode_multiscale_feature(fused)
         if self.shrink_flag:
             x = self.shrink_conv(x, out_split=isinstance(x, ops.SplitMap) and heads_take_split_map(self))

@@ -71,6 +71,9 @@ class PillarVFE(nn.Module):
     def get_output_feature_dim(self) -> int:
         return self.num_filters[-1]
 
+    def matrix_core_ok(self, max_points: int) -> bool:      # the matrix-core encoders take these pillars (else the fp32 VALU encoder); routes.plan asks too
+        return not self.with_distance and max_points <= 32 and self.num_filters[-1] <= 64
+
     def forward(self, batch_dict: dict) -> dict:
         if len(self.pfn_layers) != 1:
             raise NotImplementedError("stacked PFN layers are outside the CoAlign hot path (configs use num_filters: [64])")
@@ -86,7 +89,7 @@ class PillarVFE(nn.Module):
         from . import backbone                       # the canvas layout follows the convolution route that will read it
         channels_last = backbone.NHWC_STAGE_OUTPUTS and backbone.emu_active() and backbone.FAST_INFERENCE
         count_dev = batch_dict.get("voxel_count_dev")
-        if self.sparse_canvas and channels_last and not self.with_distance and vf.shape[1] <= 32 and self.num_filters[-1] <= 64:
+        if self.sparse_canvas and channels_last and self.matrix_core_ok(vf.shape[1]):
             # round 4 fast path (the detector switches it on when its first ResNet block consumes it): ONE launch, feature rows + cell stamps, no dense canvas
             eps = pfn.norm.eps if self.use_norm else 0.0
             cache = self.__dict__.get("_folded_cache")

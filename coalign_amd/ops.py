@@ -7,6 +7,7 @@ in this package (the CPU restatement lives in ``oracle/`` and is test infrastruc
 from __future__ import annotations
 
 import ctypes
+import os as _os
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -967,7 +968,6 @@ def _sp_workspace(device, ws_bytes: int) -> torch.Tensor:
 
 # Measurement switch (round 6): COALIGN_SP_GEO="25x88:121,50x176:81" overrides the tile geometry `coalign_conv3x3_sp` picks for maps of the listed H x W
 # (codes: include/coalign_amd.h (9e)); read once at import, the dict is read per call.
-import os as _os
 SP_GEO_OVERRIDE = {tuple(int(v) for v in k.split("x")): int(g) for k, g in (item.split(":") for item in _os.environ.get("COALIGN_SP_GEO", "").split(",") if item)}
 
 SP_RES_NONE, SP_RES_SP, SP_RES_NHWC = 0, 1, 2      # residual_kind of coalign_conv3x3_sp

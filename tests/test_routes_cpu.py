@@ -25,7 +25,7 @@ NULL, ONE = ctypes.c_void_p(0), ctypes.c_void_p(16)      # (a non-NULL, 16-byte 
 HW = 8
 
 
-def _mutant(num_filters=None, shrink=None, upf=None, anchors=None):
+def _mutant(num_filters=None, shrink=None, upf=None, anchors=None, layer_nums=None, stem=None):
     h = copy.deepcopy(builtin_config("opv2v_coalign"))
     a = h["model"]["args"]
     if num_filters is not None:
@@ -39,6 +39,19 @@ def _mutant(num_filters=None, shrink=None, upf=None, anchors=None):
         a["shrink_header"].update(dim=list(shrink), kernal_size=[3] * n, stride=[1] * n, padding=[1] * n)
     if anchors is not None:
         a["anchor_number"] = anchors
+    if layer_nums is not None:                  # (one block per stage: the stage's last block is its strided opener, no SplitMap is handed to the next stage)
+        a["base_bev_backbone"]["layer_nums"] = list(layer_nums)
+    if stem is not None:                        # (a canvas of `stem` channels: below 32 the first block's opener on a sparse canvas is the consumer-split kernel)
+        a["pillar_vfe"]["num_filters"] = [stem]
+        a["point_pillar_scatter"]["num_features"] = stem
+        a["base_bev_backbone"]["inplanes"] = stem
+    return h
+
+
+def _late_resnet():
+    """The single-agent detector on the ResNet backbone: its forward never asks the encoder for a sparse canvas (only the multi-agent ``encode`` does)."""
+    h = copy.deepcopy(builtin_config("opv2v_pointpillar_late"))
+    h["model"]["args"]["base_bev_backbone"]["resnet"] = True
     return h
 
 
@@ -56,6 +69,9 @@ MUTANTS = {
     "anchors_1": _mutant(anchors=1),
     "anchors_3": _mutant(anchors=3),
     "anchors_4": _mutant(anchors=4),
+    "one_block_stages": _mutant(layer_nums=(1, 1, 1)),
+    "stem_16": _mutant(stem=16),
+    "late_resnet": _late_resnet(),
 }
 
 
@@ -148,6 +164,36 @@ def test_split_map_predicate_equals_the_kernels_checks(cin):
         assert bb.sp_channels_ok(None, cout) == (_sp(16, cout) == 0), cout
     for rows in (1, 31, 32, 33, 40):
         assert (rows <= ops.HEADS_SP_MAX_ROWS and cin % 16 == 0) == (_heads_sp(cin, rows) == 0), (cin, rows)
+
+
+@pytest.mark.parametrize("name", list(MUTANTS))
+def test_route_plan_prints_what_the_modules_decide(name):
+    """One implementation: the string ``plan`` prints for a layer is the wording of the decision its module's ``forward`` dispatches on (``BasicBlock.route``,
+    ``DoubleConv.on_split_maps``, the decode mixin, ``detector.heads_route``) -- in the default arithmetic asked without ``terms``, as ``forward`` asks.
+    Fails when ``routes.py`` grows a rule of its own again."""
+    h = MUTANTS[name]
+    for terms in (None, 3):
+        p = plan(h) if terms is None else plan(h, terms)
+        r = p["layers"]
+        model = build_model(h).eval()
+        heads_split = (bb.HEAD_SPLIT_MAPS and model.shrink_conv.layers[0].on_split_maps(terms)) and model.backbone.heads_write_split(terms)
+        for n, m in model.named_modules():
+            if isinstance(m, bb.BasicBlock):
+                d = m.route(terms)
+                split = d.kind == bb.BLOCK_SPLIT
+                assert (r[f"{n}.conv2"] == SP) == split and (r[f"{n}.conv1"] == SP) == (split and m.stride == 1), (n, d)
+                assert r[f"{n}.conv1"].endswith("SplitMap out") == (split and m.stride == 2), (n, d)
+                assert m.downsample is None or r[f"{n}.downsample.0"].startswith("pointwise") == m.skip_pointwise(), (n, d)
+                assert m.takes_split_maps() == (m.route().kind == bb.BLOCK_SPLIT)
+            elif isinstance(m, bb.DoubleConv):
+                assert (r[f"{n}.double_conv.2"] == SP) == m.on_split_maps(terms), n
+                assert (r[f"{n}.double_conv.0"] == SP) == bool(m is model.shrink_conv.layers[0] and heads_split), n
+                assert r[f"{n}.double_conv.0"].endswith("SplitMap out") == (m.on_split_maps(terms) and r[f"{n}.double_conv.0"] != SP), n
+        for i in range(model.backbone.num_levels):
+            assert r[f"backbone.deblocks.{i}"].startswith("pointwise") == model.backbone.heads_pointwise()
+            assert ("concatenated SplitMap" in r[f"backbone.deblocks.{i}"]) == bool(heads_split)
+        assert r["cls_head"].startswith("pointwise") == detector.heads_route(model, terms).pointwise
+        assert ("sparse canvas" in p["pillar"]) == detector.sparse_canvas_route(model, terms)
 
 
 def _calls_stream(fn) -> bool:

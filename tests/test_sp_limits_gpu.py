@@ -17,7 +17,9 @@ import torch.nn.functional as F
 
 from coalign_amd import backbone as bb
 from coalign_amd import detector, ops
-from coalign_amd.synthetic import fill_parameters_
+from coalign_amd.config import builtin_config
+from coalign_amd.routes import NARROW, SP, plan
+from coalign_amd.synthetic import fill_parameters_, make_frame
 from conftest import assert_elementwise
 from sp_helpers import assert_split_map_holds, sparse_canvas
 
@@ -193,11 +195,11 @@ def test_conv3x3_sp_s2_on_the_sparse_canvas_mixed_channel_scales_and_fused_skip_
 
 # ------------------------------------------------------------------------------------------------ modules at the edges of their route predicates
 class _Spy:
-    """Records which kernel served which layer during one forward."""
+    """Records which kernel served which layer during one forward; ``more``: further ``ops`` names, recorded as (name, output channels or None, None)."""
 
-    def __init__(self, monkeypatch):
-        self.calls = []
-        for name in ("conv3x3_sp", "conv3x3_sp_s2", "heads_sp"):
+    def __init__(self, monkeypatch, more=()):
+        self.calls, self.more = [], tuple(more)
+        for name in ("conv3x3_sp", "conv3x3_sp_s2", "heads_sp") + self.more:
             monkeypatch.setattr(ops, name, self._wrap(name, getattr(ops, name)))
         monkeypatch.setattr(F, "conv2d", self._wrap("F.conv2d", F.conv2d))
 
@@ -205,6 +207,8 @@ class _Spy:
         def spy(*args, **kwargs):
             if name == "F.conv2d":
                 self.calls.append((name, tuple(args[1].shape[:2]), None))
+            elif name in self.more:
+                self.calls.append((name, args[3] if len(args) > 3 and isinstance(args[3], int) else None, None))
             elif name == "heads_sp":
                 self.calls.append((name, args[0].shape[1], args[3]))
             else:
@@ -323,6 +327,47 @@ def test_merged_heads_route_at_32_rows_against_float64(rows, monkeypatch):
     assert detector.heads_take_split_map(m) == (rows <= 32)
     assert [c[1:] for c in spy.of("heads_sp")] == ([(256, rows)] if rows <= 32 else [])
     assert spy.of("F.conv2d") == []                                          # (33 rows: the pointwise kernel on the float32 map)
+
+
+@pytest.mark.parametrize("cfg,compression", [("mini_coalign", None), ("opv2v_coalign", None), ("opv2v_coalign", 4)])
+def test_one_forward_launches_the_kernels_the_plan_names(cfg, compression, monkeypatch):
+    """``routes.plan`` against what ``forward`` launches (not against the kernels' argument checks): one forward of the whole detector under a spy calls
+    ``conv3x3_sp`` once per layer the plan puts on it, ``conv3x3_sp_s2`` once per strided SplitMap opener, ``conv3x3_sp_narrow`` for the compressor's encoder,
+    one of ``heads_sp`` / ``pointwise_conv`` for the merged heads where the plan names the pointwise kernel, and the library not at all when the plan lists
+    no fallback."""
+    h = copy.deepcopy(builtin_config(cfg))
+    if compression is not None:
+        h["model"]["args"]["compression"] = compression
+    assert bb.CONV_EMU_TERMS == bb.DEFAULT_CONV_EMU_TERMS          # (the plan below is the default arithmetic's)
+    p = plan(h)
+    model = detector.build_model(h)
+    fill_parameters_(model, seed=7)
+    model = model.to(DEV).eval()
+    frame = detector.to_device(make_frame(h, 2, pillars_per_agent=150, seed=3, spread_xy=(4.0, 2.0), spread_yaw=45.0), DEV)
+    with torch.no_grad():
+        spy = _Spy(monkeypatch, more=("conv3x3_sp_narrow", "pointwise_conv"))
+        out = model(frame)
+    assert all(bool(torch.isfinite(v).all()) for v in out.values())
+    mods = dict(model.named_modules())
+    routes = p["layers"]
+    # the strided openers of the plan ("..., SplitMap out" inside the ResNet): conv3x3_sp_s2 where the block's own decision says so for the input it gets
+    # (a sparse canvas for the first block when the encoder hands one over, a dense map or a SplitMap otherwise), else the consumer-split kernel
+    blocks = [mods[n.rsplit(".", 1)[0]] for n, r in routes.items() if r.endswith("SplitMap out") and ".resnet." in n]
+    first = model.backbone.resnet.layer0[0]
+    openers = [b for b in blocks if (b.route().s2_sparse if b is first and detector.sparse_canvas_route(model) else b.route().s2_dense)]
+    assert len(blocks) == 3 and (cfg != "opv2v_coalign" or p["fallbacks"] == [])
+    print(f"\n{cfg} compression {compression}: kernels {sorted(set(c[0] for c in spy.calls))}, fallbacks {p['fallbacks']}")
+    assert len(spy.of("conv3x3_sp")) == sum(r.startswith(SP) for r in routes.values()) > 0
+    assert len(spy.of("conv3x3_sp_s2")) == len(openers) > 0
+    assert len(spy.of("conv3x3_sp_narrow")) == sum(r.startswith(NARROW) for r in routes.values()) == (0 if compression is None else 1)
+    rows = sum(getattr(model, k).out_channels for k in ("cls_head", "reg_head", "dir_head"))
+    head_launches = len(spy.of("heads_sp")) + len([c for c in spy.of("pointwise_conv") if c[1] == rows])
+    assert head_launches == (1 if routes["cls_head"].startswith("pointwise") else 0)
+    # the heads read a SplitMap where their route allows it and a one-layer shrink header on the SplitMap route, fed by the heads, hands one over
+    handed = (routes.get("shrink_conv.layers.0.double_conv.0") == SP and len(model.shrink_conv.layers) == 1)
+    assert len(spy.of("heads_sp")) == int(detector.heads_route(model).split_in and handed)
+    if p["fallbacks"] == []:
+        assert spy.of("F.conv2d") == []
 
 
 # ------------------------------------------------------------------------------------------------ device placement of the ops (ops._device_op)
