@@ -5,7 +5,9 @@ Mirrors ``opencood/models/sub_modules/box_align_v2.py`` (``box_alignment_relativ
 one small graph per frame inside ``__getitem__`` and solves it with g2o on the CPU; here the graph construction stays host
 code (a few hundred boxes, set logic) and the Levenberg-Marquardt solve is ``coalign_pose_graph_optimize`` on the device --
 one workgroup per graph, so the graphs of a whole split (``tools/pose_graph_pre_calc.py`` style) go out in one launch
-(``box_alignment_batch``).
+(``box_alignment_batch``).  ``PoseCorrector`` is the per-frame form with no host in the middle: the same construction as ONE device launch
+(``coalign_pose_graph_build``, include/coalign_amd_align.h) between the stage-1 gather and the solver, and the corrected pairwise / affine matrices written
+where the fusion model reads them.
 
 Numerics kept from the reference: numpy inputs pass through ``pose_to_tfm`` / ``project_box3d`` in **float32**
 (common_utils.check_numpy_to_torch), so world-frame centres, the 1.5 m clustering threshold and the landmark
@@ -220,6 +222,48 @@ def box_alignment_batch(samples: Sequence[dict], max_iterations: int = 1000, dev
     live = [g for g in graphs if g is not None]
     solved = iter(optimize_pose_graphs(live, max_iterations, device)[0])
     return [_refined(g, next(solved) if g is not None else None, s["noisy_lidar_pose"]) for g, s in zip(graphs, samples)]
+
+
+class PoseCorrector:
+    """Online pose correction of ONE lane, on the device (include/coalign_amd_align.h): owns the stage-1 box store, the graph arrays, the solver workspace and
+    the output matrices.  ``box_align_args``: the keyword arguments of ``box_alignment_relative_sample_np`` (a yaml's ``box_align.args``); ``H, W,
+    discrete_ratio, downsample_rate`` as ``pose.normalize_pairwise_np`` takes them.  ``correct`` enqueues three launches on the current stream --
+    ``coalign_pose_graph_build`` (``build_pose_graph``), ``coalign_pose_graph_optimize``, ``coalign_pose_correct_matrices`` (``_refined`` +
+    ``pose.get_pairwise_transformation`` + ``pose.normalize_pairwise_np``) -- and reads nothing back: it can be captured in a HIP graph."""
+
+    def __init__(self, box_align_args: Optional[dict], max_cav: int, H: int, W: int, discrete_ratio: float, downsample_rate: float = 1, proj_first: bool = False,
+                 device="cuda:0", uncertainty_dim: int = 3):
+        args = dict(box_align_args or {})
+        self.thres, self.yaw_var_thres = float(args.pop("thres", 1.5)), float(args.pop("yaw_var_thres", 0.2))
+        self.max_iterations = int(args.pop("max_iterations", 1000))
+        args.pop("device", None)
+        self.flags = ops.align_flags(**args)
+        self.max_cav, self.H, self.W, self.proj_first = int(max_cav), int(H), int(W), bool(proj_first)
+        self.den_x, self.den_y = downsample_rate * discrete_ratio * W, downsample_rate * discrete_ratio * H
+        self.device = torch.device(device)
+        self.store = ops.Stage1Store(self.device, uncertainty_dim)
+        self.graph = ops.PoseGraphArrays(self.device)
+        self._poses = torch.zeros((MAX_AGENTS, 6), dtype=torch.float64, device=self.device)
+        self.pairwise_t_matrix = torch.zeros((1, self.max_cav, self.max_cav, 4, 4), dtype=torch.float64, device=self.device)
+        self.normalized_affine_matrix = torch.zeros((1, self.max_cav, self.max_cav, 2, 3), dtype=torch.float64, device=self.device)
+
+    def correct(self, store: Optional["ops.Stage1Store"], noisy_lidar_poses: torch.Tensor) -> dict:
+        """``store`` (None: the corrector's own) + noisy poses [N, 6] float64 on the device (degrees) -> the corrected ``lidar_poses`` [N, 6],
+        ``pairwise_t_matrix`` [1, L, L, 4, 4], ``normalized_affine_matrix`` [1, L, L, 2, 3] (float64, this object's buffers: valid until the next call) and
+        ``status`` ([1] int32 on the device, ``ops.ALIGN_*``; nothing here reads it).  ``stats``: the solver's [1, 4]."""
+        store = self.store if store is None else store
+        if not (torch.is_tensor(noisy_lidar_poses) and noisy_lidar_poses.is_cuda and store.corners.is_cuda):
+            raise ops.hip.CoalignHipError("PoseCorrector.correct runs on the MI355X only: got a CPU tensor (no CPU fallback exists)")
+        n = int(noisy_lidar_poses.shape[0])
+        if not 1 <= n <= min(MAX_AGENTS, self.max_cav):
+            raise ValueError(f"{n} agents: outside 1 .. min({MAX_AGENTS}, max_cav = {self.max_cav})")
+        out = self._poses[:n]
+        ops.pose_graph_build(store, noisy_lidar_poses, self.graph, self.flags, self.thres, self.yaw_var_thres)
+        ops.pose_graph_solve(self.graph, self.max_iterations)
+        ops.pose_correct_matrices(noisy_lidar_poses, self.graph.vertices, store.status, self.max_cav, self.H, self.W, self.den_x, self.den_y, self.proj_first,
+                                  out, self.pairwise_t_matrix, self.normalized_affine_matrix)
+        return {"lidar_poses": out, "pairwise_t_matrix": self.pairwise_t_matrix, "normalized_affine_matrix": self.normalized_affine_matrix,
+                "status": store.status, "stats": self.graph.stats}
 
 
 def box_alignment_relative_np(pred_corner3d_list, uncertainty_list, lidar_poses, record_len, **kwargs) -> np.ndarray:

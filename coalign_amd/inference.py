@@ -48,3 +48,29 @@ def inference_early_fusion(batch_data: dict, model, post_processor: VoxelPostpro
 
 def inference_intermediate_fusion(batch_data: dict, model, post_processor: VoxelPostprocessor, gt_box_tensor=None) -> dict:
     return inference_early_fusion(batch_data, model, post_processor, gt_box_tensor)
+
+
+def inference_intermediate_fusion_aligned(batch_data: dict, model, post_processor: VoxelPostprocessor, stage1_model=None, stage1_post_processor=None,
+                                          corrector=None, gt_box_tensor=None) -> dict:
+    """Intermediate fusion with ONLINE pose correction (the hook of intermediate_fusion_dataset.py:301-328 moved behind a live stage-1 forward, all on the
+    device): the stage-1 model over the frame's agents (``processed_lidar`` with the agent as batch index; ``processed_lidar_stage1`` when the stage-1 range
+    differs) -> ``post_process_stage1_device`` -> ``corrector.correct`` on ``batch_data['ego']['lidar_poses']`` -> the fusion model with
+    ``normalized_affine_matrix`` (and ``pairwise_t_matrix``) replaced by the corrected ones -> the ordinary post-process.  Returns what
+    ``inference_intermediate_fusion`` returns plus ``lidar_poses_corrected`` and ``align_status`` (device tensors).  With ``corrector=None`` it IS
+    ``inference_intermediate_fusion`` and touches neither stage-1 object."""
+    if corrector is None:
+        return inference_intermediate_fusion(batch_data, model, post_processor, gt_box_tensor)
+    if stage1_model is None or stage1_post_processor is None:
+        raise ValueError("pose correction needs the stage-1 model and its post-processor")
+    ego = batch_data["ego"]
+    with torch.no_grad():
+        stage1_out = stage1_model({"processed_lidar": ego.get("processed_lidar_stage1", ego["processed_lidar"])})
+        anchors = ego.get("anchor_box_stage1", ego["anchor_box"])
+        store = stage1_post_processor.post_process_stage1_device(stage1_out, anchors, corrector.store)
+        poses = torch.as_tensor(ego["lidar_poses"]).to(device=stage1_out["cls_preds"].device, dtype=torch.float64).contiguous()
+        fixed = corrector.correct(store, poses)
+        aligned = dict(batch_data, ego=dict(ego, pairwise_t_matrix=fixed["pairwise_t_matrix"], normalized_affine_matrix=fixed["normalized_affine_matrix"]))
+        result = inference_intermediate_fusion(aligned, model, post_processor, gt_box_tensor)
+    result["lidar_poses_corrected"] = fixed["lidar_poses"]
+    result["align_status"] = fixed["status"]
+    return result

@@ -59,6 +59,10 @@ def _device_tensor(a) -> Optional[torch.Tensor]:
         a = a.feats
     elif isinstance(a, SplitMap):
         a = a.data
+    elif isinstance(a, Stage1Store):
+        a = a.corners
+    elif isinstance(a, PoseGraphArrays):
+        a = a.vertices
     elif isinstance(a, (list, tuple)):
         return next((t for t in map(_device_tensor, a) if t is not None), None)
     return a if torch.is_tensor(a) and a.is_cuda else None
@@ -575,6 +579,7 @@ class DecodeBuffers:
     def __init__(self, capacity: int, A: int, H: int, W: int, top: int, device):
         L = hip.lib()
         self.capacity, self.top = capacity, top
+        self.dec_A, self.dec_HW = A, (H, W)
         self.frame_words = torch.zeros(67, dtype=torch.int32, device=device)  # cleared once per frame by ONE launch (reset_frame); copied to the host as ONE block
         self.counts = self.frame_words[:64]                                    # chained per-agent totals
         self.status = self.frame_words[64:65]
@@ -782,6 +787,139 @@ def pose_graph_optimize(vertex_offsets: torch.Tensor, edge_offsets: torch.Tensor
         hip.check(L.coalign_pose_graph_optimize(G, _ptr(vo), _ptr(eo), _ptr(na), V, _ptr(out), _ptr(kd), _ptr(ea), _ptr(el), _ptr(em), _ptr(ew),
                                                 int(max_iterations), _ptr(stats), _ptr(ws), ws_bytes, _stream()), "coalign_pose_graph_optimize")
     return out, stats
+
+
+# ---------------------------------------------------------------------------------------------- online pose correction (include/coalign_amd_align.h)
+ALIGN_MAX_AGENTS, ALIGN_MAX_LANDMARKS = 8, 256
+ALIGN_MAX_VERTICES = ALIGN_MAX_AGENTS + ALIGN_MAX_LANDMARKS
+ALIGN_SOLVED, ALIGN_KEPT_NOISY, ALIGN_NO_BOXES, ALIGN_OUTSIDE_LIMITS, ALIGN_STORE_OVERFLOW, ALIGN_TOO_MANY_LANDMARKS = 0, 1, 2, 4, 8, 16
+ALIGN_FLAG_BITS = {"use_uncertainty": 1, "landmark_SE2": 2, "adaptive_landmark": 4, "normalize_uncertainty": 8, "abandon_hard_cases": 16,
+                   "drop_hard_boxes": 32, "drop_unsure_edge": 64}
+
+
+class Stage1Store:
+    """Caller-owned box store of ONE sample: the kept stage-1 detections of up to 8 agents, each in its agent's frame.  corners [8, C, 8, 3], uncertainty
+    [8, C, udim], count [8] int32, status [1] int32 (``ALIGN_*``).  float32 is what ``stage1_gather`` fills; a float64 store takes boxes that did not come
+    from the float32 stage-1 kernels (``upload``)."""
+
+    def __init__(self, device, udim: int = 3, dtype: torch.dtype = torch.float32):
+        if dtype not in (torch.float32, torch.float64) or not 0 <= int(udim) <= 3:
+            raise ValueError("Stage1Store: float32 / float64, 0 <= udim <= 3")
+        self.boxes = int(hip.lib().coalign_align_store_boxes())
+        self.udim = int(udim)
+        self.corners = torch.zeros((ALIGN_MAX_AGENTS, self.boxes, 8, 3), dtype=dtype, device=device)
+        self.unc = torch.zeros((ALIGN_MAX_AGENTS, self.boxes, max(1, self.udim)), dtype=dtype, device=device)
+        self.words = torch.zeros(ALIGN_MAX_AGENTS + 1, dtype=torch.int32, device=device)
+        self.count, self.status = self.words[:ALIGN_MAX_AGENTS], self.words[ALIGN_MAX_AGENTS:]
+        self.n_agents = 0
+
+    def upload(self, corners_list, uncertainty_list=None) -> "Stage1Store":
+        """Fill the store from host (or device) arrays, one [K_i, 8, 3] (and [K_i, udim]) per agent -- tests and tools; allocates and synchronises."""
+        if len(corners_list) > ALIGN_MAX_AGENTS:
+            raise ValueError(f"a sample has at most {ALIGN_MAX_AGENTS} agents")
+        dev, dt = self.corners.device, self.corners.dtype
+        words = [0] * (ALIGN_MAX_AGENTS + 1)
+        for i, c in enumerate(corners_list):
+            c = torch.as_tensor(np.asarray(c) if not torch.is_tensor(c) else c).reshape(-1, 8, 3)
+            n = min(int(c.shape[0]), self.boxes)
+            words[i] = n
+            if c.shape[0] > self.boxes:
+                words[ALIGN_MAX_AGENTS] |= ALIGN_STORE_OVERFLOW
+            self.corners[i, :n] = c[:n].to(device=dev, dtype=dt)
+            if uncertainty_list is not None and self.udim:
+                u = uncertainty_list[i]
+                u = torch.as_tensor(np.asarray(u) if not torch.is_tensor(u) else u).reshape(-1, self.udim)
+                self.unc[i, :n] = u[:n].to(device=dev, dtype=dt)
+        self.words.copy_(torch.tensor(words, dtype=torch.int32))
+        self.n_agents = len(corners_list)
+        return self
+
+
+@_device_op
+def stage1_gather(buf: DecodeBuffers, unc: Optional[torch.Tensor], store: Stage1Store, slot: int) -> None:
+    """After ``anchor_decode`` (slot 0, identity transform) + ``nms_rotated_device`` of ONE agent on ``buf``: copy the kept corners and the raw ``unc``
+    ([A * udim, H, W]) of the kept anchors into slot ``slot`` of ``store``; slot 0 opens the frame's status word.  No host synchronisation."""
+    _need_gpu(buf.counts, unc, store.corners)
+    if store.corners.dtype != torch.float32:
+        raise ValueError("stage1_gather fills a float32 store")
+    A_udim, H, W = (0, 1, 1) if unc is None else unc.shape[-3:]
+    A = buf.dec_A
+    udim = 0 if unc is None else A_udim // A
+    if udim != store.udim or (unc is not None and (A_udim % A or unc.dtype != torch.float32 or not unc.is_contiguous())):
+        raise ValueError("unc must be contiguous float32 [A * udim, H, W] with the store's udim")
+    if unc is None:
+        H, W = buf.dec_HW
+    hip.check(hip.lib().coalign_stage1_gather(_ptr(buf.keep), _ptr(buf.keep_count), _ptr(buf.cand_index), _ptr(buf.cand_corners), buf.capacity, _ptr(unc),
+                                              A, udim, int(H), int(W), int(slot), _ptr(store.corners), _ptr(store.unc), _ptr(store.count), _ptr(store.status),
+                                              _stream()), "coalign_stage1_gather")
+
+
+class PoseGraphArrays:
+    """The graph arrays of one sample at their fixed capacities (what ``coalign_pose_graph_optimize`` reads for one graph), the solver's workspace and stats."""
+
+    def __init__(self, device):
+        L = hip.lib()
+        V, E = ALIGN_MAX_VERTICES, ALIGN_MAX_AGENTS * int(L.coalign_align_store_boxes())
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=device)
+        f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)
+        self.vertex_off, self.edge_off, self.n_agents = i32(2), i32(2), i32(1)
+        self.vertices, self.kinds = f64(V, 3), i32(V)
+        self.edge_agent, self.edge_landmark, self.edge_meas, self.edge_info = i32(E), i32(E), f64(E, 3), f64(E, 3)
+        self.stats = f64(1, 4)
+        self.ws_bytes = L.coalign_pose_graph_workspace_bytes(V)
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=device)
+
+
+def align_flags(**flags) -> int:
+    """Keyword arguments of ``box_alignment_relative_sample_np`` -> the flag word of ``coalign_pose_graph_build`` (the reference's defaults)."""
+    given = dict({"use_uncertainty": True, "landmark_SE2": True}, **flags)
+    unknown = set(given) - set(ALIGN_FLAG_BITS)
+    if unknown:
+        raise ValueError(f"unknown box alignment flags {sorted(unknown)}")
+    return sum(bit for name, bit in ALIGN_FLAG_BITS.items() if given.get(name, False))
+
+
+@_device_op
+def pose_graph_build(store: Stage1Store, noisy_poses: torch.Tensor, graph: PoseGraphArrays, flags: int, thres: float = 1.5, yaw_var_thres: float = 0.2,
+                     with_uncertainty: bool = True) -> None:
+    """``box_align.build_pose_graph`` on the device: ``store`` + noisy poses [N, 6] float64 (degrees) -> ``graph`` and the sample's status word
+    (``store.status``).  One launch, no host synchronisation."""
+    _need_gpu(store.corners, noisy_poses, graph.vertices)
+    if noisy_poses.dtype != torch.float64 or noisy_poses.dim() != 2 or noisy_poses.shape[1] != 6 or not noisy_poses.is_contiguous():
+        raise ValueError("noisy_poses must be contiguous float64 [N, 6]")
+    unc = store.unc if (with_uncertainty and store.udim) else None
+    hip.check(hip.lib().coalign_pose_graph_build(1, int(noisy_poses.shape[0]), _ptr(store.corners), _ptr(unc), int(store.corners.dtype == torch.float64), store.udim,
+                                                 _ptr(store.count), _ptr(noisy_poses), int(flags), float(thres), float(yaw_var_thres), _ptr(graph.vertex_off),
+                                                 _ptr(graph.edge_off), _ptr(graph.n_agents), _ptr(graph.vertices), _ptr(graph.kinds), _ptr(graph.edge_agent),
+                                                 _ptr(graph.edge_landmark), _ptr(graph.edge_meas), _ptr(graph.edge_info), _ptr(store.status), _stream()),
+              "coalign_pose_graph_build")
+
+
+@_device_op
+def pose_graph_solve(graph: PoseGraphArrays, max_iterations: int = 1000) -> None:
+    """``coalign_pose_graph_optimize`` in place on the arrays ``pose_graph_build`` wrote (offsets read on the device; the capacity as ``total_vertices``)."""
+    _need_gpu(graph.vertices)
+    hip.check(hip.lib().coalign_pose_graph_optimize(1, _ptr(graph.vertex_off), _ptr(graph.edge_off), _ptr(graph.n_agents), ALIGN_MAX_VERTICES, _ptr(graph.vertices),
+                                                    _ptr(graph.kinds), _ptr(graph.edge_agent), _ptr(graph.edge_landmark), _ptr(graph.edge_meas), _ptr(graph.edge_info),
+                                                    int(max_iterations), _ptr(graph.stats), _ptr(graph.ws), graph.ws_bytes, _stream()), "coalign_pose_graph_optimize")
+
+
+@_device_op
+def pose_correct_matrices(noisy_poses: torch.Tensor, vertices: torch.Tensor, status: torch.Tensor, max_cav: int, H: int, W: int, den_x: float, den_y: float,
+                          proj_first: bool, poses_out: torch.Tensor, pairwise: torch.Tensor, affine: torch.Tensor) -> None:
+    """Refined (x, y, yaw) (or the noisy poses, by ``status``) -> corrected poses [N, 6], pairwise [1, L, L, 4, 4], normalised affine [1, L, L, 2, 3], float64."""
+    _need_gpu(noisy_poses, vertices, status, poses_out, pairwise, affine)
+    n = int(noisy_poses.shape[0])
+    ok = (noisy_poses.dtype == torch.float64 and noisy_poses.is_contiguous() and tuple(noisy_poses.shape) == (n, 6) and vertices.dtype == torch.float64
+          and tuple(vertices.shape) == (ALIGN_MAX_VERTICES, 3) and vertices.is_contiguous() and status.dtype == torch.int32
+          and poses_out.dtype == torch.float64 and tuple(poses_out.shape) == (n, 6) and poses_out.is_contiguous()
+          and pairwise.dtype == torch.float64 and pairwise.numel() == max_cav * max_cav * 16 and pairwise.is_contiguous()
+          and affine.dtype == torch.float64 and affine.numel() == max_cav * max_cav * 6 and affine.is_contiguous())
+    if not ok:
+        raise ValueError("pose_correct_matrices: float64 contiguous [N, 6] poses, [264, 3] vertices, [L, L, 4, 4] / [L, L, 2, 3] outputs, int32 status")
+    hip.check(hip.lib().coalign_pose_correct_matrices(1, n, _ptr(noisy_poses), _ptr(vertices), _ptr(status), int(max_cav), int(bool(proj_first)), int(H), int(W),
+                                                      float(den_x), float(den_y), _ptr(poses_out), _ptr(pairwise), _ptr(affine), _stream()),
+              "coalign_pose_correct_matrices")
 
 
 CONV_KC, CONV_WSTRIDE = 8, 9 * 64 + 32      # kKC / kWStride of csrc/conv3x3.hip

@@ -280,6 +280,34 @@ class UncertaintyVoxelPostprocessor(VoxelPostprocessor):
             return None, None, None
         return corners, boxes, uncertainty
 
+    def post_process_stage1_device(self, stage1_output_dict: dict, anchor_box, store: "ops.Stage1Store") -> "ops.Stage1Store":
+        """The loop of ``post_process_stage1`` without its read-backs: per agent the same decode and NMS launches, then ONE gather launch
+        (``coalign_stage1_gather``) that copies the kept corners and the raw ``unc_preds`` of the kept anchors into slot ``i`` of the caller-owned ``store``
+        -- bit for bit the lists ``post_process_stage1`` returns, for the first ``store.boxes`` kept boxes of an agent (more: the overflow bit of the store's
+        status word).  Everything on the current stream; no host synchronisation and, once the buffers and anchors exist, no allocation: capturable."""
+        cls, reg, unc = stage1_output_dict["cls_preds"], stage1_output_dict["reg_preds"], stage1_output_dict["unc_preds"]
+        dirp = stage1_output_dict.get("dir_preds")
+        device = cls.device
+        n_agents, A, H, W = cls.shape
+        if n_agents > ops.ALIGN_MAX_AGENTS:
+            raise ValueError(f"pose correction handles at most {ops.ALIGN_MAX_AGENTS} agents per frame")
+        anchors = self._anchors_f32(anchor_box, device)
+        key = ("stage1", str(device), A, H, W)
+        ring = self._buffers.get(key)
+        if ring is None:
+            ring = self._buffers[key] = [ops.DecodeBuffers(A * H * W, A, H, W, NMS_TOP, device)]
+        buf = ring[0]
+        thr = self.params["target_args"]["score_threshold"]
+        da = self.params.get("dir_args", {})
+        for i in range(n_agents):
+            ops.anchor_decode(buf, 0, cls[i], reg[i], None if dirp is None else dirp[i], anchors, thr, da.get("dir_offset", 0.0),
+                              da.get("num_bins", 2), self.params["order"], None, clear_frame=True)
+            ops.nms_rotated_device(buf.cand_corners, buf.cand_score, self.params["nms_thresh"], NMS_TOP, valid=None, k_dev=buf.counts[1:2],
+                                   keep=buf.keep, keep_count=buf.keep_count, ws=buf.nms_ws)
+            ops.stage1_gather(buf, unc[i], store, i)
+        store.n_agents = n_agents
+        return store
+
 
 POSTPROCESSORS = {"VoxelPostprocessor": VoxelPostprocessor, "UncertaintyVoxelPostprocessor": UncertaintyVoxelPostprocessor}
 
