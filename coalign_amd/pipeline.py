@@ -32,6 +32,9 @@ mode one async copy + one replay per frame.  ``latencies_ms`` records, per frame
 from __future__ import annotations
 
 import collections
+import os
+import time
+import weakref
 from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -39,12 +42,10 @@ import torch
 
 from . import ops
 from .encoder import host_ints
+from .pose import normalize_pairwise_np
 from .postprocess import PostProcessHandle, VoxelPostprocessor
 
-import os as _os
-POST_PROCESS_SIDE_STREAM = _os.environ.get("COALIGN_PP_SIDE", "1") != "0"       # measurement switch (tools/ab_bench.sh)
-GRAPH_PERSISTENT_CANVAS = _os.environ.get("COALIGN_GRAPH_PERSIST", "1") != "0"  # measurement switch
-FRAME_RECORDS = _os.environ.get("COALIGN_FRAME_RECORDS", "1") != "0"            # measurement switch: 0 = every frame is copied into the graph's input buffers (rounds 2-4)
+FRAME_RECORDS = os.environ.get("COALIGN_FRAME_RECORDS", "1") != "0"            # measurement switch: 0 = every frame is copied into the graph's input buffers (rounds 2-4)
 
 FrameResult = Tuple[int, Optional[torch.Tensor], Optional[torch.Tensor]]      # (frame index, pred_box3d [K', 8, 3], scores [K'])
 
@@ -63,34 +64,113 @@ def pad_pillars(processed_lidar: Dict[str, torch.Tensor], multiple: int = 4096) 
             "voxel_num_points": torch.cat([vn, vn.new_ones(pad)])}
 
 
-class _GraphSlot:
-    """One captured frame: static inputs, the graph, the decode buffers it writes."""
+_PILLAR_ARRAYS = ("voxel_features", "voxel_coords", "voxel_num_points")
 
-    def __init__(self):
-        self.graph = None
-        self.inputs: Dict[str, torch.Tensor] = {}
+
+def _points_batch(voxelizer: tuple, pts: torch.Tensor, offsets: List[int], record: List[int], pairwise) -> dict:
+    """Raw points (device) -> the model's batch, pillar count left on the device (PillarVFE's ``voxel_count_dev`` form)."""
+    pre, ego_filter, filter_range = voxelizer
+    voxels, coords, num, counts = ops.voxelize(pts, offsets, pre.voxel_size, pre.lidar_range, pre.max_points_per_voxel, pre.max_voxels,
+                                               ego_filter=ego_filter, filter_range=filter_range)
+    return {"processed_lidar": {"voxel_features": voxels, "voxel_coords": coords, "voxel_num_points": num,
+                                "voxel_count_dev": counts[len(offsets) - 1:], "voxel_cells_unique": True},
+            "record_len": record, "pairwise_t_matrix": pairwise}
+
+
+class _GraphSlot:
+    """One captured frame: the graph, the decode buffers it writes, the canvas it owns.  What the frame READS is the subclass's: a constructor that allocates
+    from the first frame's ``src``, ``stage(src, pose_host)`` (the per-frame host-to-device work) and ``batch(record)`` (what the model is captured on)."""
+    record = affine_view = capacity = None              # fields of single forms that read as "not this form" on every slot
+
+    def __init__(self, weights_sig):
+        self.inputs: Dict[str, torch.Tensor] = {}       # static device buffers the frame is copied into
         self.buf: Optional[ops.DecodeBuffers] = None
-        self.weights_sig = None
+        self.weights_sig = weights_sig
         self.canvas_cache: dict = {}
-        self.offsets: Optional[List[int]] = None        # points mode: first point slot of every cloud in the static input buffer
-        self.count_host: Optional[torch.Tensor] = None
-        self.capacity: Optional[int] = None             # bucket mode: pillar rows of the static input buffers (the frame's count sits in inputs["count"])
         self.replays = 0                                # launches through this slot's sparse canvas since its stamps were last zeroed (ops.SPARSE_TAG_RESET_AFTER)
-        # multi-rank frames (an `exchange` between encoder and tail): `graph` holds the encoder, `tail` the ego tail; the collective runs between the two replays
-        self.tail = None
-        self.feats: Optional[list] = None               # the encoder graph's output maps (the collective's send buffers) and pose matrices
-        self.affine = None
-        self.recv_ptrs: Optional[tuple] = None          # data pointers of the collective's output maps the tail graph was captured on
-        self.rows = None
-        self.tail_record: Optional[List[int]] = None
-        # round 5: the frame is read IN PLACE through a device record (ops.PillarFrameRecord) instead of being copied into `inputs`: `blob` = record words |
-        # normalised pose matrices, filled in the pinned `blob_host` and moved with ONE host-to-device transfer per frame
-        self.record: Optional[ops.PillarFrameRecord] = None
-        self.blob: Optional[torch.Tensor] = None
-        self.blob_host: Optional[torch.Tensor] = None
-        self.proto: Optional[dict] = None               # the capture-time arrays (shapes / dtypes only)
-        self.affine_view: Optional[torch.Tensor] = None # [B, L, L, 2, 3] float64 view of the device blob (host-normalised poses), else None
-        self.affine_host: Optional[np.ndarray] = None
+        # `graph`: the whole frame or, with an `exchange` (multi-rank frames), the encoder, and `tail` the ego tail: the collective runs between the two replays
+        self.graph = self.tail = self.tail_record = None
+        self.feats = self.affine = None                 # the encoder graph's output maps (the collective's send buffers) and pose matrices
+        # the collective's output maps the tail graph was captured on: data pointers, the maps themselves (the tail graph reads them: kept referenced), row table
+        self.recv_ptrs = self.recv_keep = self.rows = None
+
+
+class _PointsSlot(_GraphSlot):
+    """Raw points: the pinned staging buffer is copied into the static ``points`` buffer, the voxeliser runs inside the captured frame."""
+    def __init__(self, weights_sig, src: dict, device, offsets: Sequence[int], voxelizer: tuple):
+        super().__init__(weights_sig)
+        self.offsets, self.voxelizer = list(offsets), voxelizer      # first point slot of every cloud in the static input buffer | _points_batch's settings
+        self.inputs = {name: torch.zeros(t.shape, dtype=t.dtype, device=device) for name, t in src.items()}
+
+    def stage(self, src: dict, pose_host) -> None:
+        for name, t in src.items():
+            self.inputs[name].copy_(t, non_blocking=True)
+
+    def batch(self, record: List[int]) -> dict:
+        return _points_batch(self.voxelizer, self.inputs["points"], self.offsets, record, self.inputs["pairwise_t_matrix"])
+
+
+class _PillarCopySlot(_GraphSlot):
+    """Pillars copied into static buffers: at their exact shape (``capacity`` None), or into ``capacity`` rows with the frame's count on the device."""
+    def __init__(self, weights_sig, src: dict, device, capacity: Optional[int]):
+        super().__init__(weights_sig)
+        self.capacity = capacity
+        for name, t in src.items():
+            rows = t.shape[0] if capacity is None or name == "pairwise_t_matrix" else capacity
+            self.inputs[name] = torch.zeros((rows,) + t.shape[1:], dtype=t.dtype, device=device)
+        if capacity is not None:
+            self.count = torch.zeros(1, dtype=torch.int32, device=device)
+            self.count_host = torch.zeros(1, dtype=torch.int32).pin_memory()      # (a 4-byte copy per frame, not a fill kernel)
+
+    def stage(self, src: dict, pose_host) -> None:
+        for name, t in src.items():
+            dst = self.inputs[name]             # (capacity-sized buffers: the frame's rows only, rows beyond the count are never read)
+            (dst if self.capacity is None else dst[: t.shape[0]]).copy_(t, non_blocking=True)
+        if self.capacity is not None:
+            self.count_host[0] = int(src["voxel_features"].shape[0])
+            self.count.copy_(self.count_host, non_blocking=True)
+
+    def batch(self, record: List[int]) -> dict:
+        pl = {k: self.inputs[k] for k in _PILLAR_ARRAYS}
+        if self.capacity is not None:
+            pl.update(voxel_count_dev=self.count, voxel_cells_unique=False)
+        return {"processed_lidar": pl, "record_len": record, "pairwise_t_matrix": self.inputs["pairwise_t_matrix"]}
+
+
+class _PillarRecordSlot(_GraphSlot):
+    """Round 5: pillars read IN PLACE through a device record (ops.PillarFrameRecord), where they are (the batch stays referenced until its frame has completed):
+    ``blob`` = record words (array pointers | pillar count) | normalised pose matrices, filled in the pinned ``blob_host``, ONE host-to-device transfer per frame."""
+    def __init__(self, weights_sig, src: dict, device, capacity: Optional[int], pose_host: Optional[torch.Tensor], grid: tuple):
+        super().__init__(weights_sig)
+        self.capacity, self.grid = capacity, grid       # rows the captured launch covers when the bucket rule sized it, else None (this frame's rows) | (ny, nx, voxel size)
+        pw = src["pairwise_t_matrix"]
+        n_aff = pw.numel() // 16 * 6 if pose_host is not None else 0
+        self.blob_host = torch.zeros(4 + n_aff, dtype=torch.int64).pin_memory()
+        self.blob = torch.zeros(4 + n_aff, dtype=torch.int64, device=device)
+        self.record = ops.PillarFrameRecord(self.blob[:4], self.blob_host[:4], capacity if capacity is not None else int(src["voxel_features"].shape[0]))
+        self.proto: Optional[dict] = {name: src[name] for name in _PILLAR_ARRAYS}      # the capture-time arrays (shapes / dtypes only)
+        if pose_host is not None:
+            shape = tuple(pw.shape[:-2]) + (2, 3)
+            self.affine_view = self.blob[4:].view(torch.float64).view(shape)      # [B, L, L, 2, 3]: host-normalised poses as the device sees them
+            self.affine_host = self.blob_host[4:].view(torch.float64).numpy().reshape(shape)
+        else:
+            self.inputs["pairwise_t_matrix"] = torch.zeros_like(pw, device=device)
+
+    def stage(self, src: dict, pose_host: Optional[torch.Tensor]) -> None:
+        """(The lane's previous frame has been collected: the pinned words are free.)  Host poses are normalised here (transformation_utils.py:69-91, the device's bits)."""
+        self.record.set(src["voxel_features"], src["voxel_num_points"], src["voxel_coords"])
+        if self.affine_view is not None:
+            assert pose_host is not None, "a slot captured with host poses serves frames that carry them (FramePipeline._slot_key)"
+            normalize_pairwise_np(pose_host.numpy(), *self.grid, out=self.affine_host)
+        else:
+            self.inputs["pairwise_t_matrix"].copy_(src["pairwise_t_matrix"], non_blocking=True)
+        self.blob.copy_(self.blob_host, non_blocking=True)
+
+    def batch(self, record: List[int]) -> dict:
+        b = {"processed_lidar": dict(self.proto, pillar_frame=self.record), "record_len": record, "pairwise_t_matrix": self.inputs.get("pairwise_t_matrix")}
+        if self.affine_view is not None:
+            b["normalized_affine_matrix"] = self.affine_view
+        return b
 
 
 class FramePipeline:
@@ -108,12 +188,11 @@ class FramePipeline:
                  ego_filter: bool = True, filter_range: Optional[Sequence[float]] = None, pillar_buckets: bool = True,
                  streams: Optional[Sequence[torch.cuda.Stream]] = None, queue_depth: int = 1):
         self.model = model
-        self.pillar_buckets = bool(pillar_buckets)               # ragged from-pillars frames share a capacity-sized graph (see _bucket_seen below)
+        self.pillar_buckets = bool(pillar_buckets)               # ragged from-pillars frames share a capacity-sized graph (_slot_key)
         self._sig_tensors: Optional[list] = None                 # cached parameter / buffer list of _weights_signature
         self._sig_age = 0
         self._sd_hook = None                                     # removed again in close(): a hook on the model must not keep every pipeline built on it alive
         if hasattr(model, "register_load_state_dict_post_hook"):
-            import weakref
             me = weakref.ref(self)
 
             def _on_load(*_):
@@ -162,73 +241,45 @@ class FramePipeline:
         self.pp.buffer_sets = max(int(getattr(self.pp, "buffer_sets", 2)), self.result_lag + 2)
         self._slots: List[Dict[tuple, _GraphSlot]] = [dict() for _ in range(self.n_lanes)]
         self.max_graphs_per_lane = 4                              # distinct input shapes kept captured per lane (oldest evicted)
-        # from-pillars frames whose pillar count changes from frame to frame (real data): the first shape a lane sees is captured exactly (a stream
-        # of equal shapes -- the bench pool -- keeps the graph that bakes its count); the SECOND different shape of the same capacity bucket (next
-        # power of two, >= 4096 rows) captures ONE graph with capacity-sized inputs and the count on the device (PillarVFE's voxel_count_dev
-        # form, cells not assumed unique), which then serves every other count of that bucket: ragged streams settle on <= 2 graphs per lane
-        self._bucket_seen: List[Dict[tuple, tuple]] = [dict() for _ in range(self.n_lanes)]
+        self._bucket_seen: List[Dict[tuple, tuple]] = [dict() for _ in range(self.n_lanes)]      # per lane: capacity bucket -> the first key seen in it (_slot_key)
         # frames read in place through a device record (no input copies); switched off for good when the model's route turns out not to take one
         # (an explicit capability of the model class -- ADVICE r05: a model whose forward builds its own batch_dict would drop the record and the captured graph would keep
         #  reading the FIRST frame's arrays; PillarVFE raises FrameRecordUnsupported when a record reaches a route that cannot take it, which switches this off as well)
         self._records_ok = FRAME_RECORDS and bool(getattr(model, "accepts_pillar_frame", False)) and hasattr(model, "pillar_vfe") and hasattr(model, "scatter")
         self.frames_in_place = self.frames_copied = 0             # graph-mode frames read through a device record / copied into the graph's input buffers
         self._host_poses = self._records_ok and bool(getattr(model, "accepts_normalized_affine", False)) and hasattr(model, "voxel_size")
+        self._grid = (model.scatter.ny, model.scatter.nx, float(model.voxel_size[0])) if self._host_poses else None      # what the host normalisation of poses needs, read HERE: a model that declares accepts_normalized_affine has scatter.ny / .nx and voxel_size
         self.graphs_captured = 0
         self._lane_busy: List[Optional[int]] = [None] * self.n_lanes          # frame index whose result still sits in the lane's buffers
-        self._pending: "collections.deque" = collections.deque()              # (index, handle, keep-alive)
+        self._pending: "collections.deque" = collections.deque()              # (index, handle, keep-alive batch, submit time)
         self._count = 0
         self.host_enqueue_s = 0.0
         self.latencies_ms: "collections.deque" = collections.deque(maxlen=65536)      # per collected frame: submit -> detections on the host (bounded: a long-running service)
         # ---- submit_points: the voxeliser in front of the model
         self.preprocessor = preprocessor                          # coalign_amd.preprocess.SpVoxelPreprocessor (grid + voxel limits)
         self.points_per_cloud = int(points_per_cloud)             # slot size of one cloud in the staging buffer (NaN padded)
-        self.ego_filter, self.filter_range = bool(ego_filter), filter_range
+        self._voxelizer = (preprocessor, bool(ego_filter), filter_range)      # _points_batch's settings
         self._staging: List[Dict[int, torch.Tensor]] = [dict() for _ in range(self.n_lanes)]      # per lane: n_clouds -> pinned [n_clouds * slot, 4]
         self._staged: List[Optional[torch.cuda.Event]] = [None] * self.n_lanes
 
     # ------------------------------------------------------------------------------------------------ one frame
     def _eager(self, k: int, batch: dict, record: List[int]) -> PostProcessHandle:
-        model = self.model
         if batch.get("_point_offsets") is not None:
             with ops.timed("stage_h2d+voxelize"):
                 pts = batch["_points_pinned"].to(self.device, non_blocking=True)
-                self._staged[k] = torch.cuda.Event()
-                self._staged[k].record()
-                batch = self._points_batch(pts, batch["_point_offsets"], record, batch["pairwise_t_matrix"].to(self.device, non_blocking=True))
+                self._staged[k] = self.streams[k].record_event()
+                batch = _points_batch(self._voxelizer, pts, batch["_point_offsets"], record, batch["pairwise_t_matrix"].to(self.device, non_blocking=True))
         with ops.timed("stage_encode(pillars+backbone)"):
-            feats, affine = model.encode(batch)
+            feats, affine = self.model.encode(batch)
         rows = None
         if self.exchange is not None:
             with ops.timed("stage_exchange"):
                 feats, rows = self.exchange[k](feats)
         with ops.timed("stage_fuse_and_heads"):
             # (an exchange that gathers agents encoded elsewhere says how many the ego tail sees: AgentGather, bench.py --mode gather)
-            out = model.fuse_and_head(feats, host_ints(batch["tail_record_len"]) if "tail_record_len" in batch else record, affine, rows)
+            out = self.model.fuse_and_head(feats, host_ints(batch["tail_record_len"]) if "tail_record_len" in batch else record, affine, rows)
         with ops.timed("stage_post_process(enqueue)"):
-            return self.pp.post_process_async(self.meta, {"ego": out}, side_stream=POST_PROCESS_SIDE_STREAM)
-
-    def _points_batch(self, pts: torch.Tensor, offsets: List[int], record: List[int], pairwise) -> dict:
-        """Raw points (device) -> the batch the model takes, pillar count left on the device (PillarVFE's ``voxel_count_dev`` form)."""
-        pre = self.preprocessor
-        voxels, coords, num, counts = ops.voxelize(pts, offsets, pre.voxel_size, pre.lidar_range, pre.max_points_per_voxel, pre.max_voxels,
-                                                   ego_filter=self.ego_filter, filter_range=self.filter_range)
-        n_clouds = len(offsets) - 1
-        return {"processed_lidar": {"voxel_features": voxels, "voxel_coords": coords, "voxel_num_points": num,
-                                    "voxel_count_dev": counts[n_clouds:], "voxel_cells_unique": True},
-                "record_len": record, "pairwise_t_matrix": pairwise}
-
-    def _slot_batch(self, slot: _GraphSlot, record: List[int]) -> dict:
-        if slot.offsets is not None:
-            return self._points_batch(slot.inputs["points"], slot.offsets, record, slot.inputs["pairwise_t_matrix"])
-        if slot.record is not None:
-            b = {"processed_lidar": dict(slot.proto, pillar_frame=slot.record), "record_len": record, "pairwise_t_matrix": slot.inputs.get("pairwise_t_matrix")}
-            if slot.affine_view is not None:
-                b["normalized_affine_matrix"] = slot.affine_view
-            return b
-        pl = {k: slot.inputs[k] for k in ("voxel_features", "voxel_coords", "voxel_num_points")}
-        if slot.capacity is not None:                       # capacity-sized arrays, the frame's pillar count on the device
-            pl.update(voxel_count_dev=slot.inputs["count"], voxel_cells_unique=False)
-        return {"processed_lidar": pl, "record_len": record, "pairwise_t_matrix": slot.inputs["pairwise_t_matrix"]}
+            return self.pp.post_process_async(self.meta, {"ego": out}, side_stream=True)
 
     def _with_slot_canvas(self, slot: _GraphSlot, fn):
         """Run ``fn()`` with the encoder's canvas bookkeeping pointed at the slot's own: a graph bakes its launches, the persistent canvas's "rows of the
@@ -238,7 +289,7 @@ class FramePipeline:
         keep = None if vfe is None else (vfe.persistent_canvas, vfe.__dict__.get("_canvas_cache"))
         try:
             if vfe is not None:
-                vfe.persistent_canvas, vfe.__dict__["_canvas_cache"] = GRAPH_PERSISTENT_CANVAS, slot.canvas_cache
+                vfe.persistent_canvas, vfe.__dict__["_canvas_cache"] = True, slot.canvas_cache
             return fn()
         finally:
             if vfe is not None:
@@ -248,21 +299,20 @@ class FramePipeline:
                 else:
                     vfe.__dict__["_canvas_cache"] = keep[1]
 
-    def _frame_body(self, slot: _GraphSlot, record: List[int]) -> None:
-        out = self._with_slot_canvas(slot, lambda: self.model(self._slot_batch(slot, record)))
+    def _post_process(self, slot: _GraphSlot, out: dict) -> None:
         if slot.buf is None:
             slot.buf = self.pp.decode_buffers({"ego": out})
         self.pp.enqueue(self.meta, {"ego": out}, slot.buf)
 
+    def _frame_body(self, slot: _GraphSlot, record: List[int]) -> None:
+        self._post_process(slot, self._with_slot_canvas(slot, lambda: self.model(slot.batch(record))))
+
     def _encode_body(self, slot: _GraphSlot, record: List[int]) -> None:
-        slot.feats, slot.affine = self._with_slot_canvas(slot, lambda: self.model.encode(self._slot_batch(slot, record)))
+        slot.feats, slot.affine = self._with_slot_canvas(slot, lambda: self.model.encode(slot.batch(record)))
         slot.feats = list(slot.feats)
 
     def _tail_body(self, slot: _GraphSlot, feats, rows) -> None:
-        out = self.model.fuse_and_head(list(feats), slot.tail_record, slot.affine, rows)
-        if slot.buf is None:
-            slot.buf = self.pp.decode_buffers({"ego": out})
-        self.pp.enqueue(self.meta, {"ego": out}, slot.buf)
+        self._post_process(slot, self.model.fuse_and_head(list(feats), slot.tail_record, slot.affine, rows))
 
     @staticmethod
     def _quiesce_collectives(stream) -> None:
@@ -275,134 +325,103 @@ class FramePipeline:
         try:
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized() and dist.get_backend() == "nccl":
-                import time
                 time.sleep(0.35)
         except Exception:      # noqa: BLE001  (no process group: nothing polls)
             pass
 
-    def _capture_split(self, k: int, slot: _GraphSlot, record: List[int]) -> None:
-        """Encoder graph | collective (eager, on the lane's stream) | tail graph.  Captured with thread-local error mode: a collective backend's watchdog
-        thread polls events while we capture."""
+    def _capture(self, k: int, slot: _GraphSlot, record: List[int], tail_rec: Optional[tuple]) -> None:
+        """Eager warm-up on the lane (MIOpen find, weight folds, anchors, canvases, buffers, the exchange's receive buffers), then the capture: the whole frame as ONE graph,
+        or, with an ``exchange``, encoder graph | collective (eager, on the lane's stream) | tail graph in thread-local error mode (the collective's watchdog polls events)."""
         stream = self.streams[k]
-        self._encode_body(slot, record)                         # eager warm-up: weight folds, canvases, the exchange's receive buffers
+        if self.exchange is None:
+            self._frame_body(slot, record)
+            stream.synchronize()
+            slot.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(slot.graph, stream=stream):
+                self._frame_body(slot, record)
+            return
+        slot.tail_record = list(record if tail_rec is None else tail_rec)
+        self._encode_body(slot, record)
         feats, rows = self.exchange[k](slot.feats)
         self._tail_body(slot, feats, rows)
         self._quiesce_collectives(stream)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=stream, capture_error_mode="thread_local"):
+        slot.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(slot.graph, stream=stream, capture_error_mode="thread_local"):
             self._encode_body(slot, record)
         feats, rows = self.exchange[k](slot.feats)              # on the capture's output maps: these are the send buffers of every replay
-        slot.recv_ptrs, slot.rows = tuple(f.data_ptr() for f in feats), None if rows is None else list(rows)
+        slot.recv_ptrs, slot.rows, slot.recv_keep = tuple(f.data_ptr() for f in feats), None if rows is None else list(rows), feats
         self._quiesce_collectives(stream)
-        t = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(t, stream=stream, capture_error_mode="thread_local"):
+        slot.tail = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(slot.tail, stream=stream, capture_error_mode="thread_local"):
             self._tail_body(slot, feats, rows)
-        slot.graph, slot.tail = g, t
-        slot._recv_keep = feats                                 # (the tail graph reads these buffers: keep them referenced)
 
-    def _graphed(self, k: int, batch: dict, record: List[int]) -> PostProcessHandle:
-        stream = self.streams[k]
-        offsets = batch.get("_point_offsets")
+    def _slot_key(self, k: int, record: List[int], tail_rec: Optional[tuple], offsets, direct: bool, pose_host: bool, src: dict) -> Tuple[tuple, Optional[int]]:
+        """-> (key of the captured frame that serves this input on lane ``k``, rows of its pillar buffers or None = this frame's own).  Ragged from-pillars frames:
+        the first shape of a capacity bucket (next power of two, >= 4096 rows) is captured exactly (a stream of equal shapes -- the bench pool -- keeps the graph that
+        bakes its count); the SECOND different shape captures ONE graph with capacity-sized inputs and the count on the device (PillarVFE's voxel_count_dev form, cells
+        not assumed unique), which serves every other count of that bucket: <= 2 graphs per lane.  ``pillar_buckets=False``: every shape is captured exactly."""
+        key = (tuple(record), tail_rec, None if offsets is None else tuple(offsets), direct, pose_host) + tuple((tuple(t.shape), str(t.dtype)) for t in src.values())
+        if offsets is not None or not self.pillar_buckets or key in self._slots[k]:
+            return key, None
+        cap = max(4096, 1 << max(int(src["voxel_features"].shape[0]) - 1, 0).bit_length())
+        bkey = (tuple(record), tail_rec, "bucket", cap, direct, pose_host, tuple(src["voxel_features"].shape[1:]), tuple(src["pairwise_t_matrix"].shape))
+        if self._bucket_seen[k].setdefault(bkey, key) != key or bkey in self._slots[k]:      # a second shape of this bucket: the capacity-sized graph from here on
+            return bkey, cap
+        return key, None                                         # first shape of its bucket: exact capture
+
+    def _frame_source(self, batch: dict, offsets) -> Tuple[dict, bool, Optional[torch.Tensor], Callable]:
+        """-> (the frame's inputs, whether the pillar launch reads them in place (a record), host poses to normalise or None, its form's ``(weights_sig, capacity) -> slot``)."""
         if offsets is not None:
             src = {"points": batch["_points_pinned"], "pairwise_t_matrix": batch["pairwise_t_matrix"]}
-        else:
-            pl = batch["processed_lidar"]
-            src = {"voxel_features": pl["voxel_features"], "voxel_coords": pl["voxel_coords"], "voxel_num_points": pl["voxel_num_points"],
-                   "pairwise_t_matrix": batch["pairwise_t_matrix"]}
-        direct = offsets is None and self._records_ok and ops.PillarFrameRecord.admits(src["voxel_features"], src["voxel_num_points"], src["voxel_coords"], self.device)
+            return src, False, None, lambda sig, cap: _PointsSlot(sig, src, self.device, offsets, self._voxelizer)
+        src = dict({name: batch["processed_lidar"][name] for name in _PILLAR_ARRAYS}, pairwise_t_matrix=batch["pairwise_t_matrix"])
+        direct = self._records_ok and ops.PillarFrameRecord.admits(src["voxel_features"], src["voxel_num_points"], src["voxel_coords"], self.device)
         pose_host = batch.get("pairwise_t_matrix_host") if direct and self._host_poses else None
         # (the host copy stands in for the device matrix only when both are the dataset's float64 matrices of one shape: a float32 device matrix normalises to other bits)
         if pose_host is not None and (pose_host.is_cuda or pose_host.dtype != torch.float64 or src["pairwise_t_matrix"].dtype != torch.float64
                                       or tuple(pose_host.shape) != tuple(src["pairwise_t_matrix"].shape)):
             pose_host = None
+        if direct:
+            return src, True, pose_host, lambda sig, cap: _PillarRecordSlot(sig, src, self.device, cap, pose_host, self._grid)
+        return src, False, None, lambda sig, cap: _PillarCopySlot(sig, src, self.device, cap)
+
+    def _graphed(self, k: int, batch: dict, record: List[int]) -> PostProcessHandle:
+        offsets = batch.get("_point_offsets")
+        src, direct, pose_host, new_slot = self._frame_source(batch, offsets)
         # (multi-rank frames: the tail graph bakes the agent grouping the ego sees -- another rank dropping an agent changes it while this rank's record stays the same)
         tail_rec = tuple(host_ints(batch["tail_record_len"])) if (self.exchange is not None and "tail_record_len" in batch) else None
-        key = (tuple(record), tail_rec, None if offsets is None else tuple(offsets), direct, pose_host is not None) + tuple((tuple(t.shape), str(t.dtype)) for t in src.values())
-        slot = self._slots[k].get(key)
-        M = cap = None
-        if offsets is None and slot is None and self.pillar_buckets:
-            M = int(src["voxel_features"].shape[0])
-            cap = max(4096, 1 << max(M - 1, 0).bit_length())
-            bkey = (tuple(record), tail_rec, "bucket", cap, direct, pose_host is not None, tuple(src["voxel_features"].shape[1:]), tuple(src["pairwise_t_matrix"].shape))
-            first = self._bucket_seen[k].setdefault(bkey, key)
-            if bkey in self._slots[k] or first != key:           # a second shape of this bucket: the capacity-sized graph from here on
-                key = bkey
-                slot = self._slots[k].get(key)
-            else:
-                cap = None                                       # first shape of its bucket: exact capture
-        # a graph holds raw pointers to the folded / packed weight images of the moment it was captured: re-capture when any
-        # parameter or buffer of the model has been replaced or written since (load_state_dict, fine-tuning between runs)
+        key, cap = self._slot_key(k, record, tail_rec, offsets, direct, pose_host is not None, src)
+        # a graph holds raw pointers to the folded / packed weight images of its capture: re-capture when any parameter or buffer has been replaced or written since
         sig = self._weights_signature()
-        if slot is not None and slot.weights_sig != sig:
-            self._slots[k].pop(key)
-            slot = None
+        if key in self._slots[k] and self._slots[k][key].weights_sig != sig:
+            del self._slots[k][key]
+        slot = self._slots[k].get(key)
         if slot is None:
-            if len(self._slots[k]) >= self.max_graphs_per_lane:      # bound the memory captured frames hold (one private pool + canvas each)
-                self._slots[k].pop(next(iter(self._slots[k])))
-            slot = _GraphSlot()
-            slot.weights_sig = sig
-            slot.offsets = None if offsets is None else list(offsets)
-            slot.capacity = cap
-            if direct:
-                pw = src["pairwise_t_matrix"]
-                n_aff = pw.numel() // 16 * 6 if pose_host is not None else 0
-                slot.blob_host = torch.zeros(4 + n_aff, dtype=torch.int64).pin_memory()
-                slot.blob = torch.zeros(4 + n_aff, dtype=torch.int64, device=self.device)
-                slot.record = ops.PillarFrameRecord(slot.blob[:4], slot.blob_host[:4], cap if cap is not None else int(src["voxel_features"].shape[0]))
-                slot.proto = {name: src[name] for name in ("voxel_features", "voxel_coords", "voxel_num_points")}
-                if pose_host is not None:
-                    shape = tuple(pw.shape[:-2]) + (2, 3)
-                    slot.affine_view = slot.blob[4:].view(torch.float64).view(shape)
-                    slot.affine_host = slot.blob_host[4:].view(torch.float64).numpy().reshape(shape)
-                else:
-                    slot.inputs["pairwise_t_matrix"] = torch.zeros_like(pw, device=self.device)
-                self._stage_record(slot, src, pose_host)
-            else:
-                for name, t in src.items():
-                    rows = cap if (cap is not None and name != "pairwise_t_matrix") else t.shape[0]
-                    slot.inputs[name] = torch.zeros((rows,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device)
-                    slot.inputs[name][: t.shape[0]].copy_(t, non_blocking=True)
-                if cap is not None:
-                    slot.inputs["count"] = torch.full((1,), M, dtype=torch.int32, device=self.device)
-                    slot.count_host = torch.zeros(1, dtype=torch.int32).pin_memory()      # (a 4-byte copy per frame, not a fill kernel)
+            if len(self._slots[k]) >= self.max_graphs_per_lane:      # bound the memory captured frames hold (one private pool + canvas each): the oldest leaves
+                del self._slots[k][next(iter(self._slots[k]))]
+            slot = new_slot(sig, cap)
+            slot.stage(src, pose_host)
             try:
-                if self.exchange is not None:
-                    slot.tail_record = host_ints(batch["tail_record_len"]) if "tail_record_len" in batch else list(record)
-                    self._capture_split(k, slot, record)
-                else:
-                    self._frame_body(slot, record)                  # eager warm-up on the lane: MIOpen find, weight folds, anchors, buffers
-                    stream.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, stream=stream):
-                        self._frame_body(slot, record)
-                    slot.graph = g
+                self._capture(k, slot, record, tail_rec)
             except ops.FrameRecordUnsupported:
                 # (raised by the eager warm-up, before any capture has begun: this model's encoder reads its arrays directly -- copy frames in from now on)
                 self._records_ok = self._host_poses = False
                 return self._graphed(k, batch, record)
+            if direct:
+                slot.proto = None                               # (the capture-time arrays gave shapes and dtypes only: not kept alive for the slot's lifetime)
             self.graphs_captured += 1
-            slot.proto = None                                   # (the capture-time arrays gave shapes and dtypes only: not kept alive for the slot's lifetime)
             self._slots[k][key] = slot                          # only a slot whose capture succeeded is ever looked up again
         self.frames_in_place += slot.record is not None
         self.frames_copied += slot.record is None
-        if slot.record is not None:
-            self._stage_record(slot, src, pose_host)
-        elif slot.capacity is not None:
-            if M is None:
-                M = int(src["voxel_features"].shape[0])
-            for name, t in src.items():
-                slot.inputs[name][: t.shape[0]].copy_(t, non_blocking=True)      # rows beyond the count are never read
-            slot.count_host[0] = M
-            slot.inputs["count"].copy_(slot.count_host, non_blocking=True)
-        else:
-            for name, t in src.items():
-                slot.inputs[name].copy_(t, non_blocking=True)
+        slot.stage(src, pose_host)
         if offsets is not None:
-            self._staged[k] = torch.cuda.Event()
-            self._staged[k].record(stream)                      # the pinned staging buffer may be refilled once this has passed
+            self._staged[k] = self.streams[k].record_event()        # the pinned staging buffer may be refilled once this has passed
+        return self._replay(k, slot)
+
+    def _replay(self, k: int, slot: _GraphSlot) -> PostProcessHandle:
         slot.replays += 1
         if slot.replays >= ops.SPARSE_TAG_RESET_AFTER:          # the 32-bit frame tag of the slot's sparse canvas must not wrap: re-zero the stamp map between replays
-            with torch.cuda.stream(stream):
+            with torch.cuda.stream(self.streams[k]):
                 ops.reset_sparse_canvases(slot.canvas_cache)
             slot.replays = 0
         slot.graph.replay()
@@ -412,23 +431,7 @@ class FramePipeline:
                 raise ops.hip.CoalignHipError("the exchange returned other buffers / another row table than the tail graph was captured on "
                                               "(a wire dtype or a changing schedule): run this pipeline with graph=False")
             slot.tail.replay()
-        done = torch.cuda.Event()
-        done.record(stream)
-        return PostProcessHandle(self.pp, slot.buf, done)
-
-    def _stage_record(self, slot: _GraphSlot, src: dict, pose_host: Optional[torch.Tensor]) -> None:
-        """This frame's record (array pointers | pillar count) and, when the caller kept the dataset's host copy of the pose matrices, their normalised form
-        (transformation_utils.py:69-91 in numpy float64: the device kernel's operations, bit for bit) go to the device as ONE transfer out of pinned memory; the
-        arrays themselves are read where they are (the batch stays referenced until its frame has completed).  The slot's previous frame has been collected
-        before the lane is reused, so the pinned words are free to be rewritten."""
-        slot.record.set(src["voxel_features"], src["voxel_num_points"], src["voxel_coords"])
-        if slot.affine_host is not None:
-            from .pose import normalize_pairwise_np
-            sc = self.model.scatter
-            normalize_pairwise_np(pose_host.numpy(), sc.ny, sc.nx, float(self.model.voxel_size[0]), out=slot.affine_host)
-        else:
-            slot.inputs["pairwise_t_matrix"].copy_(src["pairwise_t_matrix"], non_blocking=True)
-        slot.blob.copy_(slot.blob_host, non_blocking=True)
+        return PostProcessHandle(self.pp, slot.buf, self.streams[k].record_event())
 
     def _weights_signature(self) -> tuple:
         # The tensor list is cached (walking the module tree on every frame cost ~50 us of host time): it is rebuilt after a load_state_dict (hook),
@@ -450,7 +453,6 @@ class FramePipeline:
             raise ValueError("submit_points needs FramePipeline(preprocessor=SpVoxelPreprocessor(...)): grid, max points / voxels")
         if self.exchange is not None:
             raise ValueError("submit_points is the single-GPU feeder path")
-        import time
         t_sub = time.perf_counter()
         clouds = frame["clouds"]
         n, S = len(clouds), self.points_per_cloud
@@ -480,7 +482,6 @@ class FramePipeline:
         IN PLACE by the pillar launch (no input copy), so ``batch['processed_lidar']`` must stay UNMODIFIED until this frame's result has come back -- up to
         ``result_lag`` submits later (the pipeline keeps the tensors referenced; it cannot keep a caller from refilling a preallocated batch).  A caller that
         reuses its input buffers passes ``COALIGN_FRAME_RECORDS=0`` (every frame is copied into the graph's own buffers, as in rounds 2-4) or waits for the result."""
-        import time
         t0 = time.perf_counter()
         t_sub = t0 if _t_submit is None else _t_submit
         idx = self._count
@@ -505,7 +506,6 @@ class FramePipeline:
         return done
 
     def _pop(self) -> FrameResult:
-        import time
         idx, handle, _keep, t_sub = self._pending.popleft()
         boxes, scores = handle.result()
         self.latencies_ms.append((time.perf_counter() - t_sub) * 1e3)
@@ -521,10 +521,7 @@ class FramePipeline:
         return out
 
     def drain(self) -> List[FrameResult]:
-        out = []
-        while self._pending:
-            out.append(self._pop())
-        return out
+        return self._collect_through(self._count)
 
     def run(self, frames: Iterable[dict]) -> List[Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]]:
         """The reference's loop body for every frame of ``frames``; -> [(pred_box3d, scores)] in input order."""
