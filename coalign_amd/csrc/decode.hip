@@ -10,6 +10,11 @@
 //                 passing anchors (a few %) run the full decode.
 // The file is compiled with -ffp-contract=off: every a*b+c below rounds twice, like the op-by-op float32
 // evaluation of the reference.
+// Non-finite values: the reference takes the corner extents with torch.max / torch.min, which propagate NaN, and every
+// comparison with NaN is false -- a candidate with a NaN corner coordinate fails its filters.  fminf / fmaxf return the
+// non-NaN operand instead, so the NaN test is explicit: cand_keep = 0 whenever any projected corner coordinate is NaN (a
+// NaN delta; a size delta above 88.72, where expf overflows and the transform's zeros give 0 * inf).  The row is still
+// written and counted.  Infinite extents need nothing extra: inf - (-inf) = inf and inf - inf = NaN both fail "<= 6".
 #include "common.h"
 
 namespace {
@@ -84,6 +89,7 @@ __device__ void decode_and_store(const DecodeArgs &a, int i, float prob, int pos
         for (int k = 0; k < 12; ++k) T[k] = a.T[k];
     }
     float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY, zmin = INFINITY, zmax = -INFINITY;
+    bool ordered = true;      // no NaN among the 24 projected coordinates
     float *co = a.cand_corners + (size_t)pos * 24;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -98,6 +104,7 @@ __device__ void decode_and_store(const DecodeArgs &a, int i, float prob, int pos
             X = px; Y = py; Z = pz;
         }
         co[3 * k] = X; co[3 * k + 1] = Y; co[3 * k + 2] = Z;
+        ordered = ordered && (X == X) && (Y == Y) && (Z == Z);
         xmin = fminf(xmin, X); xmax = fmaxf(xmax, X);
         ymin = fminf(ymin, Y); ymax = fmaxf(ymax, Y);
         zmin = fminf(zmin, Z); zmax = fmaxf(zmax, Z);
@@ -105,7 +112,7 @@ __device__ void decode_and_store(const DecodeArgs &a, int i, float prob, int pos
     // remove_large_pred_bbx (box_utils.py:840-869, its "z_len" is the y extent used as a truthy mask) and
     // remove_bbx_abnormal_z (:872-890)
     const float x_len = xmax - xmin, y_len = ymax - ymin;
-    const bool keep = (x_len <= 6.f) && (y_len <= 6.f) && (y_len != 0.f) && (zmin >= -3.f) && (zmax <= 1.f);
+    const bool keep = ordered && (x_len <= 6.f) && (y_len <= 6.f) && (y_len != 0.f) && (zmin >= -3.f) && (zmax <= 1.f);
     a.cand_keep[pos] = keep ? 1 : 0;
     a.cand_score[pos] = prob;
     if (a.cand_index) a.cand_index[pos] = i;

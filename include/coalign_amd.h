@@ -160,6 +160,15 @@ int coalign_warp_fuse_nhwc(int n_scales, const float *const *x, const int32_t *C
  * cand_index [capacity] int32 flat anchor index, cand_score [capacity], cand_box7 [capacity, 7] (after the
  * direction fix), cand_corners [capacity, 8, 3] (projected), cand_keep [capacity] uint8 (passes both sanity
  * filters).  status: device uint32, COALIGN_FLAG_* bits are OR-ed in.  Any of cand_index/cand_box7 may be NULL.
+ * Non-finite values: the filters propagate NaN like the reference's torch.max / torch.min do -- cand_keep = 0
+ * whenever any projected corner coordinate is NaN (a NaN delta; a size delta above log(FLT_MAX) = 88.72 under a
+ * transform, where 0 * inf = NaN), and an infinite extent fails the size / z comparisons by itself.  The row is
+ * still written and counted: only cand_keep tells the NMS to leave it out.
+ * Overflow (tested in tests/test_postprocess_limits_gpu.py): when *count_in plus this agent's candidates exceeds
+ * `capacity`, *count_out is clamped to `capacity` and COALIGN_FLAG_CANDIDATE_OVERFLOW is OR-ed into status -- the
+ * flag is sticky, nothing but the frame's clear resets it.  The first capacity - *count_in candidates are written in
+ * order, rows at or beyond `capacity` are never written, and every later agent chained behind a full buffer
+ * (*count_in == capacity) writes nothing and sets the flag again if it has any candidate.
  */
 size_t coalign_anchor_decode_workspace_bytes(int A, int H, int W);
 int coalign_anchor_decode(const float *cls, const float *reg, const float *dir, const float *anchors, int A, int H, int W,

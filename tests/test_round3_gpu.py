@@ -266,7 +266,8 @@ def test_legacy_nms_kernels_in_a_subprocess():
     """COALIGN_NMS_LEGACY=1 selects round 2's rank / mask / reduce kernels (kept for tops above 1024 and as the A/B reference): the NMS tests
     again, in their own process."""
     tests = ["tests/test_hip_parity.py::test_nms_golden", "tests/test_hip_parity.py::test_nms_edge_cases_and_properties",
-             "tests/test_round3_gpu.py::test_fused_nms_gather_equals_the_separate_calls_and_the_oracle"]
+             "tests/test_round3_gpu.py::test_fused_nms_gather_equals_the_separate_calls_and_the_oracle",
+             "tests/test_postprocess_limits_gpu.py::test_nms_on_reused_buffers_and_at_the_range_limit"]
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider"] + tests,
                        env=dict(os.environ, PYTHONPATH=ROOT, COALIGN_NMS_LEGACY="1"), capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-500:])
