@@ -123,6 +123,9 @@ S2_SKIP = os.environ.get("COALIGN_S2_SKIP", "1") != "0"
 HEADS_ONE_LAUNCH = os.environ.get("COALIGN_HEADS_ONE_LAUNCH", "1") != "0"
 # Round 6: the merged cls / reg / dir 1 x 1 heads read the shrink header's map as a SplitMap (coalign_heads_sp); "0": channels-last float32 + the pointwise kernel.
 HEADS_SPLIT_IN = os.environ.get("COALIGN_HEADS_SP", "1") != "0"
+# NaiveCompressor's narrow encoder reads the pillar encoder's SparseCanvas in place (coalign_conv3x3_sp_narrow_sparse, include/coalign_amd_narrow_sparse.h): a
+# compression model keeps the one-launch pillar encoder and its frames go through frame records.  "0": the dense persistent canvas + the kernel's channels-last loader.
+COMPRESS_SPARSE = os.environ.get("COALIGN_COMPRESS_SPARSE", "1") != "0"
 
 
 def split_maps_active(terms: Optional[int] = None) -> bool:
@@ -775,6 +778,11 @@ class NaiveCompressor(nn.Module):
     def takes_split_maps(self, terms: Optional[int] = None) -> bool:
         return bool(FAST_INFERENCE and not self.training and split_maps_active(terms) and self.split_widths() is not None)
 
+    def takes_sparse_canvas(self, terms: Optional[int] = None) -> bool:
+        """The encoder reads an ``ops.SparseCanvas`` directly: the SplitMap route with the narrow encoder (whose sparse form needs two 16-channel intervals)."""
+        on_split = self.takes_split_maps() if terms is None else self.takes_split_maps(terms)
+        return bool(COMPRESS_SPARSE and on_split and self.split_widths()[0] == "narrow" and self.encoder[0].in_channels >= 32)
+
     def _split_images(self):
         """BatchNorm folded, mid padded: (encoder image or pack, its bias, decoder packs and biases), cached until a parameter or buffer changes."""
         c = _cache_of(self, "_coalign_split_cache")
@@ -791,7 +799,7 @@ class NaiveCompressor(nn.Module):
 
     def _forward_split(self, x, out_split: bool):
         kind, cp, enc, be, p1, b1, p2, b2 = self._split_images()
-        if kind == "narrow":                                       # a channels-last canvas is split by the kernel's loader, an NCHW one packed by the op
+        if kind == "narrow":                                       # a channels-last canvas is split by the kernel's loader, an NCHW one packed by the op, a sparse one gathered
             y = ops.conv3x3_sp_narrow(x, enc, be, cp, True)
         else:
             xs = x if isinstance(x, ops.SplitMap) else ops.SplitMap.pack(x)
@@ -802,6 +810,10 @@ class NaiveCompressor(nn.Module):
     def forward(self, x, out_split: bool = False):
         """``out_split``: the caller's next layer reads a SplitMap (the first ResNet block, ``detector.encode``) -- granted on the SplitMap route only; a plain
         ``module(x)`` always gets a tensor (channels-last memory on the SplitMap route)."""
+        if isinstance(x, ops.SparseCanvas):
+            if self.takes_sparse_canvas():
+                return self._forward_split(x, out_split)
+            x = x.dense()                            # (every other route reads a tensor)
         if self.takes_split_maps() and (isinstance(x, ops.SplitMap) or _fast_ok(self, x)):
             return self._forward_split(x, out_split)
         if isinstance(x, ops.SplitMap):

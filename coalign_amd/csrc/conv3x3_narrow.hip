@@ -18,12 +18,18 @@
 //
 // Input kinds: 0 = SplitMap (the patch travels global -> LDS by LDS-DMA, no VALU work in the K loop); 1 = channels-last float32 [N, H, W, Cin] (the dense
 // canvas): the loader fetches 8 channels of a pixel per lane into registers one interval ahead and splits them (sp16_split2: the pairs coalign_sp_pack would
-// have stored, bit for bit) into the other patch buffer behind the interval's matrix steps -- the 360 MB pack pass over the canvas never runs.
+// have stored, bit for bit) into the other patch buffer behind the interval's matrix steps -- the 360 MB pack pass over the canvas never runs;
+// 2 = the SPARSE CANVAS of pillar_sparse.hip (coalign_conv3x3_sp_narrow_sparse, include/coalign_amd_narrow_sparse.h): sp16 feature ROWS [M][Cin / 16][4 planes]
+// [8 x fp16] (coalign_sp_pack_rows) + the 8-byte cell stamps: pixel (n, y, x) = row (stamp & 0xffffffff) if stamp >> 32 == *tag, tag != 0 and row < M_rows,
+// else the zero group -- conv3x3_sp_s2.hip's rule.  The loader is kind 0's with another source address per lane (one 32-bit row offset or -1): the K loop,
+// the LDS layout and the products are the same.  A tile's stamps (one per lane of the ten loading wavefronts) are fetched one interval before the tile's first
+// DMA instruction is issued, which takes two intervals per tile: the entry point refuses Cin < 32 (COALIGN_ERR_UNSUPPORTED), as _s2_sparse does.
 //
 // Weight image (coalign_conv3x3_narrow_weight_bytes): [Cin / 16][9 taps][2 terms][2 channel halves][Cout][8 cin] fp16 + 16 zero bytes + [Cout] float32 2^-k_c
 // + [Cout] float32 2^k_c: the (9b) order with a Cout-wide block in place of 64, i.e. exactly its LDS order -- the weight DMA is a linear copy.
 #include "common.h"
 #include "coalign_amd_narrow.h"
+#include "coalign_amd_narrow_sparse.h"
 
 namespace {
 
@@ -44,7 +50,10 @@ static_assert(kPIns <= kWaves, "one patch piece per wavefront");
 static_assert(kLdsBytes <= 160 * 1024, "does not fit the 160 KB LDS");
 
 struct NarrowArgs {
-    const void *__restrict__ x;         // SplitMap, or channels-last float32
+    const void *__restrict__ x;         // SplitMap, channels-last float32, or sp16 rows
+    const unsigned long long *__restrict__ stamps;      // kind 2 only
+    const int *__restrict__ tag_ptr;
+    unsigned sparse_rows;
     const uint4 *__restrict__ wt;       // weight image
     const uint4 *__restrict__ zero;     // its 16 zero bytes
     const float *__restrict__ bias, *__restrict__ wscale;      // wscale: [Cout] 2^-k_c
@@ -111,11 +120,27 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv3x3_narrow_kernel(co
         const bool ok = pixel_of(t, wave * 64 + lane, gy, gx);
         return ok ? t.n * chunks * 4 * HW + gy * a.W + gx : -1;
     };
+    // ---- input kind 2: the lane's stamp of a tile (cells outside the image read stamp 0: tag 0 is never current) -> the offset of its row, in 16-byte groups
+    const unsigned tag = KIND == 2 ? (unsigned)*a.tag_ptr : 0u;
+    auto load_stamp = [&](const Tile &t) {
+        int gy, gx;
+        unsigned long long s = 0ull;
+        if (wave < kPIns && pixel_of(t, wave * 64 + lane, gy, gx)) s = a.stamps[((size_t)t.n * a.H + gy) * a.W + gx];
+        return s;
+    };
+    auto make_plan_sparse = [&](unsigned long long s) {
+        const unsigned row = (unsigned)s;
+        const bool ok = (unsigned)(s >> 32) == tag && tag != 0u && row < a.sparse_rows;
+        return ok ? (int)(row * (unsigned)(chunks * 4)) : -1;
+    };
     auto issue_patch = [&](int off, int c, int slot) {
         if (wave < kPIns) {
             const uint4 *xs = static_cast<const uint4 *>(a.x);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) dma16(off < 0 ? a.zero : xs + (size_t)off + ((size_t)c * 4 + q) * HW, lds0 + kPatch0 + slot * kBBytes + (q * kPixP + wave * 64) * 16);
+            for (int q = 0; q < 4; ++q) {
+                const uint4 *src = off < 0 ? a.zero : KIND == 2 ? xs + (size_t)off + (c * 4 + q) : xs + (size_t)off + ((size_t)c * 4 + q) * HW;
+                dma16(src, lds0 + kPatch0 + slot * kBBytes + (q * kPixP + wave * 64) * 16);
+            }
         }
     };
     auto issue_weights = [&](int c, int slot) {
@@ -190,6 +215,9 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv3x3_narrow_kernel(co
     if constexpr (KIND == 0) {
         plan = make_plan(cur);
         issue_patch(plan, 0, 0);
+    } else if constexpr (KIND == 2) {
+        plan = make_plan_sparse(load_stamp(cur));
+        issue_patch(plan, 0, 0);
     } else {
         make_stage_plan(cur, st);
         stage_load(st, 0);
@@ -205,22 +233,34 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv3x3_narrow_kernel(co
         floatx16 acc = floatx16{0}, accl = floatx16{0};
         Tile next = cur;
         int ntile = tile;
+        unsigned long long nstamp = 0ull;
         for (int chunk = 0; chunk < chunks; ++chunk, ++L) {
             __builtin_amdgcn_s_waitcnt(0);
             __syncthreads();
             const bool more = L + 1 < n_local;
             int nc = chunk + 1;
+            if constexpr (KIND == 2) {                                 // the next tile's stamps: one interval ahead of its first DMA (chunks >= 2)
+                if (chunk == chunks - 2 && L + 2 < n_local) {
+                    ntile = tile + n_wg;
+                    next = decode(ntile);
+                    nstamp = load_stamp(next);
+                }
+            }
             if (more && nc == chunks) {                                // the next interval opens this workgroup's next tile
                 nc = 0;
-                ntile = tile + n_wg;
-                next = decode(ntile);
-                if constexpr (KIND == 0) plan = make_plan(next);
-                else make_stage_plan(next, st);
+                if constexpr (KIND == 2) {
+                    plan = make_plan_sparse(nstamp);
+                } else {
+                    ntile = tile + n_wg;
+                    next = decode(ntile);
+                    if constexpr (KIND == 0) plan = make_plan(next);
+                    else make_stage_plan(next, st);
+                }
             }
             const int slot_cur = L & 1, slot_next = (L + 1) & 1;
             if (more) {
                 if (!a.stationary) issue_weights(nc, slot_next);
-                if constexpr (KIND == 0) issue_patch(plan, nc, slot_next);
+                if constexpr (KIND != 1) issue_patch(plan, nc, slot_next);
                 else stage_load(st, nc);
             }
             if (wave_live) {
@@ -350,4 +390,34 @@ extern "C" int coalign_conv3x3_sp_narrow(const void *x, int in_kind, const void 
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (Cout == 16) return in_kind == COALIGN_NARROW_IN_SP ? launch_narrow<16, 0>(a, s) : launch_narrow<16, 1>(a, s);
     return in_kind == COALIGN_NARROW_IN_SP ? launch_narrow<32, 0>(a, s) : launch_narrow<32, 1>(a, s);
+}
+
+extern "C" int coalign_conv3x3_sp_narrow_sparse(const void *rows_sp, int M_rows, const void *stamps, const int32_t *state, const void *w_narrow, const float *bias, void *y_sp,
+                                                int N, int Cin, int Cout, int H, int W, int relu, int32_t *range_flag, void *stream) {
+    if (!rows_sp || !stamps || !state || !w_narrow || !bias || !y_sp) return COALIGN_ERR_NULL_POINTER;
+    if (M_rows < 0) return COALIGN_ERR_BAD_SHAPE;
+    int rc = narrow_check(N, Cin, Cout, H, W);
+    if (rc != COALIGN_OK) return rc;
+    if (Cin < 32) return COALIGN_ERR_UNSUPPORTED;                     // (a tile's stamps are fetched one interval ahead: at least two intervals per tile)
+    if ((reinterpret_cast<uintptr_t>(rows_sp) | reinterpret_cast<uintptr_t>(w_narrow) | reinterpret_cast<uintptr_t>(y_sp)) & 15) return COALIGN_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(bias) & 3) return COALIGN_ERR_UNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(stamps) & 7) || (reinterpret_cast<uintptr_t>(state) & 3)) return COALIGN_ERR_UNSUPPORTED;
+    if ((int64_t)M_rows * Cin / 4 >= (int64_t)1 << 31) return COALIGN_ERR_UNSUPPORTED;      // row offsets are 32-bit
+    if (N == 0) return COALIGN_OK;
+    const size_t wbytes = coalign_conv3x3_narrow_weight_bytes(Cin, Cout), tail = (size_t)Cout * 8;
+    const char *wb = static_cast<const char *>(w_narrow);
+    NarrowArgs a{};
+    a.x = rows_sp;
+    a.stamps = static_cast<const unsigned long long *>(stamps);
+    a.tag_ptr = state;
+    a.sparse_rows = (unsigned)M_rows;
+    a.wt = static_cast<const uint4 *>(w_narrow);
+    a.zero = reinterpret_cast<const uint4 *>(wb + wbytes - tail - 16);
+    a.bias = bias;
+    a.wscale = reinterpret_cast<const float *>(wb + wbytes - tail);
+    a.y = static_cast<uint4 *>(y_sp);
+    a.range_flag = range_flag;
+    a.N = N; a.Cin = Cin; a.H = H; a.W = W; a.relu = relu;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return Cout == 16 ? launch_narrow<16, 2>(a, s) : launch_narrow<32, 2>(a, s);
 }

@@ -88,6 +88,14 @@ def sparse_canvas_route(model: nn.Module, terms: Optional[int] = None) -> bool:
                 and first is not None and first.takes_sparse_canvas(terms))
 
 
+def compressor_sparse_route(model: nn.Module, terms: Optional[int] = None) -> bool:
+    """``encode`` has the pillar encoder hand a ``SparseCanvas`` to NaiveCompressor, whose narrow encoder reads it in place; the first block then reads the
+    compressor's ``SplitMap`` as before (``sparse_canvas_route`` stays "the FIRST BLOCK reads the canvas")."""
+    comp = getattr(model, "naive_compressor", None) if getattr(model, "compression", False) else None
+    return bool(SPARSE_CANVAS and _bb.FAST_INFERENCE and isinstance(model, PointPillarBaselineMultiscale) and not model.training
+                and comp is not None and comp.takes_sparse_canvas(terms))
+
+
 def fusion_route(model: nn.Module, channels: Sequence[int]) -> bool:
     """The static half of the one-launch channels-last fusion: plain attention (``feat_dim`` = the map's channels) or max at every scale, and scales the kernel
     takes (<= 3 of 64 / 128 / 256 channels: ``ops.warp_fuse_nhwc_ok`` and ``ops.warp_fuse_nhwc`` are the authority and check every call; this copy serves the plan)."""
@@ -170,7 +178,7 @@ class PointPillarBaselineMultiscale(nn.Module):
         # round 4: the encoder hands a SparseCanvas (one launch, no dense canvas) to a backbone whose first block reads it
         resnet = getattr(self.backbone, "resnet", None)
         keep_sparse = self.pillar_vfe.sparse_canvas
-        self.pillar_vfe.sparse_canvas = sparse_canvas_route(self)
+        self.pillar_vfe.sparse_canvas = sparse_canvas_route(self) or compressor_sparse_route(self)
         try:
             batch_dict = self.scatter(self.pillar_vfe(batch_dict))
         finally:

@@ -110,6 +110,11 @@ NARROW_SIGNATURES = {
     "coalign_conv3x3_sp_narrow": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
 }
 
+# include/coalign_amd_narrow_sparse.h: the third extension header of ABI version 2 (product library): the narrow-output convolution reading the sparse canvas
+NARROW_SPARSE_SIGNATURES = {
+    "coalign_conv3x3_sp_narrow_sparse": (c_int, [P, c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+}
+
 # include/coalign_amd_align.h: the second extension header of ABI version 2 (product library): online pose correction -- stage-1 gather, pose-graph
 # construction, corrected pairwise / affine matrices (csrc/pose_graph_build.hip)
 ALIGN_SIGNATURES = {
@@ -145,7 +150,7 @@ def lib() -> ctypes.CDLL:
             raise CoalignHipError(
                 f"{path} is missing and could not be built ({exc}); the CoAlign hot path has no CPU fallback") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **ALIGN_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES}.items():
         fn = getattr(handle, name)  # AttributeError here == header / library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -169,7 +174,7 @@ def lab_lib() -> ctypes.CDLL:
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(f"{path} is missing and could not be built ({exc})") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **ALIGN_SIGNATURES, **LAB_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **LAB_SIGNATURES}.items():
         fn = getattr(handle, name)
         fn.restype = res
         fn.argtypes = args

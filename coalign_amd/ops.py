@@ -1192,7 +1192,21 @@ def pack_conv3x3_narrow_weight(weight: torch.Tensor) -> torch.Tensor:
 def conv3x3_sp_narrow(x, w_narrow: torch.Tensor, bias: torch.Tensor, cout: int, relu: bool = True) -> "SplitMap":
     """y = act(conv3x3(x, w, stride 1, padding 1) + bias) with 16 or 32 output channels, written as a ``SplitMap`` (include/coalign_amd_narrow.h,
     csrc/conv3x3_narrow.hip: NaiveCompressor's encoder).  ``x``: a SplitMap, or a float32 tensor of logical shape [N, C, H, W] -- read in place when its
-    memory is channels-last (the kernel's loader splits it), packed with ``SplitMap.pack`` first when it is NCHW.  ``w_narrow``: ``pack_conv3x3_narrow_weight``."""
+    memory is channels-last (the kernel's loader splits it), packed with ``SplitMap.pack`` first when it is NCHW -- or a ``SparseCanvas`` (Cin >= 32), whose rows
+    are packed to sp16 rows and gathered through its stamps (include/coalign_amd_narrow_sparse.h): no dense canvas exists.  ``w_narrow``: ``pack_conv3x3_narrow_weight``."""
+    if isinstance(x, SparseCanvas):
+        x.check_current()
+        L = hip.lib()
+        N, Cin, H, W = x.shape
+        _need_gpu(w_narrow, bias)
+        if cout not in NARROW_COUTS or Cin % 16 or w_narrow.numel() != L.coalign_conv3x3_narrow_weight_bytes(Cin, cout):
+            raise ValueError("conv3x3_sp_narrow needs the narrow weight image of (Cin, Cout), Cout 16 or 32, Cin % 16 == 0")
+        rows = sp_pack_rows(x)
+        out = SplitMap.empty(N, cout, H, W, x.device)
+        with _Timed("conv3x3_sp_narrow_sparse"):
+            hip.check(L.coalign_conv3x3_sp_narrow_sparse(_rows_ptr(rows), int(rows.shape[0]), _ptr(x.stamps), _ptr(x.state), _ptr(w_narrow), _ptr(_f32c(bias)), _ptr(out.data),
+                                                         N, Cin, cout, H, W, int(relu), _ptr(sp_range_flag(x.device)), _stream()), "coalign_conv3x3_sp_narrow_sparse")
+        return out
     if isinstance(x, SplitMap):
         kind, xt = NARROW_IN_SP, x.data
         N, Cin, H, W = x.shape

@@ -3,7 +3,7 @@
 The detector picks its kernels per layer at run time; a layer whose shape a hand-written kernel does not take falls back to MIOpen / the per-scale NCHW fusion kernel /
 the fp32 VALU encoder -- correct, slower, and until round 3 silent.  ``plan(hypes)`` builds the model of a hypes dictionary, asks every module the decision function its
 ``forward`` dispatches on (``backbone.conv3x3_route`` / ``pointwise_split``, ``BasicBlock.route``, ``DoubleConv.on_split_maps``, the decode mixin's ``heads_pointwise`` /
-``heads_write_split``, ``NaiveCompressor.split_widths``, ``detector.heads_route`` / ``sparse_canvas_route`` / ``fusion_route``, ``PillarVFE.matrix_core_ok``) with the arithmetic
+``heads_write_split``, ``NaiveCompressor.split_widths``, ``detector.heads_route`` / ``sparse_canvas_route`` / ``compressor_sparse_route`` / ``fusion_route``, ``PillarVFE.matrix_core_ok``) with the arithmetic
 mode passed in, and words the answers -- this module holds no shape rule of its own -- so that a yaml that would leave the fast path shows up in a CPU test
 (tests/test_host_cpu.py walks the reference's ``hypes_yaml/**/pointpillar*.yaml`` with it) instead of in a profile.
 The line of the merged 1x1 heads names the kernel that reads a float32 map (pointwise within its Cin limit, else rocBLAS, listed as a fallback): where a one-layer shrink header
@@ -29,6 +29,7 @@ SP = "conv3x3_sp (SplitMap input: operands by LDS-DMA, fp16 x 2)"
 NARROW = "conv3x3_sp_narrow (16 / 32 output channels, weight-stationary, SplitMap out, fp16 x 2)"
 COMPRESSOR_LIBRARY = MIOPEN + " (compressor: SURVEY 8a row D keeps it on the library)"
 SPLIT_OUT = ", SplitMap out"
+SPARSE_IN = ", sparse canvas in"
 DEFAULT_TERMS = bb.DEFAULT_CONV_EMU_TERMS      # the 2-way fp16 split since round 4
 
 
@@ -76,12 +77,13 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS) -> Dict[str, object]:
         if isinstance(m, bb.NaiveCompressor):
             # the SplitMap route puts the encoder on the narrow kernel or on conv3x3_sp (split_widths), both decoder layers on conv3x3_sp; else the library
             widths = m.split_widths() if m.takes_split_maps(terms) else None
+            sparse_in = SPARSE_IN if detector.compressor_sparse_route(model, terms) else ""
             for cn, c in m.named_modules():
                 if isinstance(c, nn.Conv2d) and widths is None:
                     note(f"{n}.{cn}", COMPRESSOR_LIBRARY, True)
                 elif isinstance(c, nn.Conv2d):
                     pad = f", mid {m.encoder[0].out_channels} zero-padded to {widths[1]}" if widths[1] != m.encoder[0].out_channels else ""
-                    note(f"{n}.{cn}", (NARROW if widths[0] == "narrow" and cn == "encoder.0" else SP) + (pad if cn in ("encoder.0", "decoder.0") else ""), False)
+                    note(f"{n}.{cn}", (NARROW + sparse_in if widths[0] == "narrow" and cn == "encoder.0" else SP) + (pad if cn in ("encoder.0", "decoder.0") else ""), False)
         elif isinstance(m, bb.BasicBlock):
             split = m.route(terms).kind == bb.BLOCK_SPLIT
             note(f"{n}.conv1", SP if split and m.stride == 1 else conv3x3_text(m.conv1, terms) + (SPLIT_OUT if split else ""))
@@ -112,6 +114,8 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS) -> Dict[str, object]:
     else:
         pillar = ("matrix-core encoder (one fp16 matrix instruction per pillar and 32 channels on a 22-bit operand split), ONE launch, sparse canvas read by the first ResNet block"
                   if detector.sparse_canvas_route(model, terms) else
+                  "matrix-core encoder (one fp16 matrix instruction per pillar and 32 channels on a 22-bit operand split), ONE launch, sparse canvas read by the compressor's encoder"
+                  if detector.compressor_sparse_route(model, terms) else
                   "matrix-core encoder (linearised PFN, split-bf16), persistent dense canvas" if bb.emu_active(terms) else "matrix-core encoder, NCHW strip writer")
     fusion = None
     if hasattr(model, "fusion_net"):
