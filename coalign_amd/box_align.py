@@ -266,6 +266,40 @@ class PoseCorrector:
                 "status": store.status, "stats": self.graph.stats}
 
 
+class Aligner:
+    """What ``FramePipeline(aligner=...)`` carries: the stage-1 model (any callable ``data_dict -> head maps``; an ``nn.Module`` in practice), its
+    ``UncertaintyVoxelPostprocessor``, the stage-1 anchors, and what a ``PoseCorrector`` is built from -- a yaml's ``box_align.args``, ``max_cav``, and ``H, W,
+    discrete_ratio, downsample_rate, proj_first`` as ``PoseCorrector`` takes them.  ``corrector(device)`` makes one: every owner of a frame in flight (a captured
+    slot, an eager lane) has its own store, graph arrays and output matrices."""
+
+    def __init__(self, stage1_model, post_processor, anchor_box, box_align_args: Optional[dict], max_cav: int, H: int, W: int, discrete_ratio: float,
+                 downsample_rate: float = 1, proj_first: bool = False):
+        self.stage1_model, self.post_processor = stage1_model, post_processor
+        self.anchor_box = anchor_box if torch.is_tensor(anchor_box) else torch.from_numpy(np.asarray(anchor_box))
+        self.box_align_args = dict(box_align_args or {})
+        self.max_cav, self.H, self.W = int(max_cav), int(H), int(W)
+        self.discrete_ratio, self.downsample_rate, self.proj_first = discrete_ratio, downsample_rate, bool(proj_first)
+        self.uncertainty_dim = int(getattr(stage1_model, "uncertainty_dim", 3))
+
+    def corrector(self, device) -> PoseCorrector:
+        return PoseCorrector(self.box_align_args, self.max_cav, self.H, self.W, self.discrete_ratio, self.downsample_rate, self.proj_first, device=device,
+                             uncertainty_dim=self.uncertainty_dim)
+
+
+def correct_frame_poses(stage1_model, stage1_post_processor, anchor_box, corrector: PoseCorrector, processed_lidar: dict, lidar_poses, record_len=None) -> dict:
+    """The chain of online pose correction, stated once: ``processed_lidar`` (the agent as batch index) + noisy ``lidar_poses`` [N, 6] -> stage-1 forward ->
+    ``post_process_stage1_device`` into the corrector's store -> ``corrector.correct``; returns what ``correct`` returns.  ``record_len`` (host ints) goes to the
+    stage-1 model so that its ``PillarVFE`` does not read the agent count back.  On the current stream; with device poses nothing here synchronises, so
+    ``FramePipeline`` captures it inside its frame, and ``inference_intermediate_fusion_aligned`` calls it eagerly."""
+    data = {"processed_lidar": processed_lidar}
+    if record_len is not None:
+        data["record_len"] = record_len
+    stage1_out = stage1_model(data)
+    store = stage1_post_processor.post_process_stage1_device(stage1_out, anchor_box, corrector.store)
+    poses = torch.as_tensor(lidar_poses).to(device=stage1_out["cls_preds"].device, dtype=torch.float64).contiguous()
+    return corrector.correct(store, poses)
+
+
 def box_alignment_relative_np(pred_corner3d_list, uncertainty_list, lidar_poses, record_len, **kwargs) -> np.ndarray:
     """box_align_v2.py:398-435: the samples of a collated batch, split by ``record_len``.  (The reference ends with
     ``np.cat``, which does not exist; the evident intent -- concatenation along axis 0 -- is what is returned.)"""

@@ -68,7 +68,7 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False, vectori
     flags = [f for f in FLAGS if not (vectorize and f in ("-fno-slp-vectorize", "-fno-vectorize"))]
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(LIB_DIR, exist_ok=True)
-    headers = [os.path.join(INCLUDE, "coalign_amd.h"), os.path.join(INCLUDE, "coalign_amd_lab.h"), os.path.join(INCLUDE, "coalign_amd_narrow.h"), os.path.join(INCLUDE, "coalign_amd_narrow_sparse.h"), os.path.join(INCLUDE, "coalign_amd_align.h"), os.path.join(CSRC, "common.h"), os.path.abspath(__file__)]
+    headers = [os.path.join(INCLUDE, "coalign_amd.h"), os.path.join(INCLUDE, "coalign_amd_lab.h"), os.path.join(INCLUDE, "coalign_amd_narrow.h"), os.path.join(INCLUDE, "coalign_amd_narrow_sparse.h"), os.path.join(INCLUDE, "coalign_amd_align.h"), os.path.join(INCLUDE, "coalign_amd_stage1.h"), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "stage1_internal.h"), os.path.abspath(__file__)]
     hipcc = _hipcc()
 
     def compile_one(src: str) -> str:

@@ -16,6 +16,7 @@
 // NaN delta; a size delta above 88.72, where expf overflows and the transform's zeros give 0 * inf).  The row is still
 // written and counted.  Infinite extents need nothing extra: inf - (-inf) = inf and inf - inf = NaN both fail "<= 6".
 #include "common.h"
+#include "stage1_internal.h"
 
 namespace {
 
@@ -122,10 +123,9 @@ __device__ void decode_and_store(const DecodeArgs &a, int i, float prob, int pos
     }
 }
 
-__global__ __launch_bounds__(kBlock) void count_kernel(DecodeArgs a) {
+// One block's share of the count pass: thread -> anchor `i` of the head maps in `a` (i >= a.total: none), the block's popcount to *out.
+__device__ __forceinline__ void count_block(const DecodeArgs &a, int i, int *out) {
     __shared__ int wave_cnt[kBlock / 64];
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (blockIdx.x == 0 && (int)threadIdx.x < a.n_clear) a.clear[threadIdx.x] = 0u;      // (nothing of this launch reads them; emit_kernel, the next launch, does)
     float p;
     const bool ok = i < a.total && passes(a, i, p);
     const unsigned long long m = __ballot(ok);
@@ -134,21 +134,21 @@ __global__ __launch_bounds__(kBlock) void count_kernel(DecodeArgs a) {
     if (threadIdx.x == 0) {
         int s = 0;
         for (int w = 0; w < kBlock / 64; ++w) s += wave_cnt[w];
-        a.block_counts[blockIdx.x] = s;
+        *out = s;
     }
 }
 
-__global__ __launch_bounds__(kBlock) void emit_kernel(DecodeArgs a) {
+// Candidates emitted by the blocks in front of this one (`before`) and by all `nblocks` blocks (`all`), to every thread of the block.
+__device__ __forceinline__ void block_prefix(const int *block_counts, int nblocks, int self, int &before_out, int &all_out) {
     __shared__ int wave_cnt[kBlock / 64];
     __shared__ int red[kBlock / 64];
     __shared__ int s_before, s_all;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    // candidates emitted by earlier blocks (and, in the last block, by everybody: the new total)
     int before = 0, all = 0;
-    for (int bq = threadIdx.x; bq < (int)gridDim.x; bq += kBlock) {
-        const int c = a.block_counts[bq];
+    for (int bq = threadIdx.x; bq < nblocks; bq += kBlock) {
+        const int c = block_counts[bq];
         all += c;
-        if (bq < (int)blockIdx.x) before += c;
+        if (bq < self) before += c;
     }
     for (int o = 32; o > 0; o >>= 1) { before += __shfl_xor(before, o); all += __shfl_xor(all, o); }
     if (lane == 0) { wave_cnt[wv] = before; red[wv] = all; }
@@ -159,16 +159,13 @@ __global__ __launch_bounds__(kBlock) void emit_kernel(DecodeArgs a) {
         s_before = sb; s_all = sa;
     }
     __syncthreads();
-    const int start = a.count_in ? *a.count_in : 0;
-    const int base = start + s_before;
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-        const long tot = (long)start + s_all;
-        *a.count_out = (int)(tot < a.capacity ? tot : a.capacity);
-        if (tot > a.capacity && a.status) atomicOr(a.status, COALIGN_FLAG_CANDIDATE_OVERFLOW);
-    }
-    __syncthreads();
+    before_out = s_before; all_out = s_all;
+}
 
-    const int i = blockIdx.x * kBlock + threadIdx.x;
+// One block's share of the emit pass: the same predicate as count_block, the passing anchors decoded to rows base, base + 1, ... in thread order.
+__device__ __forceinline__ void emit_block(const DecodeArgs &a, int i, int base) {
+    __shared__ int wave_cnt[kBlock / 64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     float p = 0.f;
     const bool ok = i < a.total && passes(a, i, p);
     const unsigned long long m = __ballot(ok);
@@ -179,7 +176,89 @@ __global__ __launch_bounds__(kBlock) void emit_kernel(DecodeArgs a) {
     if (ok && pos < a.capacity) decode_and_store(a, i, p, pos);
 }
 
+__global__ __launch_bounds__(kBlock) void count_kernel(DecodeArgs a) {
+    if (blockIdx.x == 0 && (int)threadIdx.x < a.n_clear) a.clear[threadIdx.x] = 0u;      // (nothing of this launch reads them; emit_kernel, the next launch, does)
+    count_block(a, blockIdx.x * kBlock + threadIdx.x, a.block_counts + blockIdx.x);
+}
+
+__global__ __launch_bounds__(kBlock) void emit_kernel(DecodeArgs a) {
+    // candidates emitted by earlier blocks (and, in the last block, by everybody: the new total)
+    int before, all;
+    block_prefix(a.block_counts, (int)gridDim.x, (int)blockIdx.x, before, all);
+    const int start = a.count_in ? *a.count_in : 0;
+    const int base = start + before;
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+        const long tot = (long)start + all;
+        *a.count_out = (int)(tot < a.capacity ? tot : a.capacity);
+        if (tot > a.capacity && a.status) atomicOr(a.status, COALIGN_FLAG_CANDIDATE_OVERFLOW);
+    }
+    __syncthreads();
+    emit_block(a, blockIdx.x * kBlock + threadIdx.x, base);
+}
+
+// ---- stage 1 of ALL agents in one pass (include/coalign_amd_stage1.h): the two kernels above with an agent dimension.  Agent g owns the `bpa` consecutive blocks
+// g * bpa ..: no block straddles two agents, and the chained block offsets make agent g's candidates ONE contiguous segment [seg_start[g], seg_start[g + 1]) of
+// the candidate buffer, in the agent's own (h, w, anchor) order -- row for row what a decode call on that agent alone leaves at rows 0 ...
+struct SegArgs {
+    int n_agents, bpa;
+    size_t cls_stride, reg_stride, dir_stride;      // floats between two agents' head maps
+    int *seg_start;                                 // [n_agents + 1]
+};
+
+__device__ __forceinline__ DecodeArgs agent_args(DecodeArgs a, const SegArgs &s, int agent) {
+    a.cls += (size_t)agent * s.cls_stride;
+    a.reg += (size_t)agent * s.reg_stride;
+    if (a.dir) a.dir += (size_t)agent * s.dir_stride;
+    return a;
+}
+
+__global__ __launch_bounds__(kBlock) void count_seg_kernel(DecodeArgs a, SegArgs s) {
+    const int agent = blockIdx.x / s.bpa, lb = blockIdx.x - agent * s.bpa;
+    if (blockIdx.x == 0 && (int)threadIdx.x < a.n_clear) a.clear[threadIdx.x] = 0u;      // the store's status word (the last launch of the pass ORs into it)
+    count_block(agent_args(a, s, agent), lb * kBlock + threadIdx.x, a.block_counts + blockIdx.x);
+}
+
+__global__ __launch_bounds__(kBlock) void emit_seg_kernel(DecodeArgs a, SegArgs s) {
+    const int agent = blockIdx.x / s.bpa, lb = blockIdx.x - agent * s.bpa;
+    int before, all;
+    block_prefix(a.block_counts, (int)gridDim.x, (int)blockIdx.x, before, all);
+    if (threadIdx.x == 0) {
+        if (lb == 0) s.seg_start[agent] = before;
+        if (blockIdx.x == gridDim.x - 1) s.seg_start[s.n_agents] = all;
+    }
+    emit_block(agent_args(a, s, agent), lb * kBlock + threadIdx.x, before);
+}
+
 }  // namespace
+
+size_t coalign::stage1_decode_blocks(int n_agents, int A, int H, int W) {
+    return (size_t)n_agents * (((size_t)A * H * W + kBlock - 1) / kBlock);
+}
+
+int coalign::stage1_decode_segments(const float *cls, const float *reg, const float *dir, const float *anchors, size_t cls_stride, size_t reg_stride, size_t dir_stride,
+                           int n_agents, int A, int H, int W, int num_bins,
+                                    float score_thr, float dir_offset, int order_hwl, int32_t *block_counts, int32_t *seg_start, int32_t *cand_index,
+                                    float *cand_score, float *cand_corners, uint8_t *cand_keep, uint32_t *clear_word, hipStream_t stream) {
+    DecodeArgs a;
+    a.cls = cls; a.reg = reg; a.dir = dir; a.anchors = anchors; a.T = nullptr;
+    a.A = A; a.HW = H * W; a.nb = num_bins; a.total = A * H * W; a.hwl = order_hwl; a.capacity = n_agents * a.total;
+    a.thr = score_thr; a.dir_offset = dir_offset;
+    a.count_in = nullptr; a.count_out = nullptr; a.cand_index = cand_index; a.cand_score = cand_score;
+    a.cand_box7 = nullptr; a.cand_corners = cand_corners; a.cand_keep = cand_keep; a.status = nullptr;
+    a.block_counts = block_counts;
+    a.clear = clear_word;
+    a.n_clear = 1;
+    SegArgs s;
+    s.n_agents = n_agents; s.bpa = (a.total + kBlock - 1) / kBlock;
+    s.cls_stride = cls_stride; s.reg_stride = reg_stride; s.dir_stride = dir_stride;
+    s.seg_start = seg_start;
+    const int blocks = n_agents * s.bpa;
+    hipLaunchKernelGGL(count_seg_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, s);
+    int rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(emit_seg_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, s);
+    return check_launch();
+}
 
 extern "C" {
 

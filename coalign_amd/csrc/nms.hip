@@ -19,6 +19,8 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "coalign_amd_stage1.h"
+#include "stage1_internal.h"
 
 namespace {
 
@@ -238,12 +240,12 @@ __device__ __forceinline__ int row16_sum(int v) {
     return v;
 }
 
-__global__ __launch_bounds__(256) void rank16_kernel(const float *__restrict__ scores, const uint8_t *__restrict__ valid, int Kcap, const int *K_dev,
-                                                     int top, int *__restrict__ order, int *__restrict__ n_sorted) {
+// (`bx`: the block's index along the candidates; the kernels below add what is theirs -- the live count, and with an agent dimension the agent's segment)
+__device__ __forceinline__ void rank16_block(const float *__restrict__ scores, const uint8_t *__restrict__ valid, int K, int top, int *__restrict__ order,
+                                             int *__restrict__ n_sorted, int bx) {
     __shared__ float tile[256];
-    const int K = live_k(K_dev, Kcap);
-    const int i0 = blockIdx.x * 16;
-    if (i0 >= K && blockIdx.x != 0) return;
+    const int i0 = bx * 16;
+    if (i0 >= K && bx != 0) return;
     const int sub = threadIdx.x & 15, i = i0 + (threadIdx.x >> 4);
     const float nanv = __builtin_nanf("");
     float si = nanv;
@@ -267,7 +269,12 @@ __global__ __launch_bounds__(256) void rank16_kernel(const float *__restrict__ s
     rank = row16_sum(rank);
     nvalid = row16_sum(nvalid);
     if (sub == 0 && vi && rank < top) order[rank] = i;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *n_sorted = nvalid < top ? nvalid : top;
+    if (bx == 0 && threadIdx.x == 0) *n_sorted = nvalid < top ? nvalid : top;
+}
+
+__global__ __launch_bounds__(256) void rank16_kernel(const float *__restrict__ scores, const uint8_t *__restrict__ valid, int Kcap, const int *K_dev,
+                                                     int top, int *__restrict__ order, int *__restrict__ n_sorted) {
+    rank16_block(scores, valid, live_k(K_dev, Kcap), top, order, n_sorted, blockIdx.x);
 }
 
 constexpr int kM2 = 256;          // threads of a mask2 workgroup
@@ -320,9 +327,8 @@ __device__ __forceinline__ double quad_iou_l(const P2 *a, double area_a, const P
     return inter / uni;
 }
 
-__global__ __launch_bounds__(kM2) void mask2_kernel(const float *__restrict__ boxes, int rows, int cols, const int *__restrict__ order,
-                                                    const int *__restrict__ n_sorted, float thr, int nb, unsigned long long *__restrict__ mask) {
-    const int cb = blockIdx.x, rb = blockIdx.y;
+__device__ __forceinline__ void mask2_tile(const float *__restrict__ boxes, int rows, int cols, const int *__restrict__ order, const int *__restrict__ n_sorted,
+                                           float thr, int nb, unsigned long long *__restrict__ mask, int cb, int rb) {
     if (cb < rb) return;
     const int n = *n_sorted;
     if (rb * 64 >= n || cb * 64 >= n) return;
@@ -393,6 +399,11 @@ __global__ __launch_bounds__(kM2) void mask2_kernel(const float *__restrict__ bo
     }
 }
 
+__global__ __launch_bounds__(kM2) void mask2_kernel(const float *__restrict__ boxes, int rows, int cols, const int *__restrict__ order,
+                                                    const int *__restrict__ n_sorted, float thr, int nb, unsigned long long *__restrict__ mask) {
+    mask2_tile(boxes, rows, cols, order, n_sorted, thr, nb, mask, blockIdx.x, blockIdx.y);
+}
+
 __device__ __forceinline__ unsigned long long wave_or64(unsigned long long v) {
     unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
 #pragma unroll
@@ -405,15 +416,12 @@ __device__ __forceinline__ unsigned long long wave_or64(unsigned long long v) {
 
 constexpr int kR2Rows = 1024, kR2Words = 16;      // reduce2: top <= 1024
 
-__global__ __launch_bounds__(1024) void reduce2_kernel(const unsigned long long *__restrict__ mask, const int *__restrict__ order,
-                                                       const int *__restrict__ n_sorted, int nb, int *__restrict__ keep, int *__restrict__ keep_count,
-                                                       int do_gather, const float *__restrict__ corners, int box_floats, const float *__restrict__ scores,
-                                                       double x0, double y0, double z0, double x1, double y1, double z1,
-                                                       float *__restrict__ out_corners, float *__restrict__ out_scores, int *__restrict__ out_count) {
+// The greedy walk of one NMS problem by one 1024-thread workgroup -> the number of kept boxes; `kept` = their indices in pick order (LDS, valid after the return).
+__device__ __forceinline__ int reduce2_walk(const unsigned long long *__restrict__ mask, const int *__restrict__ order, const int *__restrict__ n_sorted, int nb,
+                                            const int *&kept) {
     __shared__ unsigned long long rows[kR2Rows * kR2Words];
     __shared__ unsigned long long kbs[kR2Words];
     __shared__ int ord[kR2Rows], keep_l[kR2Rows];
-    __shared__ int wcnt[16];
     __shared__ int s_total;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int n = *n_sorted;
@@ -447,10 +455,23 @@ __global__ __launch_bounds__(1024) void reduce2_kernel(const unsigned long long 
             if (lane == 0) kbs[b] = keepbits;
             coalign::wave_lds_sync();
         }
-        if (lane == 0) { s_total = cnt; *keep_count = cnt; }
+        if (lane == 0) s_total = cnt;
     }
     __syncthreads();
-    const int total = s_total;
+    kept = keep_l;
+    return s_total;
+}
+
+__global__ __launch_bounds__(1024) void reduce2_kernel(const unsigned long long *__restrict__ mask, const int *__restrict__ order,
+                                                       const int *__restrict__ n_sorted, int nb, int *__restrict__ keep, int *__restrict__ keep_count,
+                                                       int do_gather, const float *__restrict__ corners, int box_floats, const float *__restrict__ scores,
+                                                       double x0, double y0, double z0, double x1, double y1, double z1,
+                                                       float *__restrict__ out_corners, float *__restrict__ out_scores, int *__restrict__ out_count) {
+    __shared__ int wcnt[16];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int *keep_l;
+    const int total = reduce2_walk(mask, order, n_sorted, nb, keep_l);
+    if (tid == 0) *keep_count = total;
     if (tid < total) keep[tid] = keep_l[tid];
     if (!do_gather) return;
     // ---- in-range gather (gather_kernel's rule: all 8 corners inside the range, float64 compare), order preserving
@@ -479,6 +500,75 @@ __global__ __launch_bounds__(1024) void reduce2_kernel(const unsigned long long 
     }
     if (tid == 0) *out_count = tot;
     (void)box_floats;
+}
+
+// ------------------------------------------------------------------------------------------------ stage 1 of all agents in one pass
+// include/coalign_amd_stage1.h: the three kernels above with an agent dimension in the grid.  Agent g's candidates are rows seg_start[g] .. seg_start[g + 1] of the
+// candidate arrays (csrc/decode.hip: emit_seg_kernel); its order list, sorted count and bitmask are slices g of the workspace arrays.  Indices in `order` and in
+// the walk's list are relative to the agent's segment, as they are relative to row 0 when the per-agent entry points run one agent at a time.
+struct Stage1Nms {
+    const int *seg_start;             // [n_agents + 1]
+    const float *cand_corners, *cand_score;
+    const int *cand_index;
+    int *order, *n_sorted;            // [n_agents][top], [n_agents]
+    unsigned long long *mask;         // [n_agents][top * nb]
+    int top, nb, kcap;
+    float thr;
+    // the tail of the last launch: the store (include/coalign_amd_align.h)
+    const float *unc;                 // [n_agents][A * udim][HW], unc_stride floats between two agents
+    size_t unc_stride;
+    int A, HW, udim;
+    float *store_corners, *store_unc;
+    int *store_count, *status;
+};
+
+__device__ __forceinline__ int seg_count(const Stage1Nms &s, int agent, int &start) {
+    start = s.seg_start[agent];
+    const int k = s.seg_start[agent + 1] - start;
+    return k < 0 ? 0 : (k < s.kcap ? k : s.kcap);
+}
+
+__global__ __launch_bounds__(256) void stage1_rank_kernel(const Stage1Nms s) {
+    const int agent = blockIdx.y;
+    int start;
+    const int K = seg_count(s, agent, start);
+    rank16_block(s.cand_score + start, nullptr, K, s.top, s.order + (size_t)agent * s.top, s.n_sorted + agent, blockIdx.x);
+}
+
+__global__ __launch_bounds__(kM2) void stage1_mask_kernel(const Stage1Nms s) {
+    const int agent = blockIdx.z;
+    mask2_tile(s.cand_corners + (size_t)s.seg_start[agent] * 24, 8, 3, s.order + (size_t)agent * s.top, s.n_sorted + agent, s.thr, s.nb,
+               s.mask + (size_t)agent * s.top * s.nb, blockIdx.x, blockIdx.y);
+}
+
+// One workgroup per agent: the walk, then slot `agent` of the store written from the LDS list -- what stage1_gather_kernel (csrc/pose_graph_build.hip) copies
+// from a keep list in memory: the first min(kept, C) boxes in pick order with the raw unc_preds of their anchors, the slot's count, the overflow bit.
+__global__ __launch_bounds__(1024) void stage1_reduce_kernel(const Stage1Nms s) {
+    const int agent = blockIdx.x, tid = threadIdx.x;
+    const int *keep_l;
+    const int kept = reduce2_walk(s.mask + (size_t)agent * s.top * s.nb, s.order + (size_t)agent * s.top, s.n_sorted + agent, s.nb, keep_l);
+    constexpr int C = COALIGN_ALIGN_STORE_BOXES;
+    const int n = kept > C ? C : kept;
+    const int start = s.seg_start[agent];
+    float *corners = s.store_corners + (size_t)agent * C * 24;
+    for (int e = tid; e < n * 24; e += 1024) {
+        const int k = e / 24;
+        corners[e] = s.cand_corners[(size_t)(start + keep_l[k]) * 24 + (e - k * 24)];
+    }
+    if (s.udim > 0) {                                          // unc_preds.permute(0, 2, 3, 1).view(-1, udim)[mask] of this agent
+        const float *unc = s.unc + (size_t)agent * s.unc_stride;
+        for (int e = tid; e < n * s.udim; e += 1024) {
+            const int k = e / s.udim, d = e - k * s.udim;
+            const int flat = s.cand_index[start + keep_l[k]];      // (h, w, anchor) order
+            float v = 0.f;
+            if (flat >= 0 && flat < s.A * s.HW) v = unc[(size_t)((flat % s.A) * s.udim + d) * s.HW + flat / s.A];
+            s.store_unc[(size_t)agent * C * s.udim + e] = v;
+        }
+    }
+    if (tid == 0) {
+        s.store_count[agent] = n;
+        if (kept > C) atomicOr(s.status, COALIGN_ALIGN_STORE_OVERFLOW);      // (zeroed by the first launch of the pass)
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ gather
@@ -841,6 +931,85 @@ int coalign_nms_rotated_gather(const float *corners, const float *scores, const 
     if (!range6_host) return COALIGN_ERR_NULL_POINTER;
     return nms_rotated_impl(corners, 8, 3, scores, valid, K, K_dev, iou_thr, top, keep, keep_count, workspace, workspace_bytes, range6_host, out_corners,
                             out_scores, out_count, stream);
+}
+
+// ---- stage 1 of all agents in one pass (include/coalign_amd_stage1.h)
+struct Stage1Ws {
+    int32_t *block_counts, *seg_start, *cand_index, *order, *n_sorted;
+    float *cand_score, *cand_corners;
+    uint8_t *cand_keep;
+    unsigned long long *mask;
+    size_t bytes;
+};
+
+static Stage1Ws stage1_carve(void *ws, int n_agents, int A, int H, int W, int top) {
+    using coalign::align_up;
+    const size_t cap = (size_t)n_agents * A * H * W, nb = ((size_t)top + 63) / 64;
+    Stage1Ws w;
+    char *p = (char *)ws;
+    w.mask = (unsigned long long *)p;  p += align_up((size_t)n_agents * top * nb * 8, 256);
+    w.cand_corners = (float *)p;       p += align_up(cap * 24 * sizeof(float), 256);
+    w.cand_score = (float *)p;         p += align_up(cap * sizeof(float), 256);
+    w.cand_index = (int32_t *)p;       p += align_up(cap * sizeof(int32_t), 256);
+    w.cand_keep = (uint8_t *)p;        p += align_up(cap, 256);
+    w.block_counts = (int32_t *)p;     p += align_up(coalign::stage1_decode_blocks(n_agents, A, H, W) * sizeof(int32_t), 256);
+    w.order = (int32_t *)p;            p += align_up((size_t)n_agents * top * sizeof(int32_t), 256);
+    w.seg_start = (int32_t *)p;        p += 256;             // n_agents + 1 <= 9 words
+    w.n_sorted = (int32_t *)p;         p += 256;
+    w.bytes = (size_t)(p - (char *)ws);
+    return w;
+}
+
+static bool stage1_shape_ok(int n_agents, int A, int H, int W, int top) {
+    return n_agents >= 1 && n_agents <= COALIGN_ALIGN_MAX_AGENTS && A > 0 && H > 0 && W > 0 && top > 0 &&
+           (size_t)A * H * W * 7 <= (size_t)INT32_MAX && (size_t)n_agents * A * H * W <= (size_t)INT32_MAX / 24;
+}
+
+size_t coalign_stage1_boxes_workspace_bytes(int n_agents, int A, int H, int W, int top) {
+    if (!stage1_shape_ok(n_agents, A, H, W, top) || top > kR2Rows) return 0;
+    return stage1_carve(nullptr, n_agents, A, H, W, top).bytes;
+}
+
+int coalign_stage1_boxes(const float *cls, const float *reg, const float *dir, const float *unc, const float *anchors, int n_agents, int A, int H, int W,
+                         int num_bins, int udim, float score_thr, float dir_offset, int order_hwl, float iou_thr, int top, float *store_corners, float *store_unc,
+                         int32_t *store_count, int32_t *status, void *workspace, size_t workspace_bytes, void *stream) {
+    const size_t hw = (A > 0 && H > 0 && W > 0) ? (size_t)A * H * W : 0;      // dense maps: agent after agent
+    return coalign_stage1_boxes_strided(cls, reg, dir, unc, hw, hw * 7, hw * (num_bins > 0 ? num_bins : 0), hw * (udim > 0 ? udim : 0), anchors, n_agents, A, H, W,
+                                        num_bins, udim, score_thr, dir_offset, order_hwl, iou_thr, top, store_corners, store_unc, store_count, status, workspace,
+                                        workspace_bytes, stream);
+}
+
+int coalign_stage1_boxes_strided(const float *cls, const float *reg, const float *dir, const float *unc, size_t cls_stride, size_t reg_stride, size_t dir_stride,
+                                 size_t unc_stride, const float *anchors, int n_agents, int A, int H, int W, int num_bins, int udim, float score_thr,
+                                 float dir_offset, int order_hwl, float iou_thr, int top, float *store_corners, float *store_unc, int32_t *store_count,
+                                 int32_t *status, void *workspace, size_t workspace_bytes, void *stream_) {
+    using namespace coalign;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!cls || !reg || !anchors || !store_corners || !store_count || !status || !workspace) return COALIGN_ERR_NULL_POINTER;
+    if (!stage1_shape_ok(n_agents, A, H, W, top) || udim < 0 || udim > 3 || (dir && num_bins <= 0)) return COALIGN_ERR_BAD_SHAPE;
+    if (udim > 0 && (!unc || !store_unc)) return COALIGN_ERR_NULL_POINTER;
+    {   // an agent's maps must not overlap the next agent's
+        const size_t hw = (size_t)A * H * W;
+        if (cls_stride < hw || reg_stride < hw * 7 || (dir && dir_stride < hw * num_bins) || (udim > 0 && unc_stride < hw * udim)) return COALIGN_ERR_BAD_SHAPE;
+    }
+    if (top > kR2Rows) return COALIGN_ERR_UNSUPPORTED;
+    const Stage1Ws w = stage1_carve(workspace, n_agents, A, H, W, top);
+    if (workspace_bytes < w.bytes) return COALIGN_ERR_WORKSPACE;
+    int rc = stage1_decode_segments(cls, reg, dir, anchors, cls_stride, reg_stride, dir_stride, n_agents, A, H, W, num_bins, score_thr, dir_offset, order_hwl, w.block_counts, w.seg_start,
+                                    w.cand_index, w.cand_score, w.cand_corners, w.cand_keep, (uint32_t *)status, stream);
+    if (rc) return rc;
+    Stage1Nms s;
+    s.seg_start = w.seg_start; s.cand_corners = w.cand_corners; s.cand_score = w.cand_score; s.cand_index = w.cand_index;
+    s.order = w.order; s.n_sorted = w.n_sorted; s.mask = w.mask;
+    s.top = top; s.nb = (top + 63) / 64; s.kcap = A * H * W; s.thr = iou_thr;
+    s.unc = unc; s.unc_stride = unc_stride; s.A = A; s.HW = H * W; s.udim = udim;
+    s.store_corners = store_corners; s.store_unc = store_unc; s.store_count = store_count; s.status = status;
+    hipLaunchKernelGGL(stage1_rank_kernel, dim3((s.kcap + 15) / 16, n_agents), dim3(256), 0, stream, s);
+    if ((rc = check_launch())) return rc;
+    hipLaunchKernelGGL(stage1_mask_kernel, dim3(s.nb, s.nb, n_agents), dim3(kM2), 0, stream, s);
+    if ((rc = check_launch())) return rc;
+    hipLaunchKernelGGL(stage1_reduce_kernel, dim3(n_agents), dim3(1024), 0, stream, s);
+    return check_launch();
 }
 
 int coalign_gather_in_range(const float *corners, const float *scores, const int32_t *keep, const int32_t *keep_count,

@@ -124,6 +124,15 @@ ALIGN_SIGNATURES = {
     "coalign_pose_correct_matrices": (c_int, [c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, P, P, P]),
 }
 
+# include/coalign_amd_stage1.h: the fourth extension header of ABI version 2 (product library): stage 1 of all agents in one pass -- decode, rotated NMS and
+# the store gather of every agent in five launches (csrc/decode.hip, csrc/nms.hip)
+STAGE1_SIGNATURES = {
+    "coalign_stage1_boxes_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "coalign_stage1_boxes": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_float, c_int, P, P, P, P, P, c_size_t, P]),
+    "coalign_stage1_boxes_strided": (c_int, [P, P, P, P, c_size_t, c_size_t, c_size_t, c_size_t, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_float,
+                                             c_int, P, P, P, P, P, c_size_t, P]),
+}
+
 _LAB_LIB = None
 
 
@@ -150,7 +159,7 @@ def lib() -> ctypes.CDLL:
             raise CoalignHipError(
                 f"{path} is missing and could not be built ({exc}); the CoAlign hot path has no CPU fallback") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES}.items():
         fn = getattr(handle, name)  # AttributeError here == header / library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -174,7 +183,7 @@ def lab_lib() -> ctypes.CDLL:
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(f"{path} is missing and could not be built ({exc})") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **LAB_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **LAB_SIGNATURES}.items():
         fn = getattr(handle, name)
         fn.restype = res
         fn.argtypes = args

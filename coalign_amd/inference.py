@@ -13,6 +13,7 @@ from typing import Optional
 
 import torch
 
+from .box_align import correct_frame_poses
 from .postprocess import VoxelPostprocessor
 
 
@@ -64,11 +65,8 @@ def inference_intermediate_fusion_aligned(batch_data: dict, model, post_processo
         raise ValueError("pose correction needs the stage-1 model and its post-processor")
     ego = batch_data["ego"]
     with torch.no_grad():
-        stage1_out = stage1_model({"processed_lidar": ego.get("processed_lidar_stage1", ego["processed_lidar"])})
-        anchors = ego.get("anchor_box_stage1", ego["anchor_box"])
-        store = stage1_post_processor.post_process_stage1_device(stage1_out, anchors, corrector.store)
-        poses = torch.as_tensor(ego["lidar_poses"]).to(device=stage1_out["cls_preds"].device, dtype=torch.float64).contiguous()
-        fixed = corrector.correct(store, poses)
+        fixed = correct_frame_poses(stage1_model, stage1_post_processor, ego.get("anchor_box_stage1", ego["anchor_box"]), corrector,
+                                    ego.get("processed_lidar_stage1", ego["processed_lidar"]), ego["lidar_poses"])
         aligned = dict(batch_data, ego=dict(ego, pairwise_t_matrix=fixed["pairwise_t_matrix"], normalized_affine_matrix=fixed["normalized_affine_matrix"]))
         result = inference_intermediate_fusion(aligned, model, post_processor, gt_box_tensor)
     result["lidar_poses_corrected"] = fixed["lidar_poses"]

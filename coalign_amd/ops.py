@@ -854,6 +854,45 @@ def stage1_gather(buf: DecodeBuffers, unc: Optional[torch.Tensor], store: Stage1
                                               _stream()), "coalign_stage1_gather")
 
 
+def stage1_workspace(n_agents: int, A: int, H: int, W: int, top: int, device) -> torch.Tensor:
+    """The workspace ``stage1_boxes`` needs for these head maps (include/coalign_amd_stage1.h (12a)); reused across frames by its owner."""
+    n = int(hip.lib().coalign_stage1_boxes_workspace_bytes(int(n_agents), int(A), int(H), int(W), int(top)))
+    if n == 0:
+        raise ValueError(f"stage1_boxes: no workspace for {n_agents} agents, head maps {A} x {H} x {W}, top {top} (1 .. {ALIGN_MAX_AGENTS} agents, top <= 1024)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+@_device_op
+def stage1_boxes(cls: torch.Tensor, reg: torch.Tensor, dir_: Optional[torch.Tensor], unc: Optional[torch.Tensor], anchors_f32: torch.Tensor, store: Stage1Store,
+                 ws: torch.Tensor, score_thr: float, dir_offset: float, num_bins: int, order: str, iou_thr: float, top: int = 1000) -> None:
+    """Stage 1 of ALL agents in one pass (``coalign_stage1_boxes``): the stage-1 model's head maps ``cls`` [n, A, H, W], ``reg`` [n, 7A, H, W], ``dir_``
+    [n, bins * A, H, W] or None, ``unc`` [n, A * udim, H, W] or None -> slots 0 .. n - 1 of ``store`` and its status word, bit for bit what ``anchor_decode`` +
+    ``nms_rotated_device`` + ``stage1_gather`` leave there agent by agent.  Five launches whatever n is, on the current stream; no host synchronisation."""
+    _need_gpu(cls, reg, dir_, unc, anchors_f32, store.corners, ws)
+    if store.corners.dtype != torch.float32:
+        raise ValueError("stage1_boxes fills a float32 store")
+    if cls.dim() != 4 or reg.dim() != 4:
+        raise ValueError("stage1_boxes takes the head maps of a frame's agents: cls [n, A, H, W], reg [n, 7A, H, W]")
+    def agent_dense(t):      # float32 with every agent's maps dense: read in place, agents t.stride(0) floats apart (channel slices of a merged-heads tensor)
+        if t is None or (t.dtype == torch.float32 and t.dim() == 4 and t.shape[0] >= 1 and t[0].is_contiguous() and (t.shape[0] == 1 or t.stride(0) >= t[0].numel())):
+            return t
+        return _f32c(t)
+    cls_c, reg_c, dir_c, unc_c = agent_dense(cls), agent_dense(reg), agent_dense(dir_), agent_dense(unc)
+    n, A, H, W = cls_c.shape
+    udim = 0 if unc_c is None else unc_c.shape[1] // A
+    if tuple(reg_c.shape) != (n, 7 * A, H, W) or (dir_c is not None and tuple(dir_c.shape) != (n, int(num_bins) * A, H, W)):
+        raise ValueError("stage1_boxes: reg [n, 7A, H, W] and dir [n, num_bins * A, H, W] must match cls [n, A, H, W]")
+    if udim != store.udim or (unc_c is not None and tuple(unc_c.shape) != (n, A * udim, H, W)):
+        raise ValueError("unc must be [n, A * udim, H, W] with the store's udim")
+    if anchors_f32.dtype != torch.float32 or not anchors_f32.is_contiguous() or anchors_f32.numel() != A * H * W * 7:
+        raise ValueError("anchors: contiguous float32 [H * W * A, 7]")
+    stride = lambda t: 0 if t is None else (int(t.stride(0)) if n > 1 else int(t[0].numel()))      # (one agent: its stride is never used and may be anything)
+    hip.check(hip.lib().coalign_stage1_boxes_strided(_ptr(cls_c), _ptr(reg_c), _ptr(dir_c), _ptr(unc_c if udim else None), stride(cls_c), stride(reg_c), stride(dir_c),
+                                                     stride(unc_c), _ptr(anchors_f32), n, A, H, W, int(num_bins), udim, float(score_thr), float(dir_offset),
+                                                     int(order == "hwl"), float(iou_thr), int(top), _ptr(store.corners), _ptr(store.unc), _ptr(store.count),
+                                                     _ptr(store.status), _ptr(ws), ws.numel(), _stream()), "coalign_stage1_boxes_strided")
+
+
 class PoseGraphArrays:
     """The graph arrays of one sample at their fixed capacities (what ``coalign_pose_graph_optimize`` reads for one graph), the solver's workspace and stats."""
 

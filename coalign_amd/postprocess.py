@@ -10,6 +10,7 @@ the final box count.
 from __future__ import annotations
 
 import math
+import weakref
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -281,10 +282,11 @@ class UncertaintyVoxelPostprocessor(VoxelPostprocessor):
         return corners, boxes, uncertainty
 
     def post_process_stage1_device(self, stage1_output_dict: dict, anchor_box, store: "ops.Stage1Store") -> "ops.Stage1Store":
-        """The loop of ``post_process_stage1`` without its read-backs: per agent the same decode and NMS launches, then ONE gather launch
-        (``coalign_stage1_gather``) that copies the kept corners and the raw ``unc_preds`` of the kept anchors into slot ``i`` of the caller-owned ``store``
-        -- bit for bit the lists ``post_process_stage1`` returns, for the first ``store.boxes`` kept boxes of an agent (more: the overflow bit of the store's
-        status word).  Everything on the current stream; no host synchronisation and, once the buffers and anchors exist, no allocation: capturable."""
+        """``post_process_stage1`` without its read-backs and without its loop: ONE pass over all agents (``coalign_stage1_boxes``, include/coalign_amd_stage1.h --
+        count, emit, rank, mask, reduce: five launches whatever the number of agents) that leaves the kept corners and the raw ``unc_preds`` of the kept anchors
+        in slots 0 .. n - 1 of the caller-owned ``store`` -- bit for bit the lists ``post_process_stage1`` returns, for the first ``store.boxes`` kept boxes of an
+        agent (more: the overflow bit of the store's status word).  Everything on the current stream; no host synchronisation and, once the workspace and the
+        anchors exist, no allocation: capturable."""
         cls, reg, unc = stage1_output_dict["cls_preds"], stage1_output_dict["reg_preds"], stage1_output_dict["unc_preds"]
         dirp = stage1_output_dict.get("dir_preds")
         device = cls.device
@@ -292,19 +294,15 @@ class UncertaintyVoxelPostprocessor(VoxelPostprocessor):
         if n_agents > ops.ALIGN_MAX_AGENTS:
             raise ValueError(f"pose correction handles at most {ops.ALIGN_MAX_AGENTS} agents per frame")
         anchors = self._anchors_f32(anchor_box, device)
-        key = ("stage1", str(device), A, H, W)
-        ring = self._buffers.get(key)
-        if ring is None:
-            ring = self._buffers[key] = [ops.DecodeBuffers(A * H * W, A, H, W, NMS_TOP, device)]
-        buf = ring[0]
-        thr = self.params["target_args"]["score_threshold"]
+        # the workspace is kept beside the ("stage1", ...) buffers, one PER STORE: the stores of a pipeline's lanes are filled on different streams at the same time
+        per_store = self._buffers.setdefault(("stage1", "all agents"), weakref.WeakKeyDictionary()).setdefault(store, {})
+        key = (str(device), A, H, W, n_agents)
+        ws = per_store.get(key)
+        if ws is None:
+            ws = per_store[key] = ops.stage1_workspace(n_agents, A, H, W, NMS_TOP, device)
         da = self.params.get("dir_args", {})
-        for i in range(n_agents):
-            ops.anchor_decode(buf, 0, cls[i], reg[i], None if dirp is None else dirp[i], anchors, thr, da.get("dir_offset", 0.0),
-                              da.get("num_bins", 2), self.params["order"], None, clear_frame=True)
-            ops.nms_rotated_device(buf.cand_corners, buf.cand_score, self.params["nms_thresh"], NMS_TOP, valid=None, k_dev=buf.counts[1:2],
-                                   keep=buf.keep, keep_count=buf.keep_count, ws=buf.nms_ws)
-            ops.stage1_gather(buf, unc[i], store, i)
+        ops.stage1_boxes(cls, reg, dirp, unc, anchors, store, ws, self.params["target_args"]["score_threshold"], da.get("dir_offset", 0.0), da.get("num_bins", 2),
+                         self.params["order"], self.params["nms_thresh"], NMS_TOP)
         store.n_agents = n_agents
         return store
 
