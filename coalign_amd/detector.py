@@ -21,7 +21,7 @@ from . import backbone as _bb
 from . import ops
 from .backbone import BaseBEVBackbone, BasicBlock, DownsampleConv, NaiveCompressor, ResNetBEVBackbone, _cache_of, _fast_ok
 from .encoder import PillarVFE, PointPillarScatter, host_ints
-from .fusion import AttFusion, MaxFusion, fuse_multiscale
+from .fusion import AttFusion, DiscoFusion, MaxFusion, fuse_multiscale
 from .pose import normalize_pairwise_tfm
 
 # Round 4: PillarVFE + PointPillarScatter as one launch with a sparse canvas (csrc/pillar_sparse.hip) feeding the first ResNet block directly.
@@ -301,6 +301,65 @@ class PointPillarUncertainty(nn.Module):
         return _run_heads(self, batch_dict["spatial_features_2d"])
 
 
+class PointPillarDiscoNet(nn.Module):
+    """DiscoNet on PointPillars (opencood/models/point_pillar_disconet.py:19-96): pillar encoder, ``BaseBEVBackbone``, shrink header, ONE single-scale
+    ``DiscoFusion`` on the shrunk map, 1 x 1 heads.  Same constructor keys, ``state_dict`` names and outputs (``feature`` / ``cls_preds`` / ``reg_preds`` [/ ``dir_preds``])
+    as the reference; the ``teacher_processed_lidar`` keys, which the reference's forward reads and never uses, are not required.  ``encode`` / ``fuse_and_head`` and
+    the two ``accepts_*`` flags follow ``PointPillarBaselineMultiscale``'s contracts: ``FramePipeline`` and the inference drivers run it unchanged."""
+
+    def __init__(self, args: dict):
+        super().__init__()
+        self.discrete_ratio = args["voxel_size"][0]
+        self.pillar_vfe = PillarVFE(args["pillar_vfe"], num_point_features=4, voxel_size=args["voxel_size"],
+                                    point_cloud_range=args["lidar_range"])
+        self.scatter = PointPillarScatter(args["point_pillar_scatter"])
+        self.backbone = BaseBEVBackbone(args["base_bev_backbone"], 64)
+        self.out_channel = sum(args["base_bev_backbone"]["num_upsample_filter"])
+        self.voxel_size = args["voxel_size"]
+        self.shrink_flag = "shrink_header" in args
+        if self.shrink_flag:
+            self.shrink_conv = DownsampleConv(args["shrink_header"])
+            self.out_channel = args["shrink_header"]["dim"][-1]
+        self.fusion_net = DiscoFusion(self.out_channel)
+        self.cls_head = nn.Conv2d(self.out_channel, args["anchor_number"], kernel_size=1)
+        self.reg_head = nn.Conv2d(self.out_channel, 7 * args["anchor_number"], kernel_size=1)
+        self.use_dir = "dir_args" in args
+        if self.use_dir:
+            self.dir_head = nn.Conv2d(self.out_channel, args["dir_args"]["num_bins"] * args["anchor_number"], kernel_size=1)
+
+    accepts_normalized_affine = True      # encode() takes data_dict['normalized_affine_matrix'] in place of normalising pairwise_t_matrix itself
+    accepts_pillar_frame = True           # encode() hands processed_lidar['pillar_frame'] to PillarVFE (whose dense-canvas route refuses it: FramePipeline then copies frames)
+
+    def encode(self, data_dict: dict):
+        """Per-agent part: pillars -> canvas -> backbone -> shrink header.  Returns ([the agents' maps, channels-last float32 on the SplitMap route], normalised affine)."""
+        batch_dict = self.scatter(self.pillar_vfe(_single_agent_batch(dict(data_dict, record_len=host_ints(data_dict["record_len"])))))
+        spatial_features = batch_dict["spatial_features"]
+        H0, W0 = spatial_features.shape[2:]
+        affine = data_dict.get("normalized_affine_matrix")
+        if affine is None:
+            affine = normalize_pairwise_tfm(data_dict["pairwise_t_matrix"], H0, W0, self.voxel_size[0])
+        feats = self.backbone.get_multiscale_feature(spatial_features)
+        # the up-sampling heads hand a shrink header on the SplitMap route ONE SplitMap; its second convolution (conv3x3_sp) writes the channels-last float32 map
+        # the fusion kernel reads in place
+        want_split = bool(self.shrink_flag and all(getattr(m, "is_cuda", False) for m in feats) and self.shrink_conv.takes_split_maps())
+        x = self.backbone.decode_multiscale_feature(feats, out_split=True) if want_split else self.backbone.decode_multiscale_feature(feats)
+        if self.shrink_flag:
+            x = self.shrink_conv(x)
+        elif isinstance(x, ops.SplitMap):
+            x = x.dense()
+        return [x], affine
+
+    def fuse_and_head(self, feature_list, record_len, affine, rows=None) -> dict:
+        """Ego part: the pixel-weight fusion of the agents' maps, then the heads on the fused map."""
+        fused = self.fusion_net(feature_list[0], record_len, affine, rows=rows)
+        return dict({"feature": fused}, **_run_heads(self, fused))
+
+    def forward(self, data_dict: dict) -> dict:
+        record_len = host_ints(data_dict["record_len"])
+        feats, affine = self.encode(dict(data_dict, record_len=record_len))
+        return self.fuse_and_head(feats, record_len, affine)
+
+
 MODEL_REGISTRY = {
     "point_pillar_baseline_multiscale": PointPillarBaselineMultiscale,
     "point_pillar_coalign": CoAlign,
@@ -308,14 +367,22 @@ MODEL_REGISTRY = {
     "point_pillar_uncertainty": PointPillarUncertainty,
 }
 
+# Comparison baselines: the other collaborative detectors the reference ships in the same framework and CoAlign is measured against under pose noise.  ``build_model``
+# constructs them like any model; they are NOT families of the CoAlign hot path, so ``routes.plan`` -- whose default walk answers "which of the reference's yamls does the
+# CoAlign hot path serve" -- plans them only when asked to (``plan(hypes, baselines=True)``).
+BASELINE_REGISTRY = {
+    "point_pillar_disconet": PointPillarDiscoNet,
+}
+
 
 def build_model(hypes: dict) -> nn.Module:
-    """``train_utils.create_model`` for the hot-path model families (opencood/tools/train_utils.py:113-146):
+    """``train_utils.create_model`` for the hot-path model families and the comparison baselines (opencood/tools/train_utils.py:113-146):
     ``hypes['model']['core_method']`` names the model, ``hypes['model']['args']`` is its constructor argument."""
     name = hypes["model"]["core_method"]
-    if name not in MODEL_REGISTRY:
-        raise KeyError(f"model '{name}' is outside the CoAlign hot path (available: {sorted(MODEL_REGISTRY)})")
-    return MODEL_REGISTRY[name](hypes["model"]["args"])
+    families = {**MODEL_REGISTRY, **BASELINE_REGISTRY}
+    if name not in families:
+        raise KeyError(f"model '{name}' is outside the CoAlign hot path and its baselines (available: {sorted(families)})")
+    return families[name](hypes["model"]["args"])
 
 
 def load_saved_model(saved_path: str, model: nn.Module):

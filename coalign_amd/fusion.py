@@ -1,18 +1,21 @@
 """Multi-agent feature fusion modules (SURVEY §8a rows G, H, H'), host side.
 
 Class / function names and signatures follow opencood/models/fuse_modules/fusion_in_one.py
-(``regroup`` :21-24, ``warp_feature`` :26-45, ``MaxFusion`` :47-89, ``AttFusion`` :91-136) and
-opencood/models/sub_modules/torch_transformation_utils.py (``warp_affine_simple`` :322-331).  They own no
-parameters; all arithmetic is the fused gfx950 kernel ``coalign_warp_fuse``.
+(``regroup`` :21-24, ``warp_feature`` :26-45, ``MaxFusion`` :47-89, ``AttFusion`` :91-136, ``DiscoFusion`` :138-171) and
+opencood/models/sub_modules/torch_transformation_utils.py (``warp_affine_simple`` :322-331).  ``MaxFusion`` / ``AttFusion`` own no
+parameters; all their arithmetic is the fused gfx950 kernel ``coalign_warp_fuse``.  ``DiscoFusion`` owns ``PixelWeightLayer``
+(opencood/models/fuse_modules/disco_fuse.py:76-99) and runs on ``coalign_disco_fuse``.
 """
 from __future__ import annotations
 
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import ops
+from .backbone import _cache_of, fold_bn
 from .encoder import host_ints
 
 
@@ -95,3 +98,93 @@ class AttFusion(nn.Module):
             s = (xx.shape[1] / float(self.feature_dims)) ** 0.25
             return ops.warp_fuse(xx * s, _ego_rows(normalized_affine_matrix, groups), groups, ops.FUSE_ATT, rows=rows) / s
         return ops.warp_fuse(xx, _ego_rows(normalized_affine_matrix, groups), groups, ops.FUSE_ATT, rows=rows)
+
+
+class PixelWeightLayer(nn.Module):
+    """The per-pixel weight MLP of DiscoNet (disco_fuse.py:76-99): 1 x 1 convolutions 2C -> 128 -> 32 -> 8 -> 1, BatchNorm after the first three, ReLU after all four."""
+
+    def __init__(self, channel: int):
+        super().__init__()
+        self.conv1_1 = nn.Conv2d(channel * 2, 128, kernel_size=1, stride=1, padding=0)
+        self.bn1_1 = nn.BatchNorm2d(128)
+        self.conv1_2 = nn.Conv2d(128, 32, kernel_size=1, stride=1, padding=0)
+        self.bn1_2 = nn.BatchNorm2d(32)
+        self.conv1_3 = nn.Conv2d(32, 8, kernel_size=1, stride=1, padding=0)
+        self.bn1_3 = nn.BatchNorm2d(8)
+        self.conv1_4 = nn.Conv2d(8, 1, kernel_size=1, stride=1, padding=0)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x = x.view(-1, x.size(-3), x.size(-2), x.size(-1))
+        x = F.relu(self.bn1_1(self.conv1_1(x)))
+        x = F.relu(self.bn1_2(self.conv1_2(x)))
+        x = F.relu(self.bn1_3(self.conv1_3(x)))
+        return F.relu(self.conv1_4(x))
+
+    def folded(self):
+        """Eval mode: the BatchNorms folded into their convolutions -> [(weight [Cout, Cin, 1, 1], bias)] of the four layers (cached until a tensor changes)."""
+        def build():
+            layers = [fold_bn(c.weight, c.bias, bn) for c, bn in ((self.conv1_1, self.bn1_1), (self.conv1_2, self.bn1_2), (self.conv1_3, self.bn1_3))]
+            return layers + [(self.conv1_4.weight.contiguous(), self.conv1_4.bias.contiguous())]
+        return _cache_of(self).get(self, build)
+
+    def forward_folded(self, x: torch.Tensor) -> torch.Tensor:
+        """``forward`` of eval mode on the folded layers (what the kernel's parameter image is made of)."""
+        x = x.view(-1, x.size(-3), x.size(-2), x.size(-1))
+        for w, b in self.folded():
+            x = F.relu(F.conv2d(x, w, b))
+        return x
+
+    def packed(self) -> Optional[torch.Tensor]:
+        """The parameter image ``ops.disco_fuse`` reads (None: a folded weight outside the fp16 range), cached like ``folded``."""
+        def build():
+            (w1, b1), (w2, b2), (w3, b3), (w4, b4) = self.folded()
+            img = ops.pack_disco_weights(w1, b1, w2, b2, w3, b3, w4, b4)
+            return (img,)
+        return _cache_of(self, "_coalign_disco_image").get(self, build)[0]
+
+
+class DiscoFusion(nn.Module):
+    """DiscoNet's fusion (fusion_in_one.py:138-171): every agent's map warped to the ego, a per-pixel weight from ``PixelWeightLayer([warped | ego])``, softmax over
+    the agents, weighted sum.  On the GPU in eval mode, at a shape ``coalign_disco_fuse`` takes, one launch per frame; everywhere else (CPU, training, other channel
+    counts, more than 8 agents) the reference's operations one by one -- which is also the statement of the semantics."""
+
+    def __init__(self, feature_dims: int):
+        super().__init__()
+        self.pixel_weight_layer = PixelWeightLayer(feature_dims)
+        self.force_torch = False      # measurement / test aid: take the op-by-op route whatever the device
+
+    def kernel_route(self, channels: int, n_agents: int = 1) -> bool:
+        """The static half of the decision (``routes.plan`` asks it): eval mode and a shape the kernel takes.  ``forward`` adds: a CUDA float32 map, packable weights."""
+        return bool(not self.training and not self.force_torch and ops.disco_fuse_shape_ok(channels, n_agents))
+
+    def forward_torch(self, xx: torch.Tensor, record_len, normalized_affine_matrix: torch.Tensor, folded: bool = False) -> torch.Tensor:
+        _, C, H, W = xx.shape
+        out = []
+        for b, x in enumerate(regroup(xx, record_len)):
+            N = x.shape[0]
+            M = normalized_affine_matrix[b, 0, :N]
+            grid = F.affine_grid(M, [N, C, H, W], align_corners=False).to(x)           # warp_affine_simple, torch_transformation_utils.py:322-331
+            neighbor_feature = F.grid_sample(x, grid, align_corners=False)
+            ego_feature = x[0].view(1, C, H, W).expand(N, -1, -1, -1)
+            cat = torch.cat((neighbor_feature, ego_feature), dim=1)
+            agent_weight = self.pixel_weight_layer.forward_folded(cat) if folded else self.pixel_weight_layer(cat)
+            agent_weight = F.softmax(agent_weight, dim=0)
+            out.append(torch.sum(agent_weight.expand(-1, C, -1, -1) * neighbor_feature, dim=0))
+        return torch.stack(out)
+
+    def forward(self, xx: torch.Tensor, record_len, normalized_affine_matrix: torch.Tensor, rows=None) -> torch.Tensor:
+        if rows is not None:
+            raise NotImplementedError("DiscoFusion does not run agent-sharded (rows)")
+        groups = host_ints(record_len)
+        image = None
+        if xx.is_cuda and xx.dtype == torch.float32 and self.kernel_route(xx.shape[1], max(groups)) and sum(groups) == xx.shape[0]:
+            image = self.pixel_weight_layer.packed()
+        if image is None:
+            return self.forward_torch(xx, groups, normalized_affine_matrix)
+        if not xx.is_contiguous(memory_format=torch.channels_last):
+            xx = xx.contiguous(memory_format=torch.channels_last)      # (the shrink header's conv3x3_sp writes channels-last: no copy on the detector's route)
+        outs, off = [], 0
+        for b, n in enumerate(groups):
+            outs.append(ops.disco_fuse(xx[off:off + n], normalized_affine_matrix[b, 0, :n], image))
+            off += n
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)

@@ -133,6 +133,13 @@ STAGE1_SIGNATURES = {
                                              c_int, P, P, P, P, P, c_size_t, P]),
 }
 
+# include/coalign_amd_disco.h: the fifth extension header of ABI version 2 (product library): DiscoNet's pixel-weight fusion -- warp, per-pixel MLP, softmax
+# over agents and weighted sum in one launch (csrc/disco_fuse.hip)
+DISCO_SIGNATURES = {
+    "coalign_disco_param_bytes": (c_size_t, [c_int]),
+    "coalign_disco_fuse": (c_int, [P, c_int, c_int, c_int, c_int, P, P, c_size_t, P, P]),
+}
+
 _LAB_LIB = None
 
 
@@ -159,7 +166,7 @@ def lib() -> ctypes.CDLL:
             raise CoalignHipError(
                 f"{path} is missing and could not be built ({exc}); the CoAlign hot path has no CPU fallback") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES}.items():
         fn = getattr(handle, name)  # AttributeError here == header / library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -183,7 +190,7 @@ def lab_lib() -> ctypes.CDLL:
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(f"{path} is missing and could not be built ({exc})") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **LAB_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **LAB_SIGNATURES}.items():
         fn = getattr(handle, name)
         fn.restype = res
         fn.argtypes = args

@@ -1552,3 +1552,63 @@ def pcdet_nms(boxes_sorted: torch.Tensor, thresh: float, normal: bool = False) -
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=b.device)
     hip.check(L.coalign_pcdet_nms(_ptr(b), n, float(thresh), int(normal), _ptr(keep), _ptr(cnt), _ptr(ws), ws_bytes, _stream()), "coalign_pcdet_nms")
     return keep, cnt
+
+
+# ---- DiscoNet's pixel-weight fusion (include/coalign_amd_disco.h, csrc/disco_fuse.hip) ---------------------------------------------------------------
+DISCO_MAX_CHANNELS = 384
+
+
+def disco_fuse_shape_ok(channels: int, n_agents: int) -> bool:
+    """The shapes ``coalign_disco_fuse`` takes: C % 32 == 0, 32 <= C <= 384, 1 .. 8 agents (any H, W)."""
+    return channels % 32 == 0 and 32 <= channels <= DISCO_MAX_CHANNELS and 1 <= n_agents <= 8
+
+
+def _sp16_pair(w: torch.Tensor):
+    """float32 -> the sp16 pair of csrc/common.h as the host makes it for weights: w~ = w rounded to 22 significant bits, h = fp16(w~) to nearest, l = (w~ - h) * 2^10."""
+    ws = ((w.contiguous().view(torch.int32) + 2) & -4).view(torch.float32)
+    hi = ws.half()
+    return hi, ((ws - hi.float()) * 1024.0).half()
+
+
+def _disco_operand_image(w: torch.Tensor) -> torch.Tensor:
+    """w [R, K] (R % 32 == 0, K % 16 == 0) -> bytes of [K / 16 steps][R / 32 row tiles][64 lanes][8 h | 8 l] fp16, lane (r, half) of a (step, tile) holding
+    w[32 tile + r][16 step + 8 half + j]: the A operand of v_mfma_f32_32x32x16_f16 as one contiguous 32-byte piece per lane."""
+    R, K = w.shape
+
+    def lanes(t):      # [tile, r, step, half, j] -> [step, tile, half, r, j]
+        return t.reshape(R // 32, 32, K // 16, 2, 8).permute(2, 0, 3, 1, 4)
+    hi, lo = _sp16_pair(w)
+    return torch.stack([lanes(hi), lanes(lo)], dim=4).contiguous().view(torch.uint8).reshape(-1)
+
+
+def pack_disco_weights(w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor, w4: torch.Tensor,
+                       b4: torch.Tensor) -> Optional[torch.Tensor]:
+    """The folded PixelWeightLayer (w1 [128, 2C], w2 [32, 128], w3 [8, 32], w4 [8], biases) -> the parameter image of ``coalign_disco_fuse`` (layout: the header's
+    (11a)), a uint8 tensor on the weights' device; None when a weight of the two matrix layers lies outside the fp16 range (its sp16 pair would saturate)."""
+    w1, w2, w3 = w1.detach().float().reshape(128, -1), w2.detach().float().reshape(32, 128), w3.detach().float().reshape(8, 32)
+    C = w1.shape[1] // 2
+    if not disco_fuse_shape_ok(C, 1) or not bool(torch.isfinite(w1).all() and torch.isfinite(w2).all()) or max(float(w1.abs().max()), float(w2.abs().max())) > 65504.0:
+        return None
+    w3p = w3.reshape(8, 4, 2, 4).permute(2, 0, 1, 3).reshape(-1)      # [half][row][q = 4 i + j] <- column 8 i + 4 half + j: the order of a lane's 16 result registers
+    floats = torch.cat([t.detach().float().reshape(-1) for t in (b1, b2, w3p, b3, w4, b4)] + [w1.new_zeros(3)])
+    img = torch.cat([_disco_operand_image(w1[:, :C]), _disco_operand_image(w1[:, C:]), _disco_operand_image(w2), floats.contiguous().view(torch.uint8)])
+    assert img.numel() == 2 * (C // 16) * 8192 + 16384 + 436 * 4
+    return img.contiguous()
+
+
+@_device_op
+def disco_fuse(x: torch.Tensor, theta: torch.Tensor, params: torch.Tensor) -> torch.Tensor:
+    """DiscoFusion of ONE frame in one launch: x [n <= 8, C, H, W] float32 in channels-last memory (agent 0 the ego), theta [n, 2, 3] (row 0 of the frame's
+    normalised affine matrix), params from ``pack_disco_weights`` -> the fused map [1, C, H, W], channels-last."""
+    _need_gpu(x, theta, params)
+    L = hip.lib()
+    n, C, H, W = x.shape
+    if x.dtype != torch.float32 or not x.is_contiguous(memory_format=torch.channels_last) or not disco_fuse_shape_ok(C, n):
+        raise ValueError("disco_fuse needs a channels-last float32 map [1 .. 8 agents, C % 32 == 0 in 32 .. 384, H, W]")
+    th = theta.to(device=x.device, dtype=torch.float64).contiguous()
+    if th.shape[0] != n:
+        raise ValueError("one theta row per agent")
+    out = torch.empty((1, C, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    with _Timed("disco_fuse"):
+        hip.check(L.coalign_disco_fuse(_ptr(x), n, C, H, W, _ptr(th), _ptr(params), params.numel(), _ptr(out), _stream()), "coalign_disco_fuse")
+    return out

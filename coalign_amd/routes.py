@@ -3,13 +3,13 @@
 The detector picks its kernels per layer at run time; a layer whose shape a hand-written kernel does not take falls back to MIOpen / the per-scale NCHW fusion kernel /
 the fp32 VALU encoder -- correct, slower, and until round 3 silent.  ``plan(hypes)`` builds the model of a hypes dictionary, asks every module the decision function its
 ``forward`` dispatches on (``backbone.conv3x3_route`` / ``pointwise_split``, ``BasicBlock.route``, ``DoubleConv.on_split_maps``, the decode mixin's ``heads_pointwise`` /
-``heads_write_split``, ``NaiveCompressor.split_widths``, ``detector.heads_route`` / ``sparse_canvas_route`` / ``compressor_sparse_route`` / ``fusion_route``, ``PillarVFE.matrix_core_ok``) with the arithmetic
+``heads_write_split``, ``NaiveCompressor.split_widths``, ``detector.heads_route`` / ``sparse_canvas_route`` / ``compressor_sparse_route`` / ``fusion_route``, ``DiscoFusion.kernel_route``, ``PillarVFE.matrix_core_ok``) with the arithmetic
 mode passed in, and words the answers -- this module holds no shape rule of its own -- so that a yaml that would leave the fast path shows up in a CPU test
 (tests/test_host_cpu.py walks the reference's ``hypes_yaml/**/pointpillar*.yaml`` with it) instead of in a profile.
 The line of the merged 1x1 heads names the kernel that reads a float32 map (pointwise within its Cin limit, else rocBLAS, listed as a fallback): where a one-layer shrink header
 hands them a SplitMap (``detector.heads_route(model).split_in``) they run on ``heads_sp`` whatever that line says.
 
-    python -m coalign_amd.routes <hypes.yaml> [...]          # prints the plan(s) as JSON
+    python -m coalign_amd.routes [--baselines] <hypes.yaml> [...]          # prints the plan(s) as JSON; --baselines: plan DiscoNet too
 """
 from __future__ import annotations
 
@@ -21,13 +21,16 @@ import torch.nn as nn
 
 from . import backbone as bb
 from . import detector
-from .detector import MODEL_REGISTRY, build_model
+from .detector import BASELINE_REGISTRY, MODEL_REGISTRY, build_model
+from .fusion import DiscoFusion
 
 EMU, F32, MIOPEN, ROCBLAS, POINTWISE = "conv3x3_emu (split 16-bit matrix cores)", "conv3x3 (fp32 matrix cores) / MIOpen by shape", "MIOpen", "rocBLAS (1x1 heads)", "pointwise"
 WINO = "conv3x3_wino (Winograd F(2x2,3x3), split-bf16 matrix cores)"
 SP = "conv3x3_sp (SplitMap input: operands by LDS-DMA, fp16 x 2)"
 NARROW = "conv3x3_sp_narrow (16 / 32 output channels, weight-stationary, SplitMap out, fp16 x 2)"
 COMPRESSOR_LIBRARY = MIOPEN + " (compressor: SURVEY 8a row D keeps it on the library)"
+DISCO = "disco_fuse: warp + pixel-weight MLP + softmax in one launch"
+DISCO_TORCH = "DiscoFusion op by op in PyTorch (channels outside the kernel's C % 32 == 0, 32 .. 384)"
 SPLIT_OUT = ", SplitMap out"
 SPARSE_IN = ", sparse canvas in"
 DEFAULT_TERMS = bb.DEFAULT_CONV_EMU_TERMS      # the 2-way fp16 split since round 4
@@ -55,11 +58,12 @@ def pointwise_text(cin: int, terms: int) -> str:
     return POINTWISE + (" (split-bf16 matrix cores)" if bb.pointwise_split(cin, terms) else " (fp32 matrix cores)")
 
 
-def plan(hypes: dict, terms: int = DEFAULT_TERMS) -> Dict[str, object]:
+def plan(hypes: dict, terms: int = DEFAULT_TERMS, baselines: bool = False) -> Dict[str, object]:
     """-> {"model", "layers": {module name: route}, "pillar", "fusion", "fallbacks": [names of 3x3 / pointwise layers NOT on a hand-written
-    kernel], "outside_hot_path": reason or None}."""
+    kernel], "outside_hot_path": reason or None}.  ``baselines``: also plan the comparison baselines (``detector.BASELINE_REGISTRY``: DiscoNet), which ``build_model``
+    constructs but which are no family of the CoAlign hot path -- without it they are reported as outside it, like every other family."""
     name = hypes["model"]["core_method"]
-    if name not in MODEL_REGISTRY:
+    if name not in MODEL_REGISTRY and not (baselines and name in BASELINE_REGISTRY):
         return {"model": name, "outside_hot_path": f"model family '{name}' is not part of the CoAlign hot path", "layers": {}, "fallbacks": []}
     model = build_model(hypes).eval()                       # (the decision functions answer for the module's mode)
     layers: Dict[str, str] = {}
@@ -94,6 +98,9 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS) -> Dict[str, object]:
             split, c1, c2 = m.on_split_maps(terms), m.double_conv[0], m.double_conv[2]
             note(f"{n}.double_conv.0", SP if split and heads_split and m is first_shrink else conv3x3_text(c1, terms) + (SPLIT_OUT if split else ""))
             note(f"{n}.double_conv.2", SP if split else conv3x3_text(c2, terms))
+        elif isinstance(m, nn.Conv2d) and n.startswith("fusion_net.") and isinstance(model.fusion_net, DiscoFusion):
+            ok = model.fusion_net.kernel_route(model.out_channel)      # the four 1x1 layers of PixelWeightLayer run inside the fusion launch
+            note(n, "disco_fuse (pixel-weight MLP layer inside the fusion launch)" if ok else MIOPEN + " (DiscoFusion op by op)", not ok)
         elif isinstance(m, nn.Conv2d) and n not in layers and "naive_compressor" not in n:
             if tuple(m.kernel_size) == (1, 1) and n.endswith("_head"):
                 ok = detector.heads_route(model, terms).pointwise
@@ -118,7 +125,13 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS) -> Dict[str, object]:
                   if detector.compressor_sparse_route(model, terms) else
                   "matrix-core encoder (linearised PFN, split-bf16), persistent dense canvas" if bb.emu_active(terms) else "matrix-core encoder, NCHW strip writer")
     fusion = None
-    if hasattr(model, "fusion_net"):
+    if isinstance(getattr(model, "fusion_net", None), DiscoFusion):          # ONE single-scale module on the shrunk map, not a ModuleList
+        if model.fusion_net.kernel_route(model.out_channel):
+            fusion = DISCO
+        else:
+            fusion = DISCO_TORCH
+            fallbacks.append("fusion")
+    elif hasattr(model, "fusion_net"):
         dims = [int(d) for d in hypes["model"]["args"]["base_bev_backbone"]["num_filters"]]
         if len(model.fusion_net) != len(dims):
             dims = dims[-len(model.fusion_net):]
@@ -143,9 +156,9 @@ def summary(p: dict) -> dict:
 if __name__ == "__main__":
     from .config import load_yaml
     out = {}
-    for path in sys.argv[1:]:
+    for path in [a for a in sys.argv[1:] if a != "--baselines"]:
         try:
-            out[path] = summary(plan(load_yaml(path)))
+            out[path] = summary(plan(load_yaml(path), baselines="--baselines" in sys.argv[1:]))
         except Exception as e:      # noqa: BLE001  (other model families' yamls need parsers / keys outside the hot path)
             out[path] = {"outside_hot_path": f"{type(e).__name__}: {str(e)[:120]}"}
     print(json.dumps(out, indent=1))

@@ -298,3 +298,36 @@ def make_points_frame(hypes: dict, n_agents: int, seed: int = 303, noise: Option
     clouds = [make_point_cloud(seed * 16 + i, **cloud_kw) for i in range(n_agents)]
     poses = make_poses(rng, n_agents, noise=noise)
     return {"clouds": clouds, "record_len": [n_agents], "pairwise_t_matrix": torch.from_numpy(get_pairwise_transformation(poses, L)[None])}
+
+
+def disco_parameters_(layer: torch.nn.Module, seed: int = 0, input_scale: float = 1.0) -> None:
+    """Test weights for a ``PixelWeightLayer`` (this package's or the reference's: keyed by ``state_dict`` name) that keep the MLP ALIVE.  Freshly initialised, the last
+    ReLU zeroes most logits, the softmax over agents is uniform and a comparison sees none of the four layers.  Here: He-scaled weights (the activation scale
+    survives every layer), positive biases, a non-negative last layer with a gain of 3, BatchNorm statistics away from their defaults, and ``conv1_1`` divided by ``input_scale`` so that maps of that
+    magnitude give logits of order one -- most of them positive, and different between agents."""
+    import zlib
+    sd = layer.state_dict()
+    with torch.no_grad():
+        for name in sorted(sd.keys()):
+            t = sd[name]
+            if not t.is_floating_point():
+                continue
+            g = torch.Generator().manual_seed((zlib.crc32(name.encode()) + seed) & 0x7FFFFFFF)
+            shape = tuple(t.shape)
+            if name.endswith("running_var"):
+                v = torch.rand(shape, generator=g) * 1.5 + 0.5
+            elif name.endswith("running_mean"):
+                v = torch.randn(shape, generator=g) * 0.2
+            elif name.startswith("bn") and name.endswith("bias"):
+                v = torch.rand(shape, generator=g) * 0.4 + 0.1
+            elif name.endswith("bias"):
+                v = torch.rand(shape, generator=g) * 0.2 + 0.1
+            elif t.dim() == 1:                       # BatchNorm scale
+                v = torch.rand(shape, generator=g) * 0.8 + 0.8
+            else:
+                v = torch.randn(shape, generator=g) * (2.0 / t[0].numel()) ** 0.5
+                if name == "conv1_1.weight":
+                    v = v / input_scale
+                if name == "conv1_4.weight":
+                    v = v.abs() * 3.0                    # non-negative on the non-negative last hidden layer: with its positive bias every logit passes the last ReLU
+            t.copy_(v.to(t.dtype))
