@@ -21,7 +21,7 @@ from . import backbone as _bb
 from . import ops
 from .backbone import BaseBEVBackbone, BasicBlock, DownsampleConv, NaiveCompressor, ResNetBEVBackbone, _cache_of, _fast_ok
 from .encoder import PillarVFE, PointPillarScatter, host_ints
-from .fusion import AttFusion, DiscoFusion, MaxFusion, fuse_multiscale
+from .fusion import AttFusion, DiscoFusion, MaxFusion, V2VNetFusion, fuse_multiscale
 from .pose import normalize_pairwise_tfm
 
 # Round 4: PillarVFE + PointPillarScatter as one launch with a sparse canvas (csrc/pillar_sparse.hip) feeding the first ResNet block directly.
@@ -360,6 +360,84 @@ class PointPillarDiscoNet(nn.Module):
         return self.fuse_and_head(feats, record_len, affine)
 
 
+class PointPillarBaseline(nn.Module):
+    """The single-scale collaborative baselines on PointPillars (opencood/models/point_pillar_baseline.py:17-138: F-Cooper, self-attention, DiscoNet without
+    distillation, V2VNet): pillar encoder, ``BaseBEVBackbone`` or ``ResNetBEVBackbone``, shrink header, optional ``NaiveCompressor``, ONE fusion module on the
+    shrunk map chosen by ``fusion_method`` (max | att | disconet | v2vnet), 1 x 1 heads.  Same constructor keys, ``state_dict`` names and outputs as the reference;
+    ``v2xvit`` / ``when2comm`` (and anything else) are refused at construction -- the reference would build a model without ``fusion_net`` and fail in ``forward``.
+    ``encode`` / ``fuse_and_head`` and the two ``accepts_*`` flags follow ``PointPillarDiscoNet``'s contracts: ``FramePipeline`` and the inference drivers run it
+    unchanged.  The fusion receives the whole [L, L] affine matrix (V2VNet reads every receiver's row)."""
+
+    def __init__(self, args: dict):
+        super().__init__()
+        self.pillar_vfe = PillarVFE(args["pillar_vfe"], num_point_features=4, voxel_size=args["voxel_size"],
+                                    point_cloud_range=args["lidar_range"])
+        self.scatter = PointPillarScatter(args["point_pillar_scatter"])
+        bb = args["base_bev_backbone"]
+        self.backbone = ResNetBEVBackbone(bb, 64) if bb.get("resnet", False) else BaseBEVBackbone(bb, 64)
+        self.voxel_size = args["voxel_size"]
+        method = args["fusion_method"]
+        if method == "max":
+            self.fusion_net = MaxFusion()
+        elif method == "att":
+            self.fusion_net = AttFusion(args["att"]["feat_dim"])
+        elif method == "disconet":
+            self.fusion_net = DiscoFusion(args["disconet"]["feat_dim"])
+        elif method == "v2vnet":
+            self.fusion_net = V2VNetFusion(args["v2vnet"])
+        else:
+            raise NotImplementedError(f"fusion_method '{method}' of point_pillar_baseline is not built here (max | att | disconet | v2vnet)")
+        self.out_channel = sum(bb["num_upsample_filter"])
+        self.shrink_flag = "shrink_header" in args
+        if self.shrink_flag:
+            self.shrink_conv = DownsampleConv(args["shrink_header"])
+            self.out_channel = args["shrink_header"]["dim"][-1]
+        self.compression = "compression" in args
+        if self.compression:
+            self.naive_compressor = NaiveCompressor(self.out_channel, args["compression"])
+        self.cls_head = nn.Conv2d(self.out_channel, args["anchor_number"], kernel_size=1)
+        self.reg_head = nn.Conv2d(self.out_channel, 7 * args["anchor_number"], kernel_size=1)
+        self.use_dir = "dir_args" in args
+        if self.use_dir:
+            self.dir_head = nn.Conv2d(self.out_channel, args["dir_args"]["num_bins"] * args["anchor_number"], kernel_size=1)
+        if args.get("backbone_fix"):
+            self.backbone_fix()
+
+    backbone_fix = PointPillarBaselineMultiscale.backbone_fix
+
+    accepts_normalized_affine = True      # encode() takes data_dict['normalized_affine_matrix'] in place of normalising pairwise_t_matrix itself
+    accepts_pillar_frame = True           # encode() hands processed_lidar['pillar_frame'] to PillarVFE (whose dense-canvas route refuses it: FramePipeline then copies frames)
+
+    def encode(self, data_dict: dict):
+        """Per-agent part: pillars -> canvas -> backbone -> shrink header (-> compressor).  Returns ([the agents' map], normalised affine)."""
+        batch_dict = self.scatter(self.pillar_vfe(_single_agent_batch(dict(data_dict, record_len=host_ints(data_dict["record_len"])))))
+        spatial_features = batch_dict["spatial_features"]
+        H0, W0 = spatial_features.shape[2:]
+        affine = data_dict.get("normalized_affine_matrix")
+        if affine is None:
+            affine = normalize_pairwise_tfm(data_dict["pairwise_t_matrix"], H0, W0, self.voxel_size[0])
+        feats = self.backbone.get_multiscale_feature(spatial_features)
+        # (a stride-1 shrink header on the SplitMap route takes ONE SplitMap from the up-sampling heads and writes channels-last float32, which the fusion reads in place)
+        want_split = bool(self.shrink_flag and all(getattr(m, "is_cuda", False) for m in feats) and self.shrink_conv.takes_split_maps())
+        x = self.backbone.decode_multiscale_feature(feats, out_split=True) if want_split else self.backbone.decode_multiscale_feature(feats)
+        if self.shrink_flag:
+            x = self.shrink_conv(x)
+        elif isinstance(x, ops.SplitMap):
+            x = x.dense()
+        if self.compression:
+            x = self.naive_compressor(x)
+        return [x], affine
+
+    def fuse_and_head(self, feature_list, record_len, affine, rows=None) -> dict:
+        """Ego part: the fusion of the agents' maps, then the heads on the fused map."""
+        return _run_heads(self, self.fusion_net(feature_list[0], record_len, affine, rows=rows))
+
+    def forward(self, data_dict: dict) -> dict:
+        record_len = host_ints(data_dict["record_len"])
+        feats, affine = self.encode(dict(data_dict, record_len=record_len))
+        return self.fuse_and_head(feats, record_len, affine)
+
+
 MODEL_REGISTRY = {
     "point_pillar_baseline_multiscale": PointPillarBaselineMultiscale,
     "point_pillar_coalign": CoAlign,
@@ -372,6 +450,7 @@ MODEL_REGISTRY = {
 # CoAlign hot path serve" -- plans them only when asked to (``plan(hypes, baselines=True)``).
 BASELINE_REGISTRY = {
     "point_pillar_disconet": PointPillarDiscoNet,
+    "point_pillar_baseline": PointPillarBaseline,
 }
 
 

@@ -1,10 +1,11 @@
 """Multi-agent feature fusion modules (SURVEY §8a rows G, H, H'), host side.
 
 Class / function names and signatures follow opencood/models/fuse_modules/fusion_in_one.py
-(``regroup`` :21-24, ``warp_feature`` :26-45, ``MaxFusion`` :47-89, ``AttFusion`` :91-136, ``DiscoFusion`` :138-171) and
+(``regroup`` :21-24, ``warp_feature`` :26-45, ``MaxFusion`` :47-89, ``AttFusion`` :91-136, ``DiscoFusion`` :138-171, ``V2VNetFusion`` :173-293) and
 opencood/models/sub_modules/torch_transformation_utils.py (``warp_affine_simple`` :322-331).  ``MaxFusion`` / ``AttFusion`` own no
 parameters; all their arithmetic is the fused gfx950 kernel ``coalign_warp_fuse``.  ``DiscoFusion`` owns ``PixelWeightLayer``
-(opencood/models/fuse_modules/disco_fuse.py:76-99) and runs on ``coalign_disco_fuse``.
+(opencood/models/fuse_modules/disco_fuse.py:76-99) and runs on ``coalign_disco_fuse``.  ``V2VNetFusion`` owns ``msg_cnn``, a ``ConvGRU``
+(opencood/models/sub_modules/convgru.py) and ``mlp``; its convolutions run on ``coalign_conv3x3_sp``, what lies between them on the three ``coalign_v2v_*`` kernels.
 """
 from __future__ import annotations
 
@@ -15,7 +16,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .backbone import _cache_of, fold_bn
+from . import backbone as _bb
+from .backbone import Conv3x3Pack, PointwisePack, _cache_of, fold_bn
 from .encoder import host_ints
 
 
@@ -188,3 +190,239 @@ class DiscoFusion(nn.Module):
             outs.append(ops.disco_fuse(xx[off:off + n], normalized_affine_matrix[b, 0, :n], image))
             off += n
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+
+class ConvGRUCell(nn.Module):
+    """convgru.py:7-70: gates and candidate of one GRU step as two convolutions over [input | hidden]."""
+
+    def __init__(self, input_size, input_dim: int, hidden_dim: int, kernel_size, bias: bool):
+        super().__init__()
+        self.height, self.width = input_size
+        self.padding = kernel_size[0] // 2, kernel_size[1] // 2
+        self.input_dim, self.hidden_dim, self.bias = input_dim, hidden_dim, bias
+        self.conv_gates = nn.Conv2d(input_dim + hidden_dim, 2 * hidden_dim, kernel_size=tuple(kernel_size), padding=self.padding, bias=bias)
+        self.conv_can = nn.Conv2d(input_dim + hidden_dim, hidden_dim, kernel_size=tuple(kernel_size), padding=self.padding, bias=bias)
+
+    def init_hidden(self, batch_size: int) -> torch.Tensor:
+        return torch.zeros(batch_size, self.hidden_dim, self.height, self.width)
+
+    def forward(self, input_tensor: torch.Tensor, h_cur: torch.Tensor) -> torch.Tensor:
+        combined_conv = self.conv_gates(torch.cat([input_tensor, h_cur], dim=1))
+        gamma, beta = torch.split(combined_conv, self.hidden_dim, dim=1)
+        reset_gate, update_gate = torch.sigmoid(gamma), torch.sigmoid(beta)
+        cnm = torch.tanh(self.conv_can(torch.cat([input_tensor, reset_gate * h_cur], dim=1)))
+        return (1 - update_gate) * h_cur + update_gate * cnm
+
+    def reduced(self):
+        """With h_cur = 0 the cell is ONE convolution input_dim -> 2 hidden followed by sigmoid(first half) * tanh(second half): rows [hidden, 2 hidden) of
+        ``conv_gates`` (the update gate) stacked on ``conv_can``, the first ``input_dim`` input columns of both -> (weight [2 hidden, input_dim, k, k], bias)."""
+        h, i = self.hidden_dim, self.input_dim
+        w = torch.cat([self.conv_gates.weight[h:2 * h, :i], self.conv_can.weight[:, :i]], dim=0).contiguous()
+        if self.conv_gates.bias is None:
+            return w, w.new_zeros(2 * h)
+        return w, torch.cat([self.conv_gates.bias[h:2 * h], self.conv_can.bias]).contiguous()
+
+
+class ConvGRU(nn.Module):
+    """convgru.py:73-196, as far as V2VNetFusion uses it: stacked cells, ``hidden_state`` None (zeros), the last layer's outputs returned."""
+
+    def __init__(self, input_size, input_dim: int, hidden_dim, kernel_size, num_layers: int, batch_first: bool = False, bias: bool = True,
+                 return_all_layers: bool = False):
+        super().__init__()
+        kernel_size = kernel_size if isinstance(kernel_size, list) else [kernel_size] * num_layers
+        hidden_dim = hidden_dim if isinstance(hidden_dim, list) else [hidden_dim] * num_layers
+        if not len(kernel_size) == len(hidden_dim) == num_layers:
+            raise ValueError("Inconsistent list length.")
+        self.height, self.width = input_size
+        self.input_dim, self.hidden_dim, self.kernel_size, self.num_layers = input_dim, hidden_dim, kernel_size, num_layers
+        self.batch_first, self.bias, self.return_all_layers = batch_first, bias, return_all_layers
+        self.cell_list = nn.ModuleList([ConvGRUCell((self.height, self.width), input_dim if i == 0 else hidden_dim[i - 1], hidden_dim[i], kernel_size[i], bias)
+                                        for i in range(num_layers)])
+
+    def forward(self, input_tensor: torch.Tensor, hidden_state=None):
+        if not self.batch_first:
+            input_tensor = input_tensor.permute(1, 0, 2, 3, 4)
+        if hidden_state is not None:
+            raise NotImplementedError()
+        layer_output_list, last_state_list = [], []
+        cur = input_tensor
+        for cell in self.cell_list:
+            h = cell.init_hidden(input_tensor.size(0)).to(input_tensor.device).to(input_tensor.dtype)
+            outs = []
+            for t in range(cur.size(1)):
+                h = cell(cur[:, t], h)
+                outs.append(h)
+            cur = torch.stack(outs, dim=1)
+            layer_output_list.append(cur)
+            last_state_list.append([h])
+        if not self.return_all_layers:
+            layer_output_list, last_state_list = layer_output_list[-1:], last_state_list[-1:]
+        return layer_output_list, last_state_list
+
+
+def _warp_torch(src: torch.Tensor, M: torch.Tensor) -> torch.Tensor:
+    """warp_affine_simple (torch_transformation_utils.py:322-331) in torch ops, output size = input size."""
+    grid = F.affine_grid(M, list(src.shape), align_corners=False).to(src)
+    return F.grid_sample(src, grid, align_corners=False)
+
+
+class V2VNetFusion(nn.Module):
+    """V2VNet's message passing (fusion_in_one.py:173-293).  Per iteration every agent i receives, from every agent j, ``msg_cnn([warp_i(x_j) | x_i])`` masked by the
+    warp of a map of ones; the messages are reduced over j (max / mean) and a ConvGRU with a ZERO hidden state (or a plain sum) turns [x_i | agg_i] into the new x_i;
+    after the last iteration the ego's map goes through ``mlp``.
+
+    ``forward_torch`` states that op by op.  Three exact identities cut its work to a third (``forward_reduced``, the schedule of the kernel route):
+    a GRU cell with h = 0 is one convolution in -> 2 hidden and ``sigmoid(beta) * tanh(cnm)`` (``ConvGRUCell.reduced``); ``msg_cnn`` is linear, so its ego half is
+    computed once per receiver; the last iteration updates the ego alone.  On the GPU in eval mode (``kernel_route``) the convolutions run on ``ops.conv3x3_sp`` and
+    the glue on ``ops.v2v_warp_split`` / ``v2v_aggregate`` / ``v2v_gate``, one launch per stage over all (receiver, sender) pairs of a frame."""
+
+    def __init__(self, args: dict):
+        super().__init__()
+        in_channels = args["in_channels"]
+        gru = args["conv_gru"]
+        self.num_iteration = args["num_iteration"]
+        self.gru_flag = args["gru_flag"]
+        self.agg_operator = args["agg_operator"]
+        self.msg_cnn = nn.Conv2d(in_channels * 2, in_channels, kernel_size=3, stride=1, padding=1)
+        self.conv_gru = ConvGRU(input_size=(gru["H"], gru["W"]), input_dim=in_channels * 2, hidden_dim=[in_channels] * gru["num_layers"], kernel_size=gru["kernel_size"],
+                                num_layers=gru["num_layers"], batch_first=True, bias=True, return_all_layers=False)
+        self.mlp = nn.Linear(in_channels, in_channels)
+        self.force_torch = False      # measurement / test aid: take the op-by-op route whatever the device
+
+    def _check_agg(self) -> None:
+        if self.agg_operator not in ("max", "avg"):
+            raise ValueError("agg_operator has wrong value")
+
+    def kernel_route(self, channels: int, n_agents: int = 1, terms: Optional[int] = None) -> bool:
+        """The static half of the decision (``routes.plan`` asks it): eval mode, 3 x 3 GRU kernels, widths ``conv3x3_sp`` takes (C % 64 == 0, 2C <= its 1024-channel
+        limit), at most 8 agents, the SplitMap arithmetic in force.  ``forward`` adds: a CUDA float32 map."""
+        self._check_agg()
+        k3 = all(tuple(c.conv_gates.kernel_size) == (3, 3) for c in self.conv_gru.cell_list)
+        widths = channels == self.msg_cnn.out_channels and channels % 64 == 0 and _bb.sp_channels_ok(2 * channels, 2 * channels) and ops.v2v_shape_ok(channels, n_agents)
+        return bool(not self.training and not self.force_torch and k3 and widths and _bb.split_maps_active(terms))
+
+    # ---- the reference's loops, op by op -----------------------------------------------------------------------------------------------------------------
+    def forward_torch(self, x: torch.Tensor, record_len, normalized_affine_matrix: torch.Tensor) -> torch.Tensor:
+        _, C, H, W = x.shape
+        groups = host_ints(record_len)
+        feats = list(torch.split(x, groups, dim=0))
+        A = normalized_affine_matrix
+        masks = [[_warp_torch(x.new_ones((N, 1, H, W)), A[b, i, :N]) for i in range(N)] for b, N in enumerate(groups)]
+        for _ in range(self.num_iteration):
+            updated_batch = []
+            for b, N in enumerate(groups):
+                updated = []
+                for i in range(N):
+                    neighbor_feature = _warp_torch(feats[b], A[b, i, :N])
+                    ego_agent_feature = feats[b][i].unsqueeze(0).repeat(N, 1, 1, 1)
+                    message = self.msg_cnn(torch.cat([neighbor_feature, ego_agent_feature], dim=1)) * masks[b][i]
+                    if self.agg_operator == "avg":
+                        agg_feature = torch.mean(message, dim=0)
+                    elif self.agg_operator == "max":
+                        agg_feature = torch.max(message, dim=0)[0]
+                    else:
+                        raise ValueError("agg_operator has wrong value")
+                    if self.gru_flag:
+                        cat_feature = torch.cat([feats[b][i], agg_feature], dim=0)
+                        gru_out = self.conv_gru(cat_feature.unsqueeze(0).unsqueeze(0))[0][0].squeeze(0).squeeze(0)
+                    else:
+                        gru_out = feats[b][i] + agg_feature
+                    updated.append(gru_out.unsqueeze(0))
+                updated_batch.append(torch.cat(updated, dim=0))
+            feats = updated_batch
+        out = torch.cat([f[0].unsqueeze(0) for f in feats], dim=0)
+        return self.mlp(out.permute(0, 2, 3, 1)).permute(0, 3, 1, 2)
+
+    # ---- the three identities, in the kernel route's schedule ------------------------------------------------------------------------------------------------
+    def reduced_weights(self):
+        """(msg_cnn's warped-map columns [C, C, 3, 3], its ego columns, its bias, [(cell weight [2 hidden, in, 3, 3], bias)]): views / stacks of the parameters."""
+        C = self.msg_cnn.out_channels
+        w = self.msg_cnn.weight
+        return w[:, :C].contiguous(), w[:, C:].contiguous(), self.msg_cnn.bias, [c.reduced() for c in self.conv_gru.cell_list]
+
+    @staticmethod
+    def _receivers(iteration: int, iterations: int, n: int) -> int:
+        return n if iteration < iterations - 1 else 1      # the output reads agent 0 of the last iteration only
+
+    def forward_reduced(self, x: torch.Tensor, record_len, normalized_affine_matrix: torch.Tensor) -> torch.Tensor:
+        self._check_agg()
+        _, C, H, W = x.shape
+        groups = host_ints(record_len)
+        wn, we, bm, cells = self.reduced_weights()
+        outs, off = [], 0
+        for b, N in enumerate(groups):
+            xb, theta = x[off:off + N], normalized_affine_matrix[b, :N, :N]
+            off += N
+            for it in range(self.num_iteration):
+                R = self._receivers(it, self.num_iteration, N)
+                e = F.conv2d(xb[:R], we, bm, padding=1)                                                              # the ego term, once per receiver
+                warped = torch.cat([_warp_torch(xb, theta[i]) for i in range(R)], dim=0)                             # [R N, C, H, W]
+                a = F.conv2d(warped, wn, None, padding=1).view(R, N, C, H, W)
+                mask = torch.stack([_warp_torch(xb.new_ones((N, 1, H, W)), theta[i]) for i in range(R)], dim=0)      # [R, N, 1, H, W]
+                m = (a + e.unsqueeze(1)) * mask
+                if self.agg_operator == "max":
+                    agg = m.max(dim=1)[0]
+                else:
+                    agg = m[:, 0]
+                    for j in range(1, N):
+                        agg = agg + m[:, j]
+                    agg = agg / N
+                if self.gru_flag:
+                    h = torch.cat([xb[:R], agg], dim=1)
+                    for cw, cb in cells:
+                        y = F.conv2d(h, cw, cb, padding=1)
+                        hid = cw.shape[0] // 2
+                        h = torch.sigmoid(y[:, :hid]) * torch.tanh(y[:, hid:])
+                else:
+                    h = xb[:R] + agg
+                xb = h
+            outs.append(xb[:1])
+        out = torch.cat(outs, dim=0)
+        return self.mlp(out.permute(0, 2, 3, 1)).permute(0, 3, 1, 2)
+
+    # ---- the kernel route ----------------------------------------------------------------------------------------------------------------------------------------
+    def packed(self):
+        """The weight images of the kernel route (``Conv3x3Pack(...).emu(16, True)`` of the sliced weights, the pointwise image of ``mlp``), cached until a parameter
+        changes: (warped-map image, ego image, msg bias, zero bias, [(cell image, bias, 2 hidden)], mlp image, mlp bias)."""
+        def build():
+            wn, we, bm, cells = self.reduced_weights()
+            C = wn.shape[0]
+            mlp = PointwisePack(self.mlp.weight.detach().reshape(C, C, 1, 1), False)
+            return (Conv3x3Pack(wn).emu(16, True), Conv3x3Pack(we).emu(16, True), bm.detach().float().contiguous(), torch.zeros_like(bm, dtype=torch.float32),
+                    [(Conv3x3Pack(cw).emu(16, True), cb.detach().float().contiguous(), cw.shape[0]) for cw, cb in cells], mlp.get(), self.mlp.bias.detach().float().contiguous())
+        return _cache_of(self, "_coalign_v2v_images").get(self, build)
+
+    def forward_kernels(self, xx: torch.Tensor, groups: Sequence[int], normalized_affine_matrix: torch.Tensor) -> torch.Tensor:
+        img_n, img_e, bm, zero, cells, img_mlp, b_mlp = self.packed()
+        C = xx.shape[1]
+        if not ops.nhwc_memory(xx):
+            xx = xx.contiguous(memory_format=torch.channels_last)      # (a stride-1 shrink header's conv3x3_sp writes channels-last: no copy there)
+            if not ops.nhwc_memory(xx):                                 # (a 1 x 1 map or C = 1: every stride order counts as channels-last)
+                xx = xx.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+        outs, off = [], 0
+        for b, n in enumerate(groups):
+            xb = xx[off:off + n]
+            theta = normalized_affine_matrix[b, :n, :n].to(device=xx.device, dtype=torch.float64).contiguous()
+            off += n
+            for it in range(self.num_iteration):
+                R = self._receivers(it, self.num_iteration, n)
+                th = theta[:R]
+                e = ops.conv3x3_sp(ops.SplitMap.pack(xb[:R]), img_e, bm, C, None, False, out_split=False)
+                a = ops.conv3x3_sp(ops.v2v_warp_split(xb, th), img_n, zero, C, None, False, out_split=False)
+                h = ops.v2v_aggregate(a, e, xb, th, self.agg_operator, gru=bool(self.gru_flag))
+                if self.gru_flag:
+                    for k, (img, bias, width) in enumerate(cells):
+                        h = ops.v2v_gate(ops.conv3x3_sp(h, img, bias, width, None, False, out_split=False), out_split=k + 1 < len(cells))
+                xb = h
+            outs.append(xb[:1])
+        out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+        return ops.pointwise_conv(out, img_mlp, b_mlp, C, relu=False, out_channels_last=True)
+
+    def forward(self, x: torch.Tensor, record_len, normalized_affine_matrix: torch.Tensor, rows=None) -> torch.Tensor:
+        if rows is not None:
+            raise NotImplementedError("V2VNetFusion does not run agent-sharded (rows)")
+        groups = host_ints(record_len)
+        if x.is_cuda and x.dtype == torch.float32 and sum(groups) == x.shape[0] and self.kernel_route(x.shape[1], max(groups)):
+            return self.forward_kernels(x, groups, normalized_affine_matrix)
+        self._check_agg()
+        return self.forward_torch(x, groups, normalized_affine_matrix)

@@ -140,6 +140,14 @@ DISCO_SIGNATURES = {
     "coalign_disco_fuse": (c_int, [P, c_int, c_int, c_int, c_int, P, P, c_size_t, P, P]),
 }
 
+# include/coalign_amd_v2v.h: the sixth extension header of ABI version 2 (product library): the glue of V2VNet's message passing between its convolutions --
+# warp + operand split, message mask + aggregation + GRU input, GRU gate (csrc/v2v_fuse.hip)
+V2V_SIGNATURES = {
+    "coalign_v2v_warp_split": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "coalign_v2v_aggregate": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P]),
+    "coalign_v2v_gate": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
+}
+
 _LAB_LIB = None
 
 
@@ -166,7 +174,7 @@ def lib() -> ctypes.CDLL:
             raise CoalignHipError(
                 f"{path} is missing and could not be built ({exc}); the CoAlign hot path has no CPU fallback") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES}.items():
         fn = getattr(handle, name)  # AttributeError here == header / library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -190,7 +198,7 @@ def lab_lib() -> ctypes.CDLL:
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(f"{path} is missing and could not be built ({exc})") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **LAB_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **LAB_SIGNATURES}.items():
         fn = getattr(handle, name)
         fn.restype = res
         fn.argtypes = args

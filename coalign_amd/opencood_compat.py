@@ -24,6 +24,8 @@ _EXPORTS: Dict[str, Dict[str, object]] = {
     "opencood.models.point_pillar_coalign": {"CoAlign": detector.CoAlign},
     "opencood.models.point_pillar": {"PointPillar": detector.PointPillar},
     "opencood.models.point_pillar_disconet": {"PointPillarDiscoNet": detector.PointPillarDiscoNet},
+    "opencood.models.point_pillar_baseline": {"PointPillarBaseline": detector.PointPillarBaseline},
+    "opencood.models.sub_modules.convgru": {"ConvGRU": fusion.ConvGRU, "ConvGRUCell": fusion.ConvGRUCell},
     "opencood.models.fuse_modules.disco_fuse": {"PixelWeightLayer": fusion.PixelWeightLayer},
     "opencood.models.sub_modules.pillar_vfe": {"PillarVFE": encoder.PillarVFE, "PFNLayer": encoder.PFNLayer},
     "opencood.models.sub_modules.point_pillar_scatter": {"PointPillarScatter": encoder.PointPillarScatter},
@@ -32,7 +34,7 @@ _EXPORTS: Dict[str, Dict[str, object]] = {
     "opencood.models.sub_modules.downsample_conv": {"DownsampleConv": backbone.DownsampleConv, "DoubleConv": backbone.DoubleConv},
     "opencood.models.sub_modules.naive_compress": {"NaiveCompressor": backbone.NaiveCompressor},
     "opencood.models.sub_modules.torch_transformation_utils": {"warp_affine_simple": fusion.warp_affine_simple},
-    "opencood.models.fuse_modules.fusion_in_one": {"AttFusion": fusion.AttFusion, "MaxFusion": fusion.MaxFusion, "DiscoFusion": fusion.DiscoFusion,
+    "opencood.models.fuse_modules.fusion_in_one": {"AttFusion": fusion.AttFusion, "MaxFusion": fusion.MaxFusion, "DiscoFusion": fusion.DiscoFusion, "V2VNetFusion": fusion.V2VNetFusion,
                                                    "regroup": fusion.regroup, "warp_feature": fusion.warp_feature},
     "opencood.models.fuse_modules.fuse_utils": {"regroup": fusion.regroup},
     "opencood.utils.transformation_utils": {"normalize_pairwise_tfm": pose.normalize_pairwise_tfm, "x_to_world": pose.x_to_world,

@@ -1612,3 +1612,81 @@ def disco_fuse(x: torch.Tensor, theta: torch.Tensor, params: torch.Tensor) -> to
     with _Timed("disco_fuse"):
         hip.check(L.coalign_disco_fuse(_ptr(x), n, C, H, W, _ptr(th), _ptr(params), params.numel(), _ptr(out), _stream()), "coalign_disco_fuse")
     return out
+
+
+# ---- V2VNet's message passing between its convolutions (include/coalign_amd_v2v.h, csrc/v2v_fuse.hip) -------------------------------------------------
+V2V_AGG = {"max": 0, "avg": 1}                     # COALIGN_V2V_AGG_*
+V2V_OUT_NHWC, V2V_OUT_SP = 0, 1                    # COALIGN_V2V_OUT_*
+
+
+def v2v_shape_ok(channels: int, n_agents: int) -> bool:
+    """The shapes the three ``coalign_v2v_*`` kernels take: C % 16 == 0, 1 .. 8 agents (any H, W)."""
+    return channels > 0 and channels % 16 == 0 and 1 <= n_agents <= 8
+
+
+def _nhwc_map(t: torch.Tensor, what: str) -> Tuple[int, int, int, int]:
+    if t.dtype != torch.float32 or t.dim() != 4 or not nhwc_memory(t):
+        raise ValueError(f"{what}: a float32 map [N, C, H, W] in channels-last memory")
+    return tuple(t.shape)
+
+
+def _theta_pairs(theta: torch.Tensor, n: int, device) -> torch.Tensor:
+    th = theta.to(device=device, dtype=torch.float64).contiguous()
+    if th.dim() != 4 or th.shape[1] != n or tuple(th.shape[2:]) != (2, 3) or not 1 <= th.shape[0] <= n:
+        raise ValueError("theta: [R <= n, n, 2, 3], row (i, j) receiver i's grid in sender j")
+    return th
+
+
+def _nhwc_empty(N: int, C: int, H: int, W: int, device) -> torch.Tensor:
+    return torch.empty((N, H, W, C), dtype=torch.float32, device=device).permute(0, 3, 1, 2)
+
+
+@_device_op
+def v2v_warp_split(x: torch.Tensor, theta: torch.Tensor) -> "SplitMap":
+    """``SplitMap`` [R n, C, H, W] of ``warp_affine_simple(x[j], theta[i, j])`` at index i n + j in one pass (``coalign_v2v_warp_split``): x [n <= 8, C, H, W]
+    float32 channels-last, theta [R <= n, n, 2, 3].  Bit for bit ``SplitMap.pack(warp_fuse_nhwc([x], theta[i], FUSE_NONE)[0])`` per receiver."""
+    _need_gpu(x, theta)
+    n, C, H, W = _nhwc_map(x, "v2v_warp_split")
+    if not v2v_shape_ok(C, n):
+        raise ValueError("v2v_warp_split: C % 16 == 0, 1 .. 8 agents")
+    th = _theta_pairs(theta, n, x.device)
+    R = th.shape[0]
+    out = SplitMap.empty(R * n, C, H, W, x.device)
+    with _Timed("v2v_warp_split"):
+        hip.check(hip.lib().coalign_v2v_warp_split(_ptr(x), n, R, C, H, W, _ptr(th), _ptr(out.data), _ptr(sp_range_flag(x.device)), _stream()), "coalign_v2v_warp_split")
+    return out
+
+
+@_device_op
+def v2v_aggregate(a: torch.Tensor, e: torch.Tensor, x: torch.Tensor, theta: torch.Tensor, agg: str = "max", gru: bool = True):
+    """m_ij = (a[i n + j] + e[i]) * mask_ij, agg_i = max_j / mean_j m_ij (``coalign_v2v_aggregate``); ``gru``: the SplitMap [R, 2C, H, W] of [x_i | agg_i], else the
+    float32 channels-last map x_i + agg_i.  a [R n, C, H, W], e [R, C, H, W], x [>= R, C, H, W] float32 channels-last, theta [R, n, 2, 3]."""
+    _need_gpu(a, e, x, theta)
+    if agg not in V2V_AGG:
+        raise ValueError("agg_operator has wrong value")
+    R, C, H, W = _nhwc_map(e, "v2v_aggregate e")
+    Rn = _nhwc_map(a, "v2v_aggregate a")[0]
+    n = Rn // max(R, 1)
+    th = _theta_pairs(theta, n, e.device)
+    if not v2v_shape_ok(C, n) or tuple(a.shape) != (R * n, C, H, W) or th.shape[0] != R or _nhwc_map(x, "v2v_aggregate x")[1:] != (C, H, W) or x.shape[0] < R:
+        raise ValueError("v2v_aggregate: a [R n, C, H, W], e [R, C, H, W], x [>= R, C, H, W], theta [R, n, 2, 3], C % 16 == 0, n <= 8")
+    out = SplitMap.empty(R, 2 * C, H, W, e.device) if gru else _nhwc_empty(R, C, H, W, e.device)
+    with _Timed("v2v_aggregate"):
+        hip.check(hip.lib().coalign_v2v_aggregate(_ptr(a), _ptr(e), _ptr(x), n, R, C, H, W, _ptr(th), V2V_AGG[agg], V2V_OUT_SP if gru else V2V_OUT_NHWC,
+                                                  _ptr(out.data if gru else out), _ptr(sp_range_flag(e.device)) if gru else None, _stream()), "coalign_v2v_aggregate")
+    return out
+
+
+@_device_op
+def v2v_gate(y: torch.Tensor, out_split: bool = False):
+    """sigmoid(y[:, :Ch]) * tanh(y[:, Ch:]) (``coalign_v2v_gate``): y [R, 2 Ch, H, W] float32 channels-last -> float32 channels-last [R, Ch, H, W] or its SplitMap."""
+    _need_gpu(y)
+    R, C2, H, W = _nhwc_map(y, "v2v_gate")
+    if C2 % 32:
+        raise ValueError("v2v_gate: Ch % 16 == 0")
+    Ch = C2 // 2
+    out = SplitMap.empty(R, Ch, H, W, y.device) if out_split else _nhwc_empty(R, Ch, H, W, y.device)
+    with _Timed("v2v_gate"):
+        hip.check(hip.lib().coalign_v2v_gate(_ptr(y), R, Ch, H, W, V2V_OUT_SP if out_split else V2V_OUT_NHWC, _ptr(out.data if out_split else out),
+                                             _ptr(sp_range_flag(y.device)) if out_split else None, _stream()), "coalign_v2v_gate")
+    return out

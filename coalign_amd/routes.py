@@ -3,13 +3,13 @@
 The detector picks its kernels per layer at run time; a layer whose shape a hand-written kernel does not take falls back to MIOpen / the per-scale NCHW fusion kernel /
 the fp32 VALU encoder -- correct, slower, and until round 3 silent.  ``plan(hypes)`` builds the model of a hypes dictionary, asks every module the decision function its
 ``forward`` dispatches on (``backbone.conv3x3_route`` / ``pointwise_split``, ``BasicBlock.route``, ``DoubleConv.on_split_maps``, the decode mixin's ``heads_pointwise`` /
-``heads_write_split``, ``NaiveCompressor.split_widths``, ``detector.heads_route`` / ``sparse_canvas_route`` / ``compressor_sparse_route`` / ``fusion_route``, ``DiscoFusion.kernel_route``, ``PillarVFE.matrix_core_ok``) with the arithmetic
+``heads_write_split``, ``NaiveCompressor.split_widths``, ``detector.heads_route`` / ``sparse_canvas_route`` / ``compressor_sparse_route`` / ``fusion_route``, ``DiscoFusion.kernel_route``, ``V2VNetFusion.kernel_route``, ``PillarVFE.matrix_core_ok``) with the arithmetic
 mode passed in, and words the answers -- this module holds no shape rule of its own -- so that a yaml that would leave the fast path shows up in a CPU test
 (tests/test_host_cpu.py walks the reference's ``hypes_yaml/**/pointpillar*.yaml`` with it) instead of in a profile.
 The line of the merged 1x1 heads names the kernel that reads a float32 map (pointwise within its Cin limit, else rocBLAS, listed as a fallback): where a one-layer shrink header
 hands them a SplitMap (``detector.heads_route(model).split_in``) they run on ``heads_sp`` whatever that line says.
 
-    python -m coalign_amd.routes [--baselines] <hypes.yaml> [...]          # prints the plan(s) as JSON; --baselines: plan DiscoNet too
+    python -m coalign_amd.routes [--baselines] <hypes.yaml> [...]          # prints the plan(s) as JSON; --baselines: plan DiscoNet and point_pillar_baseline too
 """
 from __future__ import annotations
 
@@ -22,7 +22,7 @@ import torch.nn as nn
 from . import backbone as bb
 from . import detector
 from .detector import BASELINE_REGISTRY, MODEL_REGISTRY, build_model
-from .fusion import DiscoFusion
+from .fusion import DiscoFusion, V2VNetFusion
 
 EMU, F32, MIOPEN, ROCBLAS, POINTWISE = "conv3x3_emu (split 16-bit matrix cores)", "conv3x3 (fp32 matrix cores) / MIOpen by shape", "MIOpen", "rocBLAS (1x1 heads)", "pointwise"
 WINO = "conv3x3_wino (Winograd F(2x2,3x3), split-bf16 matrix cores)"
@@ -31,6 +31,9 @@ NARROW = "conv3x3_sp_narrow (16 / 32 output channels, weight-stationary, SplitMa
 COMPRESSOR_LIBRARY = MIOPEN + " (compressor: SURVEY 8a row D keeps it on the library)"
 DISCO = "disco_fuse: warp + pixel-weight MLP + softmax in one launch"
 DISCO_TORCH = "DiscoFusion op by op in PyTorch (channels outside the kernel's C % 32 == 0, 32 .. 384)"
+V2V = "v2v_warp_split + conv3x3_sp + v2v_aggregate + conv3x3_sp + v2v_gate per iteration, one launch per stage over all (receiver, sender) pairs"
+V2V_TORCH = "V2VNetFusion op by op in PyTorch"
+STRIDED_SHRINK = MIOPEN + " (strided shrink-header convolution: library route)"
 SPLIT_OUT = ", SplitMap out"
 SPARSE_IN = ", sparse canvas in"
 DEFAULT_TERMS = bb.DEFAULT_CONV_EMU_TERMS      # the 2-way fp16 split since round 4
@@ -96,11 +99,20 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS, baselines: bool = False) -> Di
                 note(f"{n}.downsample.0", pointwise_text(m.downsample[0].in_channels, terms) if m.skip_pointwise() else MIOPEN + " (skip convolution outside the pointwise kernel's shapes)")
         elif isinstance(m, bb.DoubleConv):
             split, c1, c2 = m.on_split_maps(terms), m.double_conv[0], m.double_conv[2]
+            if isinstance(model, detector.PointPillarBaseline) and not m._layer_ok(c1, bb.conv3x3_shape_ok):      # DoubleConv.forward builds no weight image for it
+                note(f"{n}.double_conv.0", STRIDED_SHRINK if c1.stride != (1, 1) else MIOPEN + " (no weight image for the shape)", True)
+                note(f"{n}.double_conv.2", conv3x3_text(c2, terms))
+                continue
             note(f"{n}.double_conv.0", SP if split and heads_split and m is first_shrink else conv3x3_text(c1, terms) + (SPLIT_OUT if split else ""))
             note(f"{n}.double_conv.2", SP if split else conv3x3_text(c2, terms))
         elif isinstance(m, nn.Conv2d) and n.startswith("fusion_net.") and isinstance(model.fusion_net, DiscoFusion):
             ok = model.fusion_net.kernel_route(model.out_channel)      # the four 1x1 layers of PixelWeightLayer run inside the fusion launch
             note(n, "disco_fuse (pixel-weight MLP layer inside the fusion launch)" if ok else MIOPEN + " (DiscoFusion op by op)", not ok)
+        elif isinstance(m, nn.Conv2d) and n.startswith("fusion_net.") and isinstance(model.fusion_net, V2VNetFusion):
+            ok = model.fusion_net.kernel_route(model.out_channel, 1, terms)
+            what = (" (V2VNet: the warped-map and the ego columns as two C -> C convolutions)" if n.endswith("msg_cnn") else
+                    " (V2VNet: update-gate rows of conv_gates stacked on conv_can, one convolution per GRU cell)")
+            note(n, SP + what if ok else MIOPEN + " (V2VNetFusion op by op)", not ok)
         elif isinstance(m, nn.Conv2d) and n not in layers and "naive_compressor" not in n:
             if tuple(m.kernel_size) == (1, 1) and n.endswith("_head"):
                 ok = detector.heads_route(model, terms).pointwise
@@ -125,7 +137,22 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS, baselines: bool = False) -> Di
                   if detector.compressor_sparse_route(model, terms) else
                   "matrix-core encoder (linearised PFN, split-bf16), persistent dense canvas" if bb.emu_active(terms) else "matrix-core encoder, NCHW strip writer")
     fusion = None
-    if isinstance(getattr(model, "fusion_net", None), DiscoFusion):          # ONE single-scale module on the shrunk map, not a ModuleList
+    if isinstance(getattr(model, "fusion_net", None), V2VNetFusion):         # ONE single-scale module on the shrunk map
+        f = model.fusion_net
+        ok = f.kernel_route(model.out_channel, 1, terms)
+        note("fusion_net.mlp", pointwise_text(f.mlp.in_features, terms) + ", 1 x 1 on the fused map" if ok else ROCBLAS.split(" (")[0] + " (nn.Linear, V2VNetFusion op by op)", not ok)
+        if ok:
+            fusion = V2V
+        else:
+            k3 = all(tuple(c.conv_gates.kernel_size) == (3, 3) for c in f.conv_gru.cell_list)
+            why = ("GRU kernels other than 3 x 3" if not k3 else f"{model.out_channel} channels outside C % 64 == 0, C <= 512" if model.out_channel % 64 or model.out_channel > 512
+                   or model.out_channel != f.msg_cnn.out_channels else "the SplitMap arithmetic (fp16 x 2) is not in force")
+            fusion = V2V_TORCH + f" ({why})"
+            fallbacks.append("fusion")
+    elif isinstance(getattr(model, "fusion_net", None), (detector.MaxFusion, detector.AttFusion)):      # point_pillar_baseline: ONE module, the NCHW kernel
+        fusion = "warp_fuse: one launch (NCHW, LDS-staged patches)"
+        fallbacks.append("fusion")
+    elif isinstance(getattr(model, "fusion_net", None), DiscoFusion):          # ONE single-scale module on the shrunk map, not a ModuleList
         if model.fusion_net.kernel_route(model.out_channel):
             fusion = DISCO
         else:

@@ -331,3 +331,36 @@ def disco_parameters_(layer: torch.nn.Module, seed: int = 0, input_scale: float 
                 if name == "conv1_4.weight":
                     v = v.abs() * 3.0                    # non-negative on the non-negative last hidden layer: with its positive bias every logit passes the last ReLU
             t.copy_(v.to(t.dtype))
+
+
+def v2v_parameters_(module: torch.nn.Module, seed: int = 0, input_scale: float = 1.0) -> None:
+    """Test weights for a ``V2VNetFusion`` (this package's or the reference's: keyed by ``state_dict`` name) that keep every stage VISIBLE in the output.  Freshly
+    initialised (PyTorch's 1 / sqrt(3 fan-in) weights) the messages are a tenth of the node features and the GRU's pre-activations so small that every gate sits at
+    0.5.  Here: ``msg_cnn`` with unit gain over its 2C x 9 inputs (a message is of the order of the maps it is made of), the GRU cells with a gain of 0.8 over the
+    input columns that are ever non-zero (the hidden state is zero: most update gates fall in (0.1, 0.9), the candidate's tanh stays in its curved part), ``mlp`` with
+    unit gain, small biases.  Maps of magnitude ``input_scale`` are met by dividing ``msg_cnn`` and the node-feature columns of the first cell by it (the message
+    columns see messages that ``msg_cnn`` has already brought to order one), so that the FIRST iteration's pre-activations are of order one.  Every later iteration's
+    node features are gate outputs, below one whatever the input was: with ``input_scale`` far from 1 only a one-iteration module is calibrated throughout."""
+    import zlib
+    sd = module.state_dict()
+    down = float(input_scale)
+    with torch.no_grad():
+        for name in sorted(sd.keys()):
+            t = sd[name]
+            if not t.is_floating_point():
+                continue
+            g = torch.Generator().manual_seed((zlib.crc32(name.encode()) + seed) & 0x7FFFFFFF)
+            shape = tuple(t.shape)
+            if name.endswith("bias"):
+                v = (torch.rand(shape, generator=g) - 0.5) * 0.2
+            elif name == "msg_cnn.weight":
+                v = torch.randn(shape, generator=g) * (1.0 / t[0].numel()) ** 0.5 / down
+            elif name.startswith("conv_gru.cell_list."):
+                hidden = t.shape[0] // 2 if "conv_gates" in name else t.shape[0]
+                live = (t.shape[1] - hidden) * t.shape[2] * t.shape[3]                    # the hidden-state columns only ever multiply zeros
+                v = torch.randn(shape, generator=g) * 0.8 * (1.0 / live) ** 0.5
+                if name.startswith("conv_gru.cell_list.0."):
+                    v[:, :(t.shape[1] - hidden) // 2] /= down                               # [x_i | agg_i | h]: the node-feature columns
+            else:                                                                        # mlp.weight
+                v = torch.randn(shape, generator=g) * (1.0 / t[0].numel()) ** 0.5
+            t.copy_(v.to(t.dtype))
