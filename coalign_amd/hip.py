@@ -148,6 +148,14 @@ V2V_SIGNATURES = {
     "coalign_v2v_gate": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
 }
 
+# include/coalign_amd_v2x.h: the seventh extension header of ABI version 2 (product library): V2X-ViT's heterogeneous agent attention -- warp, LayerNorm, the folded
+# q / k / v projection, softmax over the agents per head, output projection and residual in two launches (csrc/v2x_attn.hip)
+V2X_SIGNATURES = {
+    "coalign_v2x_param_bytes": (c_size_t, [c_int]),
+    "coalign_v2x_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "coalign_v2x_agent_attention": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P, P, c_size_t, P]),
+}
+
 _LAB_LIB = None
 
 
@@ -174,7 +182,7 @@ def lib() -> ctypes.CDLL:
             raise CoalignHipError(
                 f"{path} is missing and could not be built ({exc}); the CoAlign hot path has no CPU fallback") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES}.items():
         fn = getattr(handle, name)  # AttributeError here == header / library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -198,7 +206,7 @@ def lab_lib() -> ctypes.CDLL:
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(f"{path} is missing and could not be built ({exc})") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **LAB_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **LAB_SIGNATURES}.items():
         fn = getattr(handle, name)
         fn.restype = res
         fn.argtypes = args

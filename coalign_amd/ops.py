@@ -1690,3 +1690,54 @@ def v2v_gate(y: torch.Tensor, out_split: bool = False):
         hip.check(hip.lib().coalign_v2v_gate(_ptr(y), R, Ch, H, W, V2V_OUT_SP if out_split else V2V_OUT_NHWC, _ptr(out.data if out_split else out),
                                              _ptr(sp_range_flag(y.device)) if out_split else None, _stream()), "coalign_v2v_gate")
     return out
+
+
+# ---- V2X-ViT's heterogeneous agent attention (include/coalign_amd_v2x.h, csrc/v2x_attn.hip) ------------------------------------------------------------
+V2X_DIM_HEAD = 32
+
+
+def v2x_attn_shape_ok(channels: int, heads: int, dim_head: int, n_agents: int = 1) -> bool:
+    """The shapes ``coalign_v2x_agent_attention`` takes: C = heads x 32 = 256 or 64, 1 .. 8 agents (any H, W)."""
+    return channels in (64, 256) and dim_head == V2X_DIM_HEAD and heads * dim_head == channels and 1 <= n_agents <= 8
+
+
+def pack_v2x_weights(wqkv: torch.Tensor, bqkv: torch.Tensor, wa: torch.Tensor, ba: torch.Tensor) -> Optional[torch.Tensor]:
+    """The folded agent-attention layer (wqkv [3C, C] = [q | k' | v'] rows, bqkv [3C], wa [C, C], ba [C]) -> the parameter image of ``coalign_v2x_agent_attention``
+    (layout: the header's (13a)), a uint8 tensor on the weights' device; None when a weight lies outside the fp16 range (its sp16 pair would saturate)."""
+    wqkv, wa = wqkv.detach().float(), wa.detach().float()
+    C = wa.shape[0]
+    if tuple(wqkv.shape) != (3 * C, C) or tuple(wa.shape) != (C, C) or C not in (64, 256):
+        raise ValueError("pack_v2x_weights: wqkv [3C, C], wa [C, C], C = 64 or 256")
+    if not bool(torch.isfinite(wqkv).all() and torch.isfinite(wa).all()) or max(float(wqkv.abs().max()), float(wa.abs().max())) > 65504.0:
+        return None
+    floats = torch.cat([bqkv.detach().float().reshape(-1), ba.detach().float().reshape(-1)])
+    img = torch.cat([_disco_operand_image(wqkv), _disco_operand_image(wa), floats.contiguous().view(torch.uint8)])
+    assert img.numel() == (C // 16) * (4 * C // 32) * 2048 + 16 * C
+    return img.contiguous()
+
+
+@_device_op
+def v2x_agent_attention(x: torch.Tensor, theta: Optional[torch.Tensor], params: torch.Tensor, receivers: Optional[int] = None) -> torch.Tensor:
+    """x + HGTCavAttention(LayerNorm(x)) over the agents of ONE frame (``coalign_v2x_agent_attention``): x [n <= 8, H, W, C] float32 contiguous (agent 0 the ego),
+    theta [n, 2, 3] (row 0 of the frame's normalised affine matrix: x is warped first) or None (x is read in place), params from ``pack_v2x_weights``,
+    ``receivers`` R = n (default) or 1 -> [R, H, W, C] float32."""
+    _need_gpu(x, params) if theta is None else _need_gpu(x, theta, params)
+    L = hip.lib()
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("v2x_agent_attention needs a contiguous float32 map [n, H, W, C]")
+    n, H, W, C = x.shape
+    R = n if receivers is None else int(receivers)
+    if C not in (64, 256) or not 1 <= n <= 8 or R not in (1, n):
+        raise ValueError("v2x_agent_attention: C = 64 or 256, 1 .. 8 agents, receivers = n or 1")
+    th = None
+    if theta is not None:
+        th = theta.to(device=x.device, dtype=torch.float64).contiguous()
+        if tuple(th.shape) != (n, 2, 3):
+            raise ValueError("one theta row per agent")
+    ws_bytes = int(L.coalign_v2x_workspace_bytes(n, C, H, W))
+    ws = torch.empty(max(ws_bytes, 16) // 4, dtype=torch.float32, device=x.device)
+    out = torch.empty((R, H, W, C), dtype=torch.float32, device=x.device)
+    with _Timed("v2x_agent_attention"):
+        hip.check(L.coalign_v2x_agent_attention(_ptr(x), n, R, C, H, W, _ptr(th), _ptr(params), params.numel(), _ptr(out), _ptr(ws), ws_bytes, _stream()),
+                  "coalign_v2x_agent_attention")
+    return out

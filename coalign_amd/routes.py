@@ -3,7 +3,7 @@
 The detector picks its kernels per layer at run time; a layer whose shape a hand-written kernel does not take falls back to MIOpen / the per-scale NCHW fusion kernel /
 the fp32 VALU encoder -- correct, slower, and until round 3 silent.  ``plan(hypes)`` builds the model of a hypes dictionary, asks every module the decision function its
 ``forward`` dispatches on (``backbone.conv3x3_route`` / ``pointwise_split``, ``BasicBlock.route``, ``DoubleConv.on_split_maps``, the decode mixin's ``heads_pointwise`` /
-``heads_write_split``, ``NaiveCompressor.split_widths``, ``detector.heads_route`` / ``sparse_canvas_route`` / ``compressor_sparse_route`` / ``fusion_route``, ``DiscoFusion.kernel_route``, ``V2VNetFusion.kernel_route``, ``PillarVFE.matrix_core_ok``) with the arithmetic
+``heads_write_split``, ``NaiveCompressor.split_widths``, ``detector.heads_route`` / ``sparse_canvas_route`` / ``compressor_sparse_route`` / ``fusion_route``, ``DiscoFusion.kernel_route``, ``V2VNetFusion.kernel_route``, ``V2XViTFusion.kernel_route``, ``PillarVFE.matrix_core_ok``) with the arithmetic
 mode passed in, and words the answers -- this module holds no shape rule of its own -- so that a yaml that would leave the fast path shows up in a CPU test
 (tests/test_host_cpu.py walks the reference's ``hypes_yaml/**/pointpillar*.yaml`` with it) instead of in a profile.
 The line of the merged 1x1 heads names the kernel that reads a float32 map (pointwise within its Cin limit, else rocBLAS, listed as a fallback): where a one-layer shrink header
@@ -22,7 +22,7 @@ import torch.nn as nn
 from . import backbone as bb
 from . import detector
 from .detector import BASELINE_REGISTRY, MODEL_REGISTRY, build_model
-from .fusion import DiscoFusion, V2VNetFusion
+from .fusion import DiscoFusion, V2VNetFusion, V2XViTFusion
 
 EMU, F32, MIOPEN, ROCBLAS, POINTWISE = "conv3x3_emu (split 16-bit matrix cores)", "conv3x3 (fp32 matrix cores) / MIOpen by shape", "MIOpen", "rocBLAS (1x1 heads)", "pointwise"
 WINO = "conv3x3_wino (Winograd F(2x2,3x3), split-bf16 matrix cores)"
@@ -33,6 +33,10 @@ DISCO = "disco_fuse: warp + pixel-weight MLP + softmax in one launch"
 DISCO_TORCH = "DiscoFusion op by op in PyTorch (channels outside the kernel's C % 32 == 0, 32 .. 384)"
 V2V = "v2v_warp_split + conv3x3_sp + v2v_aggregate + conv3x3_sp + v2v_gate per iteration, one launch per stage over all (receiver, sender) pairs"
 V2V_TORCH = "V2VNetFusion op by op in PyTorch"
+V2X = ("v2x_agent_attention per encoder layer: LayerNorm + folded q | k' | v' projection + softmax over the agents + output projection + residual in two launches; "
+       "pyramid window attention, split attention and feed-forward as torch ops on the device (library kernels)")
+V2X_TORCH = "V2XViTFusion op by op in PyTorch"
+V2X_ATT, V2X_UNREAD, V2X_LIBRARY = "v2x_agent_attention", "never read (every agent is of type 0; prior_feed has no caller)", ROCBLAS.split(" (")[0] + " (nn.Linear"
 STRIDED_SHRINK = MIOPEN + " (strided shrink-header convolution: library route)"
 SPLIT_OUT = ", SplitMap out"
 SPARSE_IN = ", sparse canvas in"
@@ -113,6 +117,17 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS, baselines: bool = False) -> Di
             what = (" (V2VNet: the warped-map and the ego columns as two C -> C convolutions)" if n.endswith("msg_cnn") else
                     " (V2VNet: update-gate rows of conv_gates stacked on conv_can, one convolution per GRU cell)")
             note(n, SP + what if ok else MIOPEN + " (V2VNetFusion op by op)", not ok)
+        elif isinstance(m, nn.Linear) and n.startswith("fusion_net.") and isinstance(model.fusion_net, V2XViTFusion):
+            ok = model.fusion_net.kernel_route(model.out_channel)
+            leaf = n.split(".")
+            if n.endswith("prior_feed") or (leaf[-2] in ("q_linears", "k_linears", "v_linears", "a_linears") and leaf[-1] != "0"):
+                note(n, V2X_UNREAD, False)
+            elif leaf[-2] in ("q_linears", "k_linears", "v_linears", "a_linears"):
+                part = "output projection" if leaf[-2] == "a_linears" else "one third of the folded q | k' | v' projection"
+                note(n, f"{V2X_ATT} ({part}, fp16 x 2 on the matrix cores)" if ok else V2X_LIBRARY + ", V2XViTFusion op by op)", not ok)
+            else:
+                block = "pyramid window attention" if ".pwmsa." in n else "split attention" if ".split_attn." in n else "feed-forward" if ".net." in n else "agent attention" if ".to_" in n else "time encoding"
+                note(n, V2X_LIBRARY + f", {block}: torch op on the device)", True)
         elif isinstance(m, nn.Conv2d) and n not in layers and "naive_compressor" not in n:
             if tuple(m.kernel_size) == (1, 1) and n.endswith("_head"):
                 ok = detector.heads_route(model, terms).pointwise
@@ -148,6 +163,13 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS, baselines: bool = False) -> Di
             why = ("GRU kernels other than 3 x 3" if not k3 else f"{model.out_channel} channels outside C % 64 == 0, C <= 512" if model.out_channel % 64 or model.out_channel > 512
                    or model.out_channel != f.msg_cnn.out_channels else "the SplitMap arithmetic (fp16 x 2) is not in force")
             fusion = V2V_TORCH + f" ({why})"
+            fallbacks.append("fusion")
+    elif isinstance(getattr(model, "fusion_net", None), V2XViTFusion):         # ONE single-scale module on the shrunk map
+        f = model.fusion_net
+        if f.kernel_route(model.out_channel):
+            fusion = V2X
+        else:
+            fusion = V2X_TORCH + f" ({f.kernel_shape_reason(model.out_channel) or 'training mode or force_torch'})"
             fallbacks.append("fusion")
     elif isinstance(getattr(model, "fusion_net", None), (detector.MaxFusion, detector.AttFusion)):      # point_pillar_baseline: ONE module, the NCHW kernel
         fusion = "warp_fuse: one launch (NCHW, LDS-staged patches)"

@@ -364,3 +364,32 @@ def v2v_parameters_(module: torch.nn.Module, seed: int = 0, input_scale: float =
             else:                                                                        # mlp.weight
                 v = torch.randn(shape, generator=g) * (1.0 / t[0].numel()) ** 0.5
             t.copy_(v.to(t.dtype))
+
+
+def v2xvit_parameters_(module: torch.nn.Module, seed: int = 0) -> None:
+    """Test weights for a ``V2XViTFusion`` (this package's or the reference's: keyed by ``state_dict`` name) under which attention is neither uniform nor saturated
+    and every block moves the output.  Freshly initialised (PyTorch's 1 / sqrt(3 fan-in) linears, xavier relations) the agent attention's scores are a few hundredths
+    and its softmax is uniform to three digits.  Here every linear has unit gain over its fan-in (LayerNorm hands it unit-variance tokens, so queries and keys are of
+    order one per channel), ``relation_att`` / ``relation_msg`` unit gain over ``dim_head`` (scores of order one after the 1 / sqrt(dim_head) scale), LayerNorm scales
+    in (0.6, 1.4) with small shifts, positional tables of standard deviation 0.5, small biases.  The sinusoid table of ``RTE`` is left as constructed."""
+    import zlib
+    sd = module.state_dict()
+    with torch.no_grad():
+        for name in sorted(sd.keys()):
+            t = sd[name]
+            if not t.is_floating_point() or name.endswith("emb.emb.weight"):
+                continue
+            g = torch.Generator().manual_seed((zlib.crc32(name.encode()) + seed) & 0x7FFFFFFF)
+            shape = tuple(t.shape)
+            leaf = name.rsplit(".", 2)[-2] if "." in name else ""
+            if "relation_" in name:
+                v = torch.randn(shape, generator=g) * (1.0 / t.shape[-1]) ** 0.5
+            elif name.endswith("pos_embedding"):
+                v = torch.randn(shape, generator=g) * 0.5
+            elif leaf in ("norm", "bn1") and name.endswith("weight"):
+                v = torch.rand(shape, generator=g) * 0.8 + 0.6
+            elif name.endswith("bias"):
+                v = (torch.rand(shape, generator=g) - 0.5) * 0.2
+            else:
+                v = torch.randn(shape, generator=g) * (1.0 / t.shape[-1]) ** 0.5
+            t.copy_(v.to(t.dtype))
