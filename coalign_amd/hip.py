@@ -156,6 +156,15 @@ V2X_SIGNATURES = {
     "coalign_v2x_agent_attention": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P, P, c_size_t, P]),
 }
 
+# include/coalign_amd_v2x_window.h: the eighth extension header of ABI version 2 (product library): V2X-ViT's pyramid window attention with split attention --
+# LayerNorm + the folded 9C x C projection, attention inside the 4 / 8 / 16 windows, the branch weights, output projections and residual in three or four
+# launches (csrc/v2x_window.hip)
+V2X_WINDOW_SIGNATURES = {
+    "coalign_v2x_window_param_bytes": (c_size_t, [c_int, c_int]),
+    "coalign_v2x_window_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "coalign_v2x_window_attention": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P, P, c_size_t, P]),
+}
+
 _LAB_LIB = None
 
 
@@ -182,7 +191,7 @@ def lib() -> ctypes.CDLL:
             raise CoalignHipError(
                 f"{path} is missing and could not be built ({exc}); the CoAlign hot path has no CPU fallback") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **V2X_WINDOW_SIGNATURES}.items():
         fn = getattr(handle, name)  # AttributeError here == header / library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -206,7 +215,7 @@ def lab_lib() -> ctypes.CDLL:
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(f"{path} is missing and could not be built ({exc})") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **LAB_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **V2X_WINDOW_SIGNATURES, **LAB_SIGNATURES}.items():
         fn = getattr(handle, name)
         fn.restype = res
         fn.argtypes = args

@@ -1741,3 +1741,59 @@ def v2x_agent_attention(x: torch.Tensor, theta: Optional[torch.Tensor], params: 
         hip.check(L.coalign_v2x_agent_attention(_ptr(x), n, R, C, H, W, _ptr(th), _ptr(params), params.numel(), _ptr(out), _ptr(ws), ws_bytes, _stream()),
                   "coalign_v2x_agent_attention")
     return out
+
+
+# ---- V2X-ViT's pyramid window attention with split attention (include/coalign_amd_v2x_window.h, csrc/v2x_window.hip) -----------------------------------
+V2X_WINDOWS, V2X_WINDOW_DIM_HEADS = (4, 8, 16), (16, 32, 64)
+V2X_WINDOW_FUSE = {"naive": 0, "split_attn": 1}      # COALIGN_V2X_WINDOW_FUSE_*
+V2X_WINDOW_POS_FLOATS = 1236
+
+
+def v2x_window_shape_ok(channels: int, heads, dim_heads, windows, fuse: str, relative: bool, n_agents: int = 1, hw=None) -> bool:
+    """The shapes ``coalign_v2x_window_attention`` takes: windows (4, 8, 16) with dim_head (16, 32, 64) and heads C / dim_head, a relative position table, C = 256,
+    or C = 64 with ``naive``, 1 .. 8 maps, H and W (when given) multiples of 16."""
+    if tuple(windows) != V2X_WINDOWS or tuple(dim_heads) != V2X_WINDOW_DIM_HEADS or tuple(heads) != tuple(channels // d for d in V2X_WINDOW_DIM_HEADS):
+        return False
+    if not relative or fuse not in V2X_WINDOW_FUSE or not (channels == 256 or (channels == 64 and fuse == "naive")) or not 1 <= n_agents <= 8:
+        return False
+    return hw is None or (int(hw[0]) > 0 and int(hw[1]) > 0 and int(hw[0]) % 16 == 0 and int(hw[1]) % 16 == 0)
+
+
+def pack_v2x_window_weights(wqkv: torch.Tensor, bqkv: torch.Tensor, wout: torch.Tensor, bout: torch.Tensor, pos: Sequence[torch.Tensor], split=None) -> Optional[torch.Tensor]:
+    """The folded window-attention layer (``v2xvit.folded_window_attention``: wqkv [9C, C], bqkv [9C], wout [3, C, C], bout [3, C], pos = the three position tables;
+    ``split`` = (fc1.weight, bn1.weight, bn1.bias, fc2.weight) of the split attention or None for ``naive``) -> the parameter image of
+    ``coalign_v2x_window_attention`` (layout: the header's (14a)), a uint8 tensor on the weights' device; None when a weight of the matrix layers lies outside the
+    fp16 range (its sp16 pair would saturate)."""
+    wqkv, wout = wqkv.detach().float(), wout.detach().float()
+    C = wout.shape[-1]
+    if tuple(wqkv.shape) != (9 * C, C) or tuple(wout.shape) != (3, C, C) or not (C == 256 or (C == 64 and split is None)) or [tuple(p.shape) for p in pos] != [(7, 7), (15, 15), (31, 31)]:
+        raise ValueError("pack_v2x_window_weights: wqkv [9C, C], wout [3, C, C], tables 7 x 7, 15 x 15, 31 x 31, C = 256 or (naive) 64")
+    if not bool(torch.isfinite(wqkv).all() and torch.isfinite(wout).all()) or max(float(wqkv.abs().max()), float(wout.abs().max())) > 65504.0:
+        return None
+    floats = [bqkv.detach().float().reshape(-1), bout.detach().float().reshape(-1)] + [p.detach().float().reshape(-1) for p in pos] + [wqkv.new_zeros(1)]
+    if split is not None:
+        fc1, g, b, fc2 = (t.detach().float() for t in split)
+        floats += [wout.transpose(1, 2).reshape(-1), fc1.t().reshape(-1), g.reshape(-1), b.reshape(-1), fc2.t().reshape(-1)]
+    img = torch.cat([_disco_operand_image(wqkv)] + [_disco_operand_image(w) for w in wout] + [torch.cat(floats).contiguous().view(torch.uint8)])
+    assert img.numel() == (C // 16) * (12 * C // 32) * 2048 + (12 * C + V2X_WINDOW_POS_FLOATS) * 4 + (0 if split is None else (7 * C * C + 2 * C) * 4)
+    return img.contiguous()
+
+
+@_device_op
+def v2x_window_attention(x: torch.Tensor, params: torch.Tensor, fuse: str) -> torch.Tensor:
+    """x + PyramidWindowAttention(LayerNorm(x)) for the maps of ONE frame, every map on its own (``coalign_v2x_window_attention``): x [n <= 8, H, W, C] float32
+    contiguous, params from ``pack_v2x_window_weights``, ``fuse`` "naive" or "split_attn" -> [n, H, W, C] float32."""
+    _need_gpu(x, params)
+    L = hip.lib()
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("v2x_window_attention needs a contiguous float32 map [n, H, W, C]")
+    n, H, W, C = x.shape
+    if fuse not in V2X_WINDOW_FUSE or not v2x_window_shape_ok(C, [C // d for d in V2X_WINDOW_DIM_HEADS], V2X_WINDOW_DIM_HEADS, V2X_WINDOWS, fuse, True, n, (H, W)):
+        raise ValueError("v2x_window_attention: C = 256 or (naive) 64, 1 .. 8 maps, H and W multiples of 16")
+    ws_bytes = int(L.coalign_v2x_window_workspace_bytes(n, C, H, W))
+    ws = torch.empty(max(ws_bytes, 16) // 4, dtype=torch.float32, device=x.device)
+    out = torch.empty((n, H, W, C), dtype=torch.float32, device=x.device)
+    with _Timed("v2x_window_attention"):
+        hip.check(L.coalign_v2x_window_attention(_ptr(x), n, C, H, W, V2X_WINDOW_FUSE[fuse], _ptr(params), params.numel(), _ptr(out), _ptr(ws), ws_bytes, _stream()),
+                  "coalign_v2x_window_attention")
+    return out

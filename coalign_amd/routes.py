@@ -3,7 +3,7 @@
 The detector picks its kernels per layer at run time; a layer whose shape a hand-written kernel does not take falls back to MIOpen / the per-scale NCHW fusion kernel /
 the fp32 VALU encoder -- correct, slower, and until round 3 silent.  ``plan(hypes)`` builds the model of a hypes dictionary, asks every module the decision function its
 ``forward`` dispatches on (``backbone.conv3x3_route`` / ``pointwise_split``, ``BasicBlock.route``, ``DoubleConv.on_split_maps``, the decode mixin's ``heads_pointwise`` /
-``heads_write_split``, ``NaiveCompressor.split_widths``, ``detector.heads_route`` / ``sparse_canvas_route`` / ``compressor_sparse_route`` / ``fusion_route``, ``DiscoFusion.kernel_route``, ``V2VNetFusion.kernel_route``, ``V2XViTFusion.kernel_route``, ``PillarVFE.matrix_core_ok``) with the arithmetic
+``heads_write_split``, ``NaiveCompressor.split_widths``, ``detector.heads_route`` / ``sparse_canvas_route`` / ``compressor_sparse_route`` / ``fusion_route``, ``DiscoFusion.kernel_route``, ``V2VNetFusion.kernel_route``, ``V2XViTFusion.kernel_route`` / ``window_kernel_reason``, ``PillarVFE.matrix_core_ok``) with the arithmetic
 mode passed in, and words the answers -- this module holds no shape rule of its own -- so that a yaml that would leave the fast path shows up in a CPU test
 (tests/test_host_cpu.py walks the reference's ``hypes_yaml/**/pointpillar*.yaml`` with it) instead of in a profile.
 The line of the merged 1x1 heads names the kernel that reads a float32 map (pointwise within its Cin limit, else rocBLAS, listed as a fallback): where a one-layer shrink header
@@ -35,6 +35,10 @@ V2V = "v2v_warp_split + conv3x3_sp + v2v_aggregate + conv3x3_sp + v2v_gate per i
 V2V_TORCH = "V2VNetFusion op by op in PyTorch"
 V2X = ("v2x_agent_attention per encoder layer: LayerNorm + folded q | k' | v' projection + softmax over the agents + output projection + residual in two launches; "
        "pyramid window attention, split attention and feed-forward as torch ops on the device (library kernels)")
+V2X_WINDOW = ("v2x_agent_attention + v2x_window_attention per encoder layer: the agent attention in two launches, the pyramid window attention with its split attention "
+              "(LayerNorm + folded 9C x C projection, attention inside the 4 / 8 / 16 windows, branch weights, output projections + residual) in three or four; "
+              "the feed-forward is still torch ops on the device (library kernels)")
+V2X_WIN = "v2x_window_attention"
 V2X_TORCH = "V2XViTFusion op by op in PyTorch"
 V2X_ATT, V2X_UNREAD, V2X_LIBRARY = "v2x_agent_attention", "never read (every agent is of type 0; prior_feed has no caller)", ROCBLAS.split(" (")[0] + " (nn.Linear"
 STRIDED_SHRINK = MIOPEN + " (strided shrink-header convolution: library route)"
@@ -125,6 +129,10 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS, baselines: bool = False) -> Di
             elif leaf[-2] in ("q_linears", "k_linears", "v_linears", "a_linears"):
                 part = "output projection" if leaf[-2] == "a_linears" else "one third of the folded q | k' | v' projection"
                 note(n, f"{V2X_ATT} ({part}, fp16 x 2 on the matrix cores)" if ok else V2X_LIBRARY + ", V2XViTFusion op by op)", not ok)
+            elif ok and (".pwmsa." in n or ".split_attn." in n) and isinstance(m, nn.Linear) and model.fusion_net.window_kernel_reason(model.out_channel) is None:
+                part = ("one third of the folded 9C x C projection, fp16 x 2 on the matrix cores" if leaf[-1] == "to_qkv" else "output projection, fp16 x 2 on the matrix cores"
+                        if ".to_out." in n else "split attention's branch weights, fp32")
+                note(n, f"{V2X_WIN} ({part})", False)
             else:
                 block = "pyramid window attention" if ".pwmsa." in n else "split attention" if ".split_attn." in n else "feed-forward" if ".net." in n else "agent attention" if ".to_" in n else "time encoding"
                 note(n, V2X_LIBRARY + f", {block}: torch op on the device)", True)
@@ -167,7 +175,7 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS, baselines: bool = False) -> Di
     elif isinstance(getattr(model, "fusion_net", None), V2XViTFusion):         # ONE single-scale module on the shrunk map
         f = model.fusion_net
         if f.kernel_route(model.out_channel):
-            fusion = V2X
+            fusion = V2X_WINDOW if f.window_kernel_reason(model.out_channel) is None else V2X
         else:
             fusion = V2X_TORCH + f" ({f.kernel_shape_reason(model.out_channel) or 'training mode or force_torch'})"
             fallbacks.append("fusion")

@@ -15,11 +15,13 @@ What fusion_in_one.py fixes for every call, and what follows from it:
     computed once per map shape on the CPU as the reference's CPU run does, and cached); the resample is skipped only at a shape where the positions ARE the grid.
 
 On the GPU in eval mode (``kernel_route``) the agent attention of every layer runs on ``ops.v2x_agent_attention``; the pyramid window attention, split attention
-and feed-forward stay torch ops on the device (library kernels).
+and feed-forward stay torch ops on the device (library kernels) -- unless ``window_kernels`` is set (off by default), which puts the pyramid window attention with
+its split attention on ``ops.v2x_window_attention`` where ``window_kernel_reason`` allows it.
 """
 from __future__ import annotations
 
 import math
+import os
 from typing import List, Optional, Sequence
 
 import torch
@@ -29,6 +31,10 @@ import torch.nn.functional as F
 from . import ops
 from .backbone import _cache_of
 from .encoder import host_ints
+
+# Measurement switch: the pyramid window attention and split attention of the kernel route on ``ops.v2x_window_attention`` (csrc/v2x_window.hip) instead of torch
+# ops.  Off by default; copied into ``V2XViTFusion.window_kernels`` at construction (tests and tools set the attribute).
+V2X_WINDOW_KERNELS = os.environ.get("COALIGN_V2X_WINDOW", "0") != "0"
 
 
 def _warp_torch(src: torch.Tensor, M: torch.Tensor) -> torch.Tensor:
@@ -161,6 +167,57 @@ def agent_attention_reduced(x: torch.Tensor, R: int, norm: nn.LayerNorm, att: nn
     p = torch.einsum("ihwmc,jhwmc->hwmij", q, kv[:, :, :, 0]).softmax(dim=-1)
     o = torch.einsum("hwmij,jhwmc->ihwmc", p, kv[:, :, :, 1]).reshape(R, H, W, inner)
     return x[:R] + F.linear(o, wa, ba)
+
+
+def folded_window_attention(norm: nn.LayerNorm, pw: "PyramidWindowAttention"):
+    """One PreNorm(PyramidWindowAttention) layer with ONE projection, folded in float64: -> (wqkv [3BC, C], bqkv [3BC], wout [B, C, C], bout [B, C], pos = the B position
+    tables) in the parameters' dtype, B branches, with yhat = (x - mean) / sqrt(var + eps):
+        [q_0 | k_0 | v_0 | q_1 | ...] = wqkv yhat + bqkv,   o_b = softmax_j(q_i . k_j + pos_b[xj - xi + ws - 1][yj - yi + ws - 1]) v_j,   out_b = wout_b o_b + bout_b.
+    Exact identities: the bias-free ``to_qkv`` stacked, LayerNorm's gamma into the columns, beta as the bias W beta, each branch's scale into its query rows and bias."""
+    dt, d = norm.weight.dtype, torch.float64
+    ws, bs = [], []
+    for att in pw.pwmsa:
+        w = att.to_qkv.weight.to(d).clone()
+        inner = w.shape[0] // 3
+        w[:inner] *= att.scale
+        bs.append(w @ norm.bias.to(d))
+        ws.append(w * norm.weight.to(d)[None, :])
+    wout = torch.stack([att.to_out[0].weight.to(d) for att in pw.pwmsa])
+    bout = torch.stack([att.to_out[0].bias.to(d) for att in pw.pwmsa])
+    return (torch.cat(ws).to(dt).contiguous(), torch.cat(bs).to(dt).contiguous(), wout.to(dt).contiguous(), bout.to(dt).contiguous(),
+            [att.pos_embedding.detach().to(dt).contiguous() for att in pw.pwmsa])
+
+
+def window_attention_reduced(x: torch.Tensor, norm: nn.LayerNorm, pw: "PyramidWindowAttention") -> torch.Tensor:
+    """x [n, H, W, C] (one frame's maps) -> x + PyramidWindowAttention(LayerNorm(x)) on the folded projection, in the schedule of ``ops.v2x_window_attention`` in torch
+    ops (eval mode: no dropout; any dtype, any device): one projection, the attention inside the windows with the position table indexed directly, the split
+    attention's branch weights from the per-map channel means of the attention outputs (the pooled sum is linear in them), one weighted sum of the output projections."""
+    if any(not att.relative_pos_embedding for att in pw.pwmsa) or pw.fuse_mehod not in ("naive", "split_attn"):
+        raise NotImplementedError("window_attention_reduced: relative position tables, fusion_method naive or split_attn")
+    wqkv, bqkv, wout, bout, pos = _cache_of(pw, "_coalign_v2x_window_fold").get(list(norm.parameters()) + list(pw.parameters()), lambda: folded_window_attention(norm, pw))
+    n, H, W, C = x.shape
+    qkv = F.linear(F.layer_norm(x, (C,), None, None, norm.eps), wqkv, bqkv)
+    outs, off = [], 0
+    for att, table in zip(pw.pwmsa, pos):
+        ws, m = att.window_size, att.heads
+        inner = att.to_out[0].in_features
+        nh, nw = H // ws, W // ws
+        q, k, v = (qkv[..., off + i * inner:off + (i + 1) * inner].reshape(n, nh, ws, nw, ws, m, -1).permute(0, 1, 3, 5, 2, 4, 6).reshape(n, nh, nw, m, ws * ws, -1) for i in range(3))
+        off += 3 * inner
+        r = torch.arange(ws, device=x.device)
+        rows = (r[None, :] - r[:, None] + ws - 1)                                               # [i, j] -> j - i + ws - 1
+        bias = table[rows[:, None, :, None], rows[None, :, None, :]].reshape(ws * ws, ws * ws)  # [(xi, yi), (xj, yj)]
+        p = (torch.einsum("nhwmic,nhwmjc->nhwmij", q, k) + bias).softmax(dim=-1)
+        o = torch.einsum("nhwmij,nhwmjc->nhwmic", p, v).reshape(n, nh, nw, m, ws, ws, -1).permute(0, 1, 4, 2, 5, 3, 6).reshape(n, H, W, inner)
+        outs.append(o)
+    B = len(outs)
+    if pw.fuse_mehod == "naive":
+        a = x.new_full((n, B, C), 1.0 / B)
+    else:
+        sa = pw.split_attn
+        gap = sum(F.linear(o.mean(dim=(1, 2)), wout[b], bout[b]) for b, o in enumerate(outs))      # [n, C]
+        a = sa.fc2(sa.act1(sa.bn1(sa.fc1(gap)))).reshape(n, B, -1).softmax(dim=1)
+    return x + sum(a[:, b, None, None, :] * F.linear(o, wout[b], bout[b]) for b, o in enumerate(outs))
 
 
 def get_relative_distances(window_size: int) -> torch.Tensor:
@@ -456,6 +513,7 @@ class V2XViTFusion(nn.Module):
         super().__init__()
         self.fusion_net = V2XTransformer(args["transformer"])
         self.force_torch = False      # measurement / test aid: take the op-by-op route whatever the device
+        self.window_kernels = V2X_WINDOW_KERNELS      # the kernel route's window attention on ops.v2x_window_attention (off by default)
 
     # ---- the decision --------------------------------------------------------------------------------------------------------------------------------------
     def _attentions(self):
@@ -470,6 +528,27 @@ class V2XViTFusion(nn.Module):
                 return f"dim {channels} = {att.heads} heads x {att.dim_head} outside the kernel's 8 x 32 | 2 x 32, or more than 8 agents"
             if att.q_linears[0].in_features != channels:
                 return f"the map's {channels} channels are not the transformer's dim {att.q_linears[0].in_features}"
+        return None
+
+    def _windows(self):
+        return [blk[1].fn for layer in self.fusion_net.encoder.layers for blk in layer[0].layers]
+
+    def window_kernel_reason(self, channels: int, hw=None) -> Optional[str]:
+        """None when ``ops.v2x_window_attention`` takes every pyramid window attention of the kernel route at ``channels`` (and the map shape ``hw``, when given);
+        else why not."""
+        if not self.window_kernels:
+            return "the window kernels are switched off (COALIGN_V2X_WINDOW / window_kernels)"
+        for pw in self._windows():
+            if pw.fuse_mehod not in ops.V2X_WINDOW_FUSE:
+                return f"fusion_method {pw.fuse_mehod} has no kernel"
+            if any(not att.relative_pos_embedding for att in pw.pwmsa):
+                return "relative_pos_embedding: false has no kernel"
+            heads, dim_heads, windows = [att.heads for att in pw.pwmsa], [att.to_out[0].in_features // att.heads for att in pw.pwmsa], [att.window_size for att in pw.pwmsa]
+            if pw.pwmsa[0].to_qkv.in_features != channels or not ops.v2x_window_shape_ok(channels, heads, dim_heads, windows, pw.fuse_mehod, True):
+                return (f"windows {windows} x heads {heads} x dim_head {dim_heads} on {channels} channels ({pw.fuse_mehod}) outside the kernel's 4 / 8 / 16 windows of "
+                        f"16 / 32 / 64 channels a head on 256 channels (64: naive only)")
+        if hw is not None and (int(hw[0]) % 16 or int(hw[1]) % 16):
+            return f"a {int(hw[0])} x {int(hw[1])} map: H and W must be multiples of 16"
         return None
 
     def kernel_route(self, channels: int, n_agents: int = 1, hw=None) -> bool:
@@ -535,6 +614,17 @@ class V2XViTFusion(nn.Module):
             return (None if any(i is None for i in imgs) else imgs,)
         return _cache_of(self, "_coalign_v2x_images").get(self, build)[0]
 
+    def packed_windows(self) -> Optional[List[torch.Tensor]]:
+        """The parameter image of every window-attention layer (``ops.pack_v2x_window_weights`` of ``folded_window_attention``), cached until a parameter changes; None
+        when a folded weight lies outside the fp16 range."""
+        def build():
+            imgs = []
+            for _, _, _, pw, _ in self._schedule(1):
+                sa = pw.fn.split_attn if pw.fn.fuse_mehod == "split_attn" else None
+                imgs.append(ops.pack_v2x_window_weights(*folded_window_attention(pw.norm, pw.fn), split=None if sa is None else (sa.fc1.weight, sa.bn1.weight, sa.bn1.bias, sa.fc2.weight)))
+            return (None if any(i is None for i in imgs) else imgs,)
+        return _cache_of(self, "_coalign_v2x_window_images").get(self, build)[0]
+
     def forward_kernels(self, xx: torch.Tensor, groups: Sequence[int], normalized_affine_matrix: torch.Tensor, images: List[torch.Tensor]) -> torch.Tensor:
         enc = self.fusion_net.encoder
         _, C, H, W = xx.shape
@@ -543,6 +633,7 @@ class V2XViTFusion(nn.Module):
             xx = xx.contiguous(memory_format=torch.channels_last)             # (the shrink header's conv3x3_sp writes channels-last: no copy on the detector's route)
             if not ops.nhwc_memory(xx):
                 xx = xx.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+        wimages = self.packed_windows() if self.window_kernel_reason(C, (H, W)) is None else None      # (one decision per call)
         outs, off = [], 0
         for b, n in enumerate(groups):
             xb = xx[off:off + n]
@@ -555,10 +646,13 @@ class V2XViTFusion(nn.Module):
                 if enc.use_RTE:
                     xb = enc.rte(xb.permute(0, 2, 3, 1)).permute(0, 3, 1, 2)
                 xb, th = torch.cat([xb[:1], enc.sttf.resample(xb[1:])], dim=0).permute(0, 2, 3, 1).contiguous(), None
-            for img, (norm, att, R, pw, ff) in zip(images, self._schedule(n)):
+            for k, (img, (norm, att, R, pw, ff)) in enumerate(zip(images, self._schedule(n))):
                 xb = ops.v2x_agent_attention(xb.contiguous(), th, img, receivers=R)
                 th = None
-                xb = xb + pw(xb.unsqueeze(0)).squeeze(0)
+                if wimages is not None:
+                    xb = ops.v2x_window_attention(xb, wimages[k], pw.fn.fuse_mehod)
+                else:
+                    xb = xb + pw(xb.unsqueeze(0)).squeeze(0)
                 if ff is not None:
                     xb = xb + ff(xb)
             outs.append(xb[:1])
