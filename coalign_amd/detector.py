@@ -21,7 +21,7 @@ from . import backbone as _bb
 from . import ops
 from .backbone import BaseBEVBackbone, BasicBlock, DownsampleConv, NaiveCompressor, ResNetBEVBackbone, _cache_of, _fast_ok
 from .encoder import PillarVFE, PointPillarScatter, host_ints
-from .fusion import AttFusion, DiscoFusion, MaxFusion, V2VNetFusion, V2XViTFusion, fuse_multiscale
+from .fusion import AttFusion, DiscoFusion, MaxFusion, V2VNetFusion, V2XViTFusion, When2comFusion, fuse_multiscale
 from .pose import normalize_pairwise_tfm
 
 # Round 4: PillarVFE + PointPillarScatter as one launch with a sparse canvas (csrc/pillar_sparse.hip) feeding the first ResNet block directly.
@@ -362,10 +362,10 @@ class PointPillarDiscoNet(nn.Module):
 
 class PointPillarBaseline(nn.Module):
     """The single-scale collaborative baselines on PointPillars (opencood/models/point_pillar_baseline.py:17-138: F-Cooper, self-attention, DiscoNet without
-    distillation, V2VNet): pillar encoder, ``BaseBEVBackbone`` or ``ResNetBEVBackbone``, shrink header, optional ``NaiveCompressor``, ONE fusion module on the
-    shrunk map chosen by ``fusion_method`` (max | att | disconet | v2vnet | v2xvit), 1 x 1 heads.  Same constructor keys, ``state_dict`` names and outputs as the
-    reference; ``v2xvit`` reads the ``v2xvit`` section (without one it is refused with ``NotImplementedError``); ``when2comm`` (and anything else) is refused at
-    construction -- the reference would build a model without ``fusion_net`` and fail in ``forward``.
+    distillation, V2VNet, V2X-ViT, When2com): pillar encoder, ``BaseBEVBackbone`` or ``ResNetBEVBackbone``, shrink header, optional ``NaiveCompressor``, ONE fusion
+    module on the shrunk map chosen by ``fusion_method`` (max | att | disconet | v2vnet | v2xvit | when2comm), 1 x 1 heads.  Same constructor keys, ``state_dict``
+    names and outputs as the reference; ``v2xvit`` reads the ``v2xvit`` section and ``when2comm`` the ``when2comm`` section (without its section either is refused
+    with ``NotImplementedError``); any other name is refused at construction -- the reference would build a model without ``fusion_net`` and fail in ``forward``.
     ``encode`` / ``fuse_and_head`` and the two ``accepts_*`` flags follow ``PointPillarDiscoNet``'s contracts: ``FramePipeline`` and the inference drivers run it
     unchanged.  The fusion receives the whole [L, L] affine matrix (V2VNet reads every receiver's row)."""
 
@@ -390,8 +390,12 @@ class PointPillarBaseline(nn.Module):
             if "v2xvit" not in args:
                 raise NotImplementedError("fusion_method 'v2xvit' of point_pillar_baseline needs the model's 'v2xvit' section (the transformer's arguments), which this config lacks")
             self.fusion_net = V2XViTFusion(args["v2xvit"])
+        elif method == "when2comm":
+            if "when2comm" not in args:
+                raise NotImplementedError("fusion_method 'when2comm' of point_pillar_baseline needs the model's 'when2comm' section (in_channels, H, W, query_size, key_size), which this config lacks")
+            self.fusion_net = When2comFusion(args["when2comm"])
         else:
-            raise NotImplementedError(f"fusion_method '{method}' of point_pillar_baseline is not built here (max | att | disconet | v2vnet | v2xvit)")
+            raise NotImplementedError(f"fusion_method '{method}' of point_pillar_baseline is not built here (max | att | disconet | v2vnet | v2xvit | when2comm)")
         self.out_channel = sum(bb["num_upsample_filter"])
         self.shrink_flag = "shrink_header" in args
         if self.shrink_flag:

@@ -165,6 +165,14 @@ V2X_WINDOW_SIGNATURES = {
     "coalign_v2x_window_attention": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P, P, c_size_t, P]),
 }
 
+# include/coalign_amd_w2c.h: the ninth extension header of ABI version 2 (product library): When2com's handshake fusion after its convolutions -- the pooled key /
+# query heads with the softmax over the agents in two launches, the warp-and-weighted-sum of the agents' maps in one (csrc/w2c_fuse.hip)
+W2C_SIGNATURES = {
+    "coalign_w2c_workspace_bytes": (c_size_t, []),
+    "coalign_w2c_score": (c_int, [P, c_int, P, c_int, c_int, c_int, P, c_size_t, P, P, P, c_size_t, P]),
+    "coalign_w2c_fuse": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P]),
+}
+
 _LAB_LIB = None
 
 
@@ -191,7 +199,7 @@ def lib() -> ctypes.CDLL:
             raise CoalignHipError(
                 f"{path} is missing and could not be built ({exc}); the CoAlign hot path has no CPU fallback") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **V2X_WINDOW_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **V2X_WINDOW_SIGNATURES, **W2C_SIGNATURES}.items():
         fn = getattr(handle, name)  # AttributeError here == header / library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -215,7 +223,7 @@ def lab_lib() -> ctypes.CDLL:
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(f"{path} is missing and could not be built ({exc})") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **V2X_WINDOW_SIGNATURES, **LAB_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **V2X_WINDOW_SIGNATURES, **W2C_SIGNATURES, **LAB_SIGNATURES}.items():
         fn = getattr(handle, name)
         fn.restype = res
         fn.argtypes = args

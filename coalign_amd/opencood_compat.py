@@ -34,7 +34,7 @@ _EXPORTS: Dict[str, Dict[str, object]] = {
     "opencood.models.sub_modules.downsample_conv": {"DownsampleConv": backbone.DownsampleConv, "DoubleConv": backbone.DoubleConv},
     "opencood.models.sub_modules.naive_compress": {"NaiveCompressor": backbone.NaiveCompressor},
     "opencood.models.sub_modules.torch_transformation_utils": {"warp_affine_simple": fusion.warp_affine_simple},
-    "opencood.models.fuse_modules.fusion_in_one": {"AttFusion": fusion.AttFusion, "MaxFusion": fusion.MaxFusion, "DiscoFusion": fusion.DiscoFusion, "V2VNetFusion": fusion.V2VNetFusion, "V2XViTFusion": fusion.V2XViTFusion,
+    "opencood.models.fuse_modules.fusion_in_one": {"AttFusion": fusion.AttFusion, "MaxFusion": fusion.MaxFusion, "DiscoFusion": fusion.DiscoFusion, "V2VNetFusion": fusion.V2VNetFusion, "V2XViTFusion": fusion.V2XViTFusion, "When2commFusion": fusion.When2comFusion,
                                                    "regroup": fusion.regroup, "warp_feature": fusion.warp_feature},
     "opencood.models.fuse_modules.fuse_utils": {"regroup": fusion.regroup},
     "opencood.utils.transformation_utils": {"normalize_pairwise_tfm": pose.normalize_pairwise_tfm, "x_to_world": pose.x_to_world,

@@ -1797,3 +1797,82 @@ def v2x_window_attention(x: torch.Tensor, params: torch.Tensor, fuse: str) -> to
         hip.check(L.coalign_v2x_window_attention(_ptr(x), n, C, H, W, V2X_WINDOW_FUSE[fuse], _ptr(params), params.numel(), _ptr(out), _ptr(ws), ws_bytes, _stream()),
                   "coalign_v2x_window_attention")
     return out
+
+
+# ---- When2com's handshake fusion after its convolutions (include/coalign_amd_w2c.h, csrc/w2c_fuse.hip) ---------------------------------------------------
+W2C_CHANNELS, W2C_FEAT, W2C_HIDDEN1, W2C_HIDDEN2, W2C_ATT = 128, 4480, 256, 128, 128      # COALIGN_W2C_*
+W2C_PARAM_FLOATS = 2 * W2C_HIDDEN1 * W2C_FEAT + 2 * W2C_HIDDEN1 + 2 * (W2C_HIDDEN1 * W2C_HIDDEN2 + W2C_HIDDEN2) + 2 * (W2C_HIDDEN2 * W2C_ATT + W2C_ATT)
+
+
+def w2c_shape_ok(channels: int, n_agents: int) -> bool:
+    """The shapes ``coalign_w2c_fuse`` (and ``v2v_warp_split`` ahead of it) takes: C % 16 == 0, 1 .. 8 agents (any H, W)."""
+    return channels > 0 and channels % 16 == 0 and 1 <= n_agents <= 8
+
+
+def pack_w2c_weights(key_net, query_net) -> torch.Tensor:
+    """The parameter image of ``coalign_w2c_score`` (layout: the header's COALIGN_W2C_PARAM_FLOATS) from two tuples ``(W1 [256, 4480], b1, W2 [128, 256], b2,
+    T [128, 128], tb)`` -- fc.0, fc.2 and the folded tail of the key and the query net -- as one float32 tensor on the weights' device."""
+    shapes = ((W2C_HIDDEN1, W2C_FEAT), (W2C_HIDDEN1,), (W2C_HIDDEN2, W2C_HIDDEN1), (W2C_HIDDEN2,), (W2C_ATT, W2C_HIDDEN2), (W2C_ATT,))
+    nets = []
+    for net in (key_net, query_net):
+        if len(net) != 6 or any(tuple(t.shape) != s for t, s in zip(net, shapes)):
+            raise ValueError("pack_w2c_weights: (W1 [256, 4480], b1 [256], W2 [128, 256], b2 [128], T [128, 128], tb [128]) per net")
+        nets.append([t.detach().float() for t in net])
+    k, q = nets
+    parts = [k[0], q[0], k[1], q[1], k[2].t(), k[3], q[2].t(), q[3], k[4].t(), k[5], q[4].t(), q[5]]
+    img = torch.cat([p.contiguous().reshape(-1) for p in parts]).contiguous()
+    assert img.numel() == W2C_PARAM_FLOATS
+    return img
+
+
+_W2C_WS = {}
+
+
+def _w2c_workspace(device) -> torch.Tensor:
+    """The partial-sum workspace of ``coalign_w2c_score`` for the current stream of ``device`` (launches on a stream are ordered; nothing to initialise)."""
+    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+    ws = _W2C_WS.get(key)
+    if ws is None:
+        ws = _W2C_WS[key] = torch.empty(hip.lib().coalign_w2c_workspace_bytes(), dtype=torch.uint8, device=device)
+    return ws
+
+
+@_device_op
+def w2c_score(key: "SplitMap", query: "SplitMap", params: torch.Tensor, return_logits: bool = False):
+    """The attention weights of ONE frame (``coalign_w2c_score``): key [n <= 8, 128 or more, h, w] (the key net's conv1 output in its first 128 channels) and query
+    [1, 128, h, w] SplitMaps, read in place -- of a stacked key | query convolution: the 256-channel map itself and ``SplitMap(map.data[:1, 8:])``; params from
+    ``pack_w2c_weights`` -> w [n] float32 on the device; ``return_logits`` (tests): (w, logits [n])."""
+    if not isinstance(key, SplitMap) or not isinstance(query, SplitMap):
+        raise TypeError("w2c_score reads SplitMaps")
+    _need_gpu(key.data, query.data, params)
+    n, C, h, w = key.shape
+    if C < W2C_CHANNELS or tuple(query.shape) != (1, W2C_CHANNELS, h, w) or not 1 <= n <= 8 or query.device != key.device:
+        raise ValueError("w2c_score: key [1 .. 8, >= 128, h, w], query [1, 128, h, w] on one device")
+    if params.dtype != torch.float32 or params.numel() != W2C_PARAM_FLOATS or not params.is_contiguous() or params.device != key.device:
+        raise ValueError("w2c_score: params is the float32 image of pack_w2c_weights on the maps' device")
+    out = torch.empty(n, dtype=torch.float32, device=key.device)
+    logits = torch.empty(n, dtype=torch.float32, device=key.device) if return_logits else None
+    ws = _w2c_workspace(key.device)
+    with _Timed("w2c_score"):
+        hip.check(hip.lib().coalign_w2c_score(_ptr(key.data), C, _ptr(query.data), n, h, w, _ptr(params), params.numel() * 4, _ptr(out), _ptr(logits), _ptr(ws), ws.numel(),
+                                              _stream()), "coalign_w2c_score")
+    return (out, logits) if return_logits else out
+
+
+@_device_op
+def w2c_fuse(x: torch.Tensor, theta: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+    """sum_j weights[j] * warp_affine_simple(x[j], theta[j]) of ONE frame in one launch (``coalign_w2c_fuse``): x [n <= 8, C, H, W] float32 channels-last, theta
+    [n, 2, 3], weights [n] float32 on the device -> [1, C, H, W] float32 channels-last."""
+    _need_gpu(x, theta, weights)
+    n, C, H, W = _nhwc_map(x, "w2c_fuse")
+    if not w2c_shape_ok(C, n):
+        raise ValueError("w2c_fuse: C % 16 == 0, 1 .. 8 agents")
+    th = theta.to(device=x.device, dtype=torch.float64).contiguous()
+    if tuple(th.shape) != (n, 2, 3):
+        raise ValueError("w2c_fuse: theta [n, 2, 3], one row per agent")
+    if weights.dtype != torch.float32 or tuple(weights.shape) != (n,) or not weights.is_contiguous() or weights.device != x.device:
+        raise ValueError("w2c_fuse: weights [n] float32 on the map's device")
+    out = _nhwc_empty(1, C, H, W, x.device)
+    with _Timed("w2c_fuse"):
+        hip.check(hip.lib().coalign_w2c_fuse(_ptr(x), n, C, H, W, _ptr(th), _ptr(weights), _ptr(out), _stream()), "coalign_w2c_fuse")
+    return out

@@ -3,7 +3,7 @@
 The detector picks its kernels per layer at run time; a layer whose shape a hand-written kernel does not take falls back to MIOpen / the per-scale NCHW fusion kernel /
 the fp32 VALU encoder -- correct, slower, and until round 3 silent.  ``plan(hypes)`` builds the model of a hypes dictionary, asks every module the decision function its
 ``forward`` dispatches on (``backbone.conv3x3_route`` / ``pointwise_split``, ``BasicBlock.route``, ``DoubleConv.on_split_maps``, the decode mixin's ``heads_pointwise`` /
-``heads_write_split``, ``NaiveCompressor.split_widths``, ``detector.heads_route`` / ``sparse_canvas_route`` / ``compressor_sparse_route`` / ``fusion_route``, ``DiscoFusion.kernel_route``, ``V2VNetFusion.kernel_route``, ``V2XViTFusion.kernel_route`` / ``window_kernel_reason``, ``PillarVFE.matrix_core_ok``) with the arithmetic
+``heads_write_split``, ``NaiveCompressor.split_widths``, ``detector.heads_route`` / ``sparse_canvas_route`` / ``compressor_sparse_route`` / ``fusion_route``, ``DiscoFusion.kernel_route``, ``V2VNetFusion.kernel_route``, ``V2XViTFusion.kernel_route`` / ``window_kernel_reason``, ``When2comFusion.kernel_route`` / ``kernel_shape_reason``, ``PillarVFE.matrix_core_ok``) with the arithmetic
 mode passed in, and words the answers -- this module holds no shape rule of its own -- so that a yaml that would leave the fast path shows up in a CPU test
 (tests/test_host_cpu.py walks the reference's ``hypes_yaml/**/pointpillar*.yaml`` with it) instead of in a profile.
 The line of the merged 1x1 heads names the kernel that reads a float32 map (pointwise within its Cin limit, else rocBLAS, listed as a fallback): where a one-layer shrink header
@@ -22,7 +22,7 @@ import torch.nn as nn
 from . import backbone as bb
 from . import detector
 from .detector import BASELINE_REGISTRY, MODEL_REGISTRY, build_model
-from .fusion import DiscoFusion, V2VNetFusion, V2XViTFusion
+from .fusion import DiscoFusion, V2VNetFusion, V2XViTFusion, When2comFusion
 
 EMU, F32, MIOPEN, ROCBLAS, POINTWISE = "conv3x3_emu (split 16-bit matrix cores)", "conv3x3 (fp32 matrix cores) / MIOpen by shape", "MIOpen", "rocBLAS (1x1 heads)", "pointwise"
 WINO = "conv3x3_wino (Winograd F(2x2,3x3), split-bf16 matrix cores)"
@@ -41,6 +41,11 @@ V2X_WINDOW = ("v2x_agent_attention + v2x_window_attention per encoder layer: the
 V2X_WIN = "v2x_window_attention"
 V2X_TORCH = "V2XViTFusion op by op in PyTorch"
 V2X_ATT, V2X_UNREAD, V2X_LIBRARY = "v2x_agent_attention", "never read (every agent is of type 0; prior_feed has no caller)", ROCBLAS.split(" (")[0] + " (nn.Linear"
+SP_S2 = "conv3x3_sp_s2 (SplitMap input and output, stride 2, fp16 x 2)"
+W2C = ("v2v_warp_split + conv3x3_sp x 3 + conv3x3_sp_s2 x 3 + w2c_score + w2c_fuse per frame: the warped maps as SplitMaps, policy_net4 and the stacked key | query block on "
+       "the SplitMap convolutions, the pooled heads with the softmax over the agents in two launches, warp and weighted sum in one; a one-agent frame is w2c_fuse alone")
+W2C_TORCH = "When2comFusion op by op in PyTorch"
+W2C_SCORE, W2C_UNREAD = "w2c_score", "never read (AdditiveAttentin.forward does not use linear_out)"
 STRIDED_SHRINK = MIOPEN + " (strided shrink-header convolution: library route)"
 SPLIT_OUT = ", SplitMap out"
 SPARSE_IN = ", sparse canvas in"
@@ -121,6 +126,21 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS, baselines: bool = False) -> Di
             what = (" (V2VNet: the warped-map and the ego columns as two C -> C convolutions)" if n.endswith("msg_cnn") else
                     " (V2VNet: update-gate rows of conv_gates stacked on conv_can, one convolution per GRU cell)")
             note(n, SP + what if ok else MIOPEN + " (V2VNetFusion op by op)", not ok)
+        elif isinstance(m, nn.Conv2d) and n.startswith("fusion_net.") and isinstance(model.fusion_net, When2comFusion):
+            ok = model.fusion_net.kernel_route(model.out_channel, 1, terms)
+            what = (" (When2com: stacked under key_net.conv1 in one launch; the ego's rows are read)" if n.startswith("fusion_net.query_net.") else
+                    " (When2com: query_net.conv1 stacked under it in one launch)" if n.startswith("fusion_net.key_net.") else " (When2com: every agent's warped map)")
+            note(n, (SP_S2 if m.stride[0] == 2 else SP + SPLIT_OUT) + what if ok else MIOPEN + " (When2comFusion op by op)", not ok)
+        elif isinstance(m, nn.Linear) and n.startswith("fusion_net.") and isinstance(model.fusion_net, When2comFusion):
+            ok = model.fusion_net.kernel_route(model.out_channel, 1, terms)
+            if n.endswith("attention_net.linear_out"):
+                note(n, W2C_UNREAD, False)
+            elif ok:
+                part = ("first layer, 4480 inputs spread over 256 workgroups" if n.endswith("fc.0") else "second layer" if n.endswith("fc.2") else
+                        "folded with the attention's linear into one 128 x 128 matrix" if n.endswith("fc.4") else "folded into the key / query net's last layer")
+                note(n, f"{W2C_SCORE} ({part}, fp32)", False)
+            else:
+                note(n, ROCBLAS.split(" (")[0] + " (nn.Linear, When2comFusion op by op)", True)
         elif isinstance(m, nn.Linear) and n.startswith("fusion_net.") and isinstance(model.fusion_net, V2XViTFusion):
             ok = model.fusion_net.kernel_route(model.out_channel)
             leaf = n.split(".")
@@ -178,6 +198,13 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS, baselines: bool = False) -> Di
             fusion = V2X_WINDOW if f.window_kernel_reason(model.out_channel) is None else V2X
         else:
             fusion = V2X_TORCH + f" ({f.kernel_shape_reason(model.out_channel) or 'training mode or force_torch'})"
+            fallbacks.append("fusion")
+    elif isinstance(getattr(model, "fusion_net", None), When2comFusion):       # ONE single-scale module on the shrunk map
+        f = model.fusion_net
+        if f.kernel_route(model.out_channel, 1, terms):
+            fusion = W2C
+        else:
+            fusion = W2C_TORCH + f" ({f.kernel_shape_reason(model.out_channel, 1, terms) or 'training mode or force_torch'})"
             fallbacks.append("fusion")
     elif isinstance(getattr(model, "fusion_net", None), (detector.MaxFusion, detector.AttFusion)):      # point_pillar_baseline: ONE module, the NCHW kernel
         fusion = "warp_fuse: one launch (NCHW, LDS-staged patches)"

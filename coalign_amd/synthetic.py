@@ -393,3 +393,42 @@ def v2xvit_parameters_(module: torch.nn.Module, seed: int = 0) -> None:
             else:
                 v = torch.randn(shape, generator=g) * (1.0 / t.shape[-1]) ** 0.5
             t.copy_(v.to(t.dtype))
+
+
+def when2com_parameters_(module: torch.nn.Module, seed: int = 0, input_scale: float = 1.0, attention_gain: float = 0.2) -> None:
+    """Test weights for a ``When2comFusion`` (this package's or the reference's ``When2commFusion``: keyed by ``state_dict`` name) under which the softmax over the
+    agents is neither uniform nor one-hot.  Freshly initialised the logits are a few thousandths, the weights 1 / n to four digits, and a comparison sees neither the
+    key nor the query head.  Here: He-scaled convolution and linear weights (the activation scale survives every ReLU), small biases, BatchNorm statistics and
+    affine away from their defaults, ``attention_net.linear_feat`` / ``linear_context`` scaled by ``attention_gain`` so that the logits -- a dot product of two
+    128-vectors -- are of order one (with a gain of 1 every softmax saturates), and ``query_key_net.conv1`` divided by ``input_scale`` so that maps of that magnitude
+    meet the same pre-activations.  The module has six million parameters, too many to store in a fixture: the draws come from numpy's legacy ``RandomState``, whose
+    stream is frozen, one generator per tensor seeded from its name, in float64 and cast to the tensor's dtype."""
+    import zlib
+
+    import numpy as np
+    sd = module.state_dict()
+    with torch.no_grad():
+        for name in sorted(sd.keys()):
+            t = sd[name]
+            if not t.is_floating_point():
+                continue
+            rs = np.random.RandomState((zlib.crc32(name.encode()) + seed) & 0x7FFFFFFF)
+            shape = tuple(t.shape)
+            bn = ".cbr_unit.1." in name
+            if name.endswith("running_var"):
+                v = rs.uniform(0.5, 2.0, shape)
+            elif name.endswith("running_mean"):
+                v = rs.standard_normal(shape) * 0.2
+            elif bn and name.endswith("bias"):
+                v = rs.uniform(0.1, 0.5, shape)
+            elif bn:                                     # BatchNorm scale
+                v = rs.uniform(0.8, 1.6, shape)
+            elif name.endswith("bias"):
+                v = rs.uniform(-0.1, 0.1, shape)
+            else:
+                v = rs.standard_normal(shape) * (2.0 / t[0].numel()) ** 0.5
+                if name == "query_key_net.conv1.cbr_unit.0.weight":
+                    v = v / float(input_scale)
+                if name in ("attention_net.linear_feat.weight", "attention_net.linear_context.weight"):
+                    v = v * float(attention_gain)
+            t.copy_(torch.from_numpy(np.ascontiguousarray(v)).to(t.dtype))
