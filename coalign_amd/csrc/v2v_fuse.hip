@@ -14,13 +14,11 @@
 // 16 x 16 B = 256 contiguous bytes of a SplitMap plane.  No LDS, no barriers, no workspace, the caller's stream: capturable.
 #include "common.h"
 #include "warp_taps.h"
+#include "v2v_lanes.h"
 
 #include "coalign_amd_v2v.h"
 
 namespace {
-
-constexpr int PW = 16;      // pixels per wavefront
-constexpr int GL = 4;       // channel groups in flight per pixel (lanes per pixel)
 
 struct Geom { int C, H, W, Ho, Wo; };      // what make_taps reads: source plane and output grid are the same map here
 
@@ -46,49 +44,6 @@ struct GateArgs {
     int *range_flag;
     int R, Ch, H, W, out_kind;
 };
-
-// this wavefront's (map, pixel tile) and this lane's pixel of it; false: the wavefront lies beyond the last tile
-struct Place { int map, pix, g0; bool live; };
-__device__ __forceinline__ bool place(int maps, int HW, Place &p) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int tiles = (HW + PW - 1) / PW;
-    const long long t = (long long)blockIdx.x * 4 + wave;
-    if (t >= (long long)maps * tiles) return false;
-    p.map = (int)(t / tiles);
-    const int raw = (int)(t - (long long)p.map * tiles) * PW + (lane & (PW - 1));
-    p.live = raw < HW;
-    p.pix = p.live ? raw : HW - 1;      // (a lane past the end reads the last pixel and stores nothing)
-    p.g0 = lane / PW;
-    return true;
-}
-
-__device__ __forceinline__ void load8(const float *p, float (&v)[8]) {
-    const float4 a = reinterpret_cast<const float4 *>(p)[0], b = reinterpret_cast<const float4 *>(p)[1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-
-__device__ __forceinline__ void store8(float *p, const float (&v)[8]) {
-    reinterpret_cast<float4 *>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-    reinterpret_cast<float4 *>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-}
-
-// 8 consecutive channels (group g of a map of C16 16-channel steps) of one pixel -> the two planes of their channel half (the arithmetic of sp_pack_kernel)
-__device__ __forceinline__ bool store_split8(uint4 *y, int map, int C16, int g, int HW, int pix, const float (&v)[8], bool live) {
-    uint4 h, l;
-    coalign::sp16_split2(v[0], v[1], h.x, l.x);
-    coalign::sp16_split2(v[2], v[3], h.y, l.y);
-    coalign::sp16_split2(v[4], v[5], h.z, l.z);
-    coalign::sp16_split2(v[6], v[7], h.w, l.w);
-    bool big = false;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) big = big || fabsf(v[k]) > 65504.f;
-    if (live) {
-        const size_t base = ((size_t)((size_t)map * C16 + (g >> 1)) * 4 + (g & 1) * 2) * HW + pix;
-        y[base] = h;
-        y[base + HW] = l;
-    }
-    return big && live;
-}
 
 __global__ __launch_bounds__(256) void v2v_warp_split_kernel(const WarpArgs a) {
     const int HW = a.H * a.W, G = a.C / 8;
@@ -178,11 +133,6 @@ __global__ __launch_bounds__(256) void v2v_gate_kernel(const GateArgs a) {
     if (a.range_flag && big) atomicOr(a.range_flag, 1);
 }
 
-inline unsigned blocks_of(int maps, int H, int W) {
-    const long long tiles = ((long long)H * W + PW - 1) / PW;
-    return (unsigned)((maps * tiles + 3) / 4);
-}
-
 // the checks the three entry points share; COALIGN_OK + *empty when there is nothing to do
 int check_counts(int n, int R, int C, int H, int W, long long maps, bool *empty) {
     *empty = false;
@@ -196,8 +146,6 @@ int check_counts(int n, int R, int C, int H, int W, long long maps, bool *empty)
     if ((long long)C * H * W * maps > (long long)INT32_MAX) return COALIGN_ERR_BAD_SHAPE;
     return COALIGN_OK;
 }
-
-inline bool misaligned16(const void *p) { return reinterpret_cast<uintptr_t>(p) & 15; }
 
 }  // namespace
 

@@ -22,7 +22,11 @@ from . import ops
 from .backbone import BaseBEVBackbone, BasicBlock, DownsampleConv, NaiveCompressor, ResNetBEVBackbone, _cache_of, _fast_ok
 from .encoder import PillarVFE, PointPillarScatter, host_ints
 from .fusion import AttFusion, DiscoFusion, MaxFusion, V2VNetFusion, V2XViTFusion, When2comFusion, fuse_multiscale
-from .pose import normalize_pairwise_tfm
+from . import v2v_robust
+from .pose import generate_noise_torch, get_pairwise_transformation_torch, normalize_pairwise_tfm
+from .v2v_robust import AttentionWrapper, PoseRegressionWraper
+
+ROBUST_MIN_MAP = v2v_robust.MIN_MAP
 
 # Round 4: PillarVFE + PointPillarScatter as one launch with a sparse canvas (csrc/pillar_sparse.hip) feeding the first ResNet block directly.
 # "0": the dense persistent canvas of rounds 2-3 (measurement aid; module attribute, read at every call).
@@ -447,6 +451,240 @@ class PointPillarBaseline(nn.Module):
         return self.fuse_and_head(feats, record_len, affine)
 
 
+class PointPillarV2VNetRobust(nn.Module):
+    """V2VNet with learned pose correction (opencood/models/point_pillar_v2vnet_robust.py:21-332), the baseline CoAlign is compared with under pose noise: pillar
+    encoder, ``BaseBEVBackbone``, shrink header, optional ``NaiveCompressor(256, rate)`` when the integer ``compression`` > 0, then on the shrunk maps the pose
+    regression over all pairs (``pose_reg_net``), the globally consistent poses (``v2v_robust.weighted_em``), the attention scores (``attention_net``, with
+    ``attention_net.alpha``) and ``V2VNetFusion`` with ``agg_operator: weight``, 1 x 1 heads.  Same constructor keys, members, ``state_dict`` names and output keys
+    as the reference; its ``self.apply(weight_init)`` is not mirrored.
+
+    ``forward`` follows ``train_forward`` for ``stage`` 0 / 1 / 2.  Quirks of the reference, kept as they are:
+      * ``forward`` ALWAYS runs ``train_forward``: noise is added to the poses in eval mode too (stage 0: strong or weak per agent; stages 1 and 2: strong);
+        ``eval_forward`` exists and is never called by ``forward``;
+      * the rotation noise is a von Mises sample in RADIANS added to a yaw in degrees (``pose.generate_noise_torch``);
+      * ``get_intersection`` warps a tensor of zeros: the intersection is 0.01 whatever the poses;
+      * ``weighted_mle`` sees the INPUT poses in every one of the ten rounds, only the weights change;
+      * both wrappers warp to (robust.H, robust.W) but normalise the translation by the map's own H, W;
+      * stage 1 returns no ``cls_preds``: its outputs are ``pairwise_corr`` and ``pairwise_t_matrix`` only.
+    NOT kept: the reference adds the noise to the caller's ``lidar_pose`` in place; here the caller's tensor is left untouched.
+    Extension: ``data_dict['pose_noise']`` [n, 6] (and ``data_dict['noise_choice']`` [n, 1] for stage 0) replaces the drawn noise -- a run becomes repeatable, and
+    zeros give ``eval_forward``'s arithmetic.
+
+    Maps whose H, W differ from robust.H, robust.W, or lie below 24 x 24 (the smallest map the regression's pooling accepts), are refused with
+    ``NotImplementedError``.  Three routes: ``forward_torch`` (the reference op by op), ``forward_reduced`` (the exact identities of ``v2v_robust`` and
+    ``V2VNetFusion.forward_reduced`` in torch ops), ``forward_kernels`` (CUDA float32 in eval mode when ``kernel_route`` holds; ``force_torch`` is the test aid)."""
+
+    def __init__(self, args: dict):
+        super().__init__()
+        self.max_cav = args["max_cav"]
+        self.pillar_vfe = PillarVFE(args["pillar_vfe"], num_point_features=4, voxel_size=args["voxel_size"], point_cloud_range=args["lidar_range"])
+        self.scatter = PointPillarScatter(args["point_pillar_scatter"])
+        self.backbone = BaseBEVBackbone(args["base_bev_backbone"], 64)
+        self.voxel_size = args["voxel_size"]
+        self.out_channel = sum(args["base_bev_backbone"]["num_upsample_filter"])
+        self.shrink_flag = "shrink_header" in args
+        if self.shrink_flag:
+            self.shrink_conv = DownsampleConv(args["shrink_header"])
+            self.out_channel = args["shrink_header"]["dim"][-1]
+        self.compression = args.get("compression", 0) > 0
+        if self.compression:
+            self.naive_compressor = NaiveCompressor(256, args["compression"])
+        self.fusion_net = V2VNetFusion(args["v2vfusion"])
+        self.fusion_downsample_rate, self.fusion_discrete_ratio = args["v2vfusion"]["downsample_rate"], args["v2vfusion"]["voxel_size"][0]
+        self.cls_head = nn.Conv2d(self.out_channel, args["anchor_number"], kernel_size=1)
+        self.reg_head = nn.Conv2d(self.out_channel, 7 * args["anchor_number"], kernel_size=1)
+        robust = args["robust"]
+        self.downsample_rate, self.discrete_ratio, self.H, self.W = robust["downsample_rate"], robust["discrete_ratio"], robust["H"], robust["W"]
+        self.affine_parameter = {"H": self.H, "W": self.W, "downsample_rate": self.downsample_rate, "discrete_ratio": self.discrete_ratio}
+        self.pose_reg_net = PoseRegressionWraper(robust["feature_dim"] * 2, robust["hidden_dim"], self.affine_parameter)
+        self.attention_net = AttentionWrapper(robust["feature_dim"] * 2, robust["hidden_dim"], self.affine_parameter, robust.get("learnable_alpha", True))
+        self.stage = args["stage"]
+        self.use_dir = False
+        self.force_torch = False      # measurement / test aid: take the op-by-op route whatever the device
+        if self.stage == 1:
+            self.backbone_fix()
+        if self.stage == 2:
+            self.backbone_unfix()
+
+    def _trunk(self):
+        parts = [self.pillar_vfe, self.scatter, self.backbone, self.fusion_net, self.cls_head, self.reg_head, self.attention_net]
+        return parts + ([self.naive_compressor] if self.compression else []) + ([self.shrink_conv] if self.shrink_flag else [])
+
+    def backbone_fix(self) -> None:
+        """Stage 1 trains the pose regression alone: everything else is frozen (point_pillar_v2vnet_robust.py:81-110)."""
+        for m in self._trunk():
+            for p in m.parameters():
+                p.requires_grad = False
+
+    def backbone_unfix(self) -> None:
+        for m in self._trunk():
+            for p in m.parameters():
+                p.requires_grad = True
+
+    # ---- encoder -------------------------------------------------------------------------------------------------------------------------------------------
+    def encode(self, data_dict: dict) -> torch.Tensor:
+        """Per-agent part: pillars -> canvas -> backbone -> shrink header (-> compressor): the agents' maps [N, C, H, W]."""
+        batch_dict = self.scatter(self.pillar_vfe(_single_agent_batch(dict(data_dict, record_len=host_ints(data_dict["record_len"])))))
+        feats = self.backbone.get_multiscale_feature(batch_dict["spatial_features"])
+        want_split = bool(self.shrink_flag and all(getattr(m, "is_cuda", False) for m in feats) and self.shrink_conv.takes_split_maps())
+        x = self.backbone.decode_multiscale_feature(feats, out_split=True) if want_split else self.backbone.decode_multiscale_feature(feats)
+        if self.shrink_flag:
+            x = self.shrink_conv(x)
+        elif isinstance(x, ops.SplitMap):
+            x = x.dense()
+        if self.compression:
+            x = self.naive_compressor(x)
+        return x
+
+    # ---- noise ---------------------------------------------------------------------------------------------------------------------------------------------
+    def noise_generator(self, lidar_pose: torch.Tensor, all_strong: bool = False):
+        """(noise [N, 6], choice [N, 1]: 0 strong (0.4 m, 4 deg), 1 weak (0.01 m, 0.1 deg)) (point_pillar_v2vnet_robust.py:190-202)."""
+        noise_s = generate_noise_torch(lidar_pose, pos_std=0.4, rot_std=4)
+        noise_w = generate_noise_torch(lidar_pose, pos_std=0.01, rot_std=0.1)
+        N = lidar_pose.shape[0]
+        if all_strong:
+            return noise_s, torch.zeros((N, 1), device=lidar_pose.device)
+        choice = torch.randint(0, 2, (N, 1), device=lidar_pose.device)
+        return choice * noise_w + (1 - choice) * noise_s, choice
+
+    # ---- routes --------------------------------------------------------------------------------------------------------------------------------------------
+    def _check_map(self, x: torch.Tensor) -> None:
+        H, W = x.shape[2:]
+        if (H, W) != (self.H, self.W):
+            raise NotImplementedError(f"point_pillar_v2vnet_robust: the shrunk map is {H} x {W} but robust.H x robust.W is {self.H} x {self.W}")
+        if H < ROBUST_MIN_MAP or W < ROBUST_MIN_MAP:
+            raise NotImplementedError(f"point_pillar_v2vnet_robust: a {H} x {W} map is below {ROBUST_MIN_MAP} x {ROBUST_MIN_MAP}, the smallest the pose regression's pooling accepts")
+
+    def one_normalisation(self) -> bool:
+        """The three warps (pose regression, attention, fusion) normalise alike: ONE affine per pose set serves them, and one warp the attention and the fusion."""
+        return float(self.fusion_downsample_rate) * float(self.fusion_discrete_ratio) == float(self.downsample_rate) * float(self.discrete_ratio)
+
+    def kernel_route(self, channels: int, n_agents: int = 1, terms: Optional[int] = None) -> bool:
+        """The static half of the decision (``routes.plan`` asks it): the fusion's, both small nets' and the shapes' conditions; ``forward`` adds a CUDA float32 map."""
+        return bool(not self.training and not self.force_torch and self.one_normalisation() and self.fusion_net.kernel_route(channels, n_agents, terms)
+                    and self.pose_reg_net.kernel_route(channels, n_agents, terms, self.max_cav) and self.attention_net.kernel_route(channels, n_agents, terms, self.max_cav))
+
+    def _fusion_affine(self, T: torch.Tensor, H: int, W: int) -> torch.Tensor:
+        return normalize_pairwise_tfm(T, H, W, self.fusion_discrete_ratio, self.fusion_downsample_rate)
+
+    def _stages(self, x: torch.Tensor, groups, pose3: torch.Tensor, stage: int, reduced: bool) -> dict:
+        """train_forward after the noise, in torch ops: ``reduced`` picks every part's ``forward_reduced`` and the constant intersection."""
+        H, W = x.shape[2:]
+        L = max(self.max_cav, max(groups))
+        reg = self.pose_reg_net.forward_reduced if reduced else self.pose_reg_net.forward_torch
+        att = self.attention_net.forward_reduced if reduced else self.attention_net.forward_torch
+        fuse = self.fusion_net.forward_reduced if reduced else self.fusion_net.forward_torch
+        T = get_pairwise_transformation_torch(pose3, L, groups, dof=3)
+        out = {"stage": stage}
+        if stage in (1, 2):
+            out["pairwise_corr"], T_new = reg(x, groups, T)
+            out["pairwise_t_matrix"], out["pairwise_t_matrix_new"] = T, T_new
+        if stage == 1:
+            return out
+        if stage == 2:
+            poses, off = [], 0
+            for b, n in enumerate(groups):
+                p = pose3[off:off + n]
+                off += n
+                if n > 1:
+                    inter = v2v_robust.constant_intersection(T_new[b]) if reduced else v2v_robust.get_intersection(T_new[b], self.affine_parameter)
+                    p = v2v_robust.weighted_em(p, T_new[b], inter)
+                poses.append(p)
+            out["lidar_pose_corrected"] = torch.cat(poses, dim=0)
+            T = get_pairwise_transformation_torch(out["lidar_pose_corrected"], L, groups, dof=3)
+        out["scores"], weight = att(x, groups, T)
+        fused = fuse(x, groups, self._fusion_affine(T, H, W), weight)
+        return dict(out, weight=weight, **_run_heads(self, fused))
+
+    def forward_torch(self, x: torch.Tensor, record_len, pose3: torch.Tensor, stage: Optional[int] = None) -> dict:
+        self._check_map(x)
+        return self._stages(x, host_ints(record_len), pose3, self.stage if stage is None else stage, False)
+
+    def forward_reduced(self, x: torch.Tensor, record_len, pose3: torch.Tensor, stage: Optional[int] = None) -> dict:
+        self._check_map(x)
+        return self._stages(x, host_ints(record_len), pose3, self.stage if stage is None else stage, True)
+
+    def forward_kernels(self, x: torch.Tensor, record_len, pose3: torch.Tensor, stage: Optional[int] = None) -> dict:
+        """The same on the gfx950 kernels, frame by frame; nothing returns to the host between the maps and the head outputs (capturable)."""
+        self._check_map(x)
+        groups = host_ints(record_len)
+        stage = self.stage if stage is None else stage
+        C, H, W = x.shape[1:]
+        L = max(self.max_cav, max(groups))
+        den_x, den_y = self.downsample_rate * self.discrete_ratio * W, self.downsample_rate * self.discrete_ratio * H
+        if not ops.nhwc_memory(x):
+            x = x.contiguous(memory_format=torch.channels_last)
+        per = {k: [] for k in ("pairwise_corr", "pairwise_t_matrix", "pairwise_t_matrix_new", "lidar_pose_corrected", "scores", "weight", "fused")}
+        off = 0
+        for b, n in enumerate(groups):
+            xb = x[off:off + n]
+            poses = pose3[off:off + n].to(torch.float64).contiguous()
+            off += n
+            T, theta = ops.v2vr_pairwise(poses, L, H, W, den_x, den_y)
+            per["pairwise_t_matrix"].append(T)
+            warped = ops.v2v_warp_split(xb, theta[:n, :n])
+            if stage in (1, 2):
+                corr, T_new = self.pose_reg_net.forward_kernels(xb, warped, T)
+                per["pairwise_corr"].append(corr)
+                per["pairwise_t_matrix_new"].append(T_new)
+            if stage == 1:
+                continue
+            if stage == 2:
+                fixed, T, theta = ops.v2vr_consistency(poses, T_new, H, W, den_x, den_y)
+                per["lidar_pose_corrected"].append(fixed)
+                warped = ops.v2v_warp_split(xb, theta[:n, :n])
+            scores, weight = self.attention_net.forward_kernels(xb, warped, L)
+            per["scores"].append(scores)
+            per["weight"].append(weight)
+            per["fused"].append(self.fusion_net.forward_kernels(xb, [n], theta.unsqueeze(0), weight.unsqueeze(0), first_warp=[warped]))      # identity (c): one warp
+        out = {"stage": stage}
+        if stage in (1, 2):
+            out["pairwise_corr"] = torch.stack(per["pairwise_corr"])
+            out["pairwise_t_matrix"], out["pairwise_t_matrix_new"] = torch.stack(per["pairwise_t_matrix"]).float(), torch.stack(per["pairwise_t_matrix_new"]).float()
+        if stage == 1:
+            return out
+        if stage == 2:
+            out["lidar_pose_corrected"] = torch.cat(per["lidar_pose_corrected"], dim=0).to(pose3.dtype)
+        out["scores"], out["weight"] = torch.stack(per["scores"]), torch.stack(per["weight"])
+        fused = per["fused"][0] if len(per["fused"]) == 1 else torch.cat(per["fused"], dim=0)
+        return dict(out, **_run_heads(self, fused))
+
+    # ---- the reference's entry points ----------------------------------------------------------------------------------------------------------------------
+    def _route(self, x: torch.Tensor, record_len, pose3: torch.Tensor, stage: int) -> dict:
+        groups = host_ints(record_len)
+        if x.is_cuda and x.dtype == torch.float32 and sum(groups) == x.shape[0] and self.kernel_route(x.shape[1], max(groups)):
+            return self.forward_kernels(x, groups, pose3, stage)
+        return self.forward_torch(x, groups, pose3, stage)
+
+    def train_forward(self, spatial_features_2d: torch.Tensor, record_len, lidar_pose: torch.Tensor, pairwise_t_matrix=None, noise=None, choice=None) -> dict:
+        """point_pillar_v2vnet_robust.py:205-267.  ``pairwise_t_matrix`` is accepted and, like in the reference, never read: the matrices come from the noisy poses."""
+        stage = self.stage
+        if noise is None:
+            noise, choice = self.noise_generator(lidar_pose, all_strong=stage != 0)
+        elif choice is None:
+            choice = torch.zeros((lidar_pose.shape[0], 1), device=lidar_pose.device)
+        noisy = lidar_pose + noise.to(lidar_pose)                                      # (a copy: the reference's ``lidar_pose += noise`` changes the caller's tensor)
+        pose3 = noisy[:, [0, 1, 4]].to(spatial_features_2d.dtype)
+        out = self._route(spatial_features_2d, record_len, pose3, stage)
+        keys = {0: ("stage", "scores", "cls_preds", "reg_preds"), 1: ("stage", "pairwise_corr", "pairwise_t_matrix"),
+                2: ("stage", "scores", "cls_preds", "reg_preds", "pairwise_corr", "pairwise_t_matrix")}[stage]
+        out = {k: out[k] for k in keys}
+        if stage == 0:
+            out["choice"] = choice
+        return out
+
+    def eval_forward(self, spatial_features_2d: torch.Tensor, record_len, lidar_pose: torch.Tensor, pairwise_t_matrix=None) -> dict:
+        """Stage 2 without noise (point_pillar_v2vnet_robust.py:271-295); its ``pairwise_t_matrix`` is the regressed one, as in the reference.  Not called by ``forward``."""
+        pose3 = lidar_pose[:, [0, 1, 4]].to(spatial_features_2d.dtype)
+        out = self._route(spatial_features_2d, record_len, pose3, 2)
+        return {"stage": self.stage, "scores": out["scores"], "cls_preds": out["cls_preds"], "reg_preds": out["reg_preds"], "pairwise_t_matrix": out["pairwise_t_matrix_new"]}
+
+    def forward(self, data_dict: dict) -> dict:
+        record_len = host_ints(data_dict["record_len"])
+        x = self.encode(dict(data_dict, record_len=record_len))
+        return self.train_forward(x, record_len, data_dict["lidar_pose"], data_dict.get("pairwise_t_matrix"), noise=data_dict.get("pose_noise"), choice=data_dict.get("noise_choice"))
+
+
 MODEL_REGISTRY = {
     "point_pillar_baseline_multiscale": PointPillarBaselineMultiscale,
     "point_pillar_coalign": CoAlign,
@@ -460,6 +698,7 @@ MODEL_REGISTRY = {
 BASELINE_REGISTRY = {
     "point_pillar_disconet": PointPillarDiscoNet,
     "point_pillar_baseline": PointPillarBaseline,
+    "point_pillar_v2vnet_robust": PointPillarV2VNetRobust,
 }
 
 

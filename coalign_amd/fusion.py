@@ -278,7 +278,10 @@ class V2VNetFusion(nn.Module):
     ``forward_torch`` states that op by op.  Three exact identities cut its work to a third (``forward_reduced``, the schedule of the kernel route):
     a GRU cell with h = 0 is one convolution in -> 2 hidden and ``sigmoid(beta) * tanh(cnm)`` (``ConvGRUCell.reduced``); ``msg_cnn`` is linear, so its ego half is
     computed once per receiver; the last iteration updates the ego alone.  On the GPU in eval mode (``kernel_route``) the convolutions run on ``ops.conv3x3_sp`` and
-    the glue on ``ops.v2v_warp_split`` / ``v2v_aggregate`` / ``v2v_gate``, one launch per stage over all (receiver, sender) pairs of a frame."""
+    the glue on ``ops.v2v_warp_split`` / ``v2v_aggregate`` / ``v2v_gate``, one launch per stage over all (receiver, sender) pairs of a frame.
+
+    ``agg_operator: weight`` (fuse_modules/v2v_fuse.py:140-141, the pose-robust V2VNet's fusion): ``agg_i = sum_j message_ij * weight[b, i, j]`` with the caller's
+    ``weight`` [B, L, L], products and sums in order of j; on the kernel route ``ops.v2vr_aggregate``.  Without a weight every route raises ``ValueError``."""
 
     def __init__(self, args: dict):
         super().__init__()
@@ -293,24 +296,29 @@ class V2VNetFusion(nn.Module):
         self.mlp = nn.Linear(in_channels, in_channels)
         self.force_torch = False      # measurement / test aid: take the op-by-op route whatever the device
 
-    def _check_agg(self) -> None:
-        if self.agg_operator not in ("max", "avg"):
+    def _check_agg(self, weight=None, static: bool = False) -> None:
+        """``static``: the name alone (``kernel_route`` answers before any weight exists)."""
+        if self.agg_operator not in ("max", "avg", "weight"):
             raise ValueError("agg_operator has wrong value")
+        if self.agg_operator == "weight" and weight is None and not static:
+            raise ValueError("agg_operator 'weight' needs the weight [B, L, L] of the senders (v2v_fuse.py:140-141)")
 
     def kernel_route(self, channels: int, n_agents: int = 1, terms: Optional[int] = None) -> bool:
         """The static half of the decision (``routes.plan`` asks it): eval mode, 3 x 3 GRU kernels, widths ``conv3x3_sp`` takes (C % 64 == 0, 2C <= its 1024-channel
         limit), at most 8 agents, the SplitMap arithmetic in force.  ``forward`` adds: a CUDA float32 map."""
-        self._check_agg()
+        self._check_agg(static=True)
         k3 = all(tuple(c.conv_gates.kernel_size) == (3, 3) for c in self.conv_gru.cell_list)
         widths = channels == self.msg_cnn.out_channels and channels % 64 == 0 and _bb.sp_channels_ok(2 * channels, 2 * channels) and ops.v2v_shape_ok(channels, n_agents)
         return bool(not self.training and not self.force_torch and k3 and widths and _bb.split_maps_active(terms))
 
     # ---- the reference's loops, op by op -----------------------------------------------------------------------------------------------------------------
-    def forward_torch(self, x: torch.Tensor, record_len, normalized_affine_matrix: torch.Tensor) -> torch.Tensor:
+    def forward_torch(self, x: torch.Tensor, record_len, normalized_affine_matrix: torch.Tensor, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
         _, C, H, W = x.shape
         groups = host_ints(record_len)
         feats = list(torch.split(x, groups, dim=0))
         A = normalized_affine_matrix
+        if self.agg_operator == "weight":
+            self._check_agg(weight)
         masks = [[_warp_torch(x.new_ones((N, 1, H, W)), A[b, i, :N]) for i in range(N)] for b, N in enumerate(groups)]
         for _ in range(self.num_iteration):
             updated_batch = []
@@ -324,6 +332,8 @@ class V2VNetFusion(nn.Module):
                         agg_feature = torch.mean(message, dim=0)
                     elif self.agg_operator == "max":
                         agg_feature = torch.max(message, dim=0)[0]
+                    elif self.agg_operator == "weight":                                                            # v2v_fuse.py:140-141
+                        agg_feature = torch.sum(message * weight[b][i, :N].view(-1, 1, 1, 1).to(message), dim=0)
                     else:
                         raise ValueError("agg_operator has wrong value")
                     if self.gru_flag:
@@ -348,8 +358,8 @@ class V2VNetFusion(nn.Module):
     def _receivers(iteration: int, iterations: int, n: int) -> int:
         return n if iteration < iterations - 1 else 1      # the output reads agent 0 of the last iteration only
 
-    def forward_reduced(self, x: torch.Tensor, record_len, normalized_affine_matrix: torch.Tensor) -> torch.Tensor:
-        self._check_agg()
+    def forward_reduced(self, x: torch.Tensor, record_len, normalized_affine_matrix: torch.Tensor, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+        self._check_agg(weight)
         _, C, H, W = x.shape
         groups = host_ints(record_len)
         wn, we, bm, cells = self.reduced_weights()
@@ -366,6 +376,11 @@ class V2VNetFusion(nn.Module):
                 m = (a + e.unsqueeze(1)) * mask
                 if self.agg_operator == "max":
                     agg = m.max(dim=1)[0]
+                elif self.agg_operator == "weight":                                                                # the products and the sum in order of j
+                    wb = weight[b].to(m)
+                    agg = m[:, 0] * wb[:R, 0].view(R, 1, 1, 1)
+                    for j in range(1, N):
+                        agg = agg + m[:, j] * wb[:R, j].view(R, 1, 1, 1)
                 else:
                     agg = m[:, 0]
                     for j in range(1, N):
@@ -396,7 +411,11 @@ class V2VNetFusion(nn.Module):
                     [(Conv3x3Pack(cw).emu(16, True), cb.detach().float().contiguous(), cw.shape[0]) for cw, cb in cells], mlp.get(), self.mlp.bias.detach().float().contiguous())
         return _cache_of(self, "_coalign_v2v_images").get(self, build)
 
-    def forward_kernels(self, xx: torch.Tensor, groups: Sequence[int], normalized_affine_matrix: torch.Tensor) -> torch.Tensor:
+    def forward_kernels(self, xx: torch.Tensor, groups: Sequence[int], normalized_affine_matrix: torch.Tensor, weight: Optional[torch.Tensor] = None,
+                        first_warp=None) -> torch.Tensor:
+        """``first_warp``: per frame the SplitMap ``ops.v2v_warp_split(x_b, theta_b)`` a caller has already made of the INPUT maps (the pose-robust model's attention
+        reads the same warp), used in place of iteration 0's own."""
+        self._check_agg(weight)
         img_n, img_e, bm, zero, cells, img_mlp, b_mlp = self.packed()
         C = xx.shape[1]
         if not ops.nhwc_memory(xx):
@@ -408,12 +427,19 @@ class V2VNetFusion(nn.Module):
             xb = xx[off:off + n]
             theta = normalized_affine_matrix[b, :n, :n].to(device=xx.device, dtype=torch.float64).contiguous()
             off += n
+            wb = None
+            if self.agg_operator == "weight":
+                wb = weight[b].to(device=xx.device, dtype=torch.float32).contiguous()
             for it in range(self.num_iteration):
                 R = self._receivers(it, self.num_iteration, n)
                 th = theta[:R]
                 e = ops.conv3x3_sp(ops.SplitMap.pack(xb[:R]), img_e, bm, C, None, False, out_split=False)
-                a = ops.conv3x3_sp(ops.v2v_warp_split(xb, th), img_n, zero, C, None, False, out_split=False)
-                h = ops.v2v_aggregate(a, e, xb, th, self.agg_operator, gru=bool(self.gru_flag))
+                warped = ops.v2v_warp_split(xb, th) if it > 0 or first_warp is None else ops.SplitMap(first_warp[b].data[:R * n])
+                a = ops.conv3x3_sp(warped, img_n, zero, C, None, False, out_split=False)
+                if wb is not None:
+                    h = ops.v2vr_aggregate(a, e, xb, th, wb, gru=bool(self.gru_flag))
+                else:
+                    h = ops.v2v_aggregate(a, e, xb, th, self.agg_operator, gru=bool(self.gru_flag))
                 if self.gru_flag:
                     for k, (img, bias, width) in enumerate(cells):
                         h = ops.v2v_gate(ops.conv3x3_sp(h, img, bias, width, None, False, out_split=False), out_split=k + 1 < len(cells))
@@ -422,11 +448,11 @@ class V2VNetFusion(nn.Module):
         out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
         return ops.pointwise_conv(out, img_mlp, b_mlp, C, relu=False, out_channels_last=True)
 
-    def forward(self, x: torch.Tensor, record_len, normalized_affine_matrix: torch.Tensor, rows=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, record_len, normalized_affine_matrix: torch.Tensor, weight: Optional[torch.Tensor] = None, rows=None) -> torch.Tensor:
         if rows is not None:
             raise NotImplementedError("V2VNetFusion does not run agent-sharded (rows)")
         groups = host_ints(record_len)
         if x.is_cuda and x.dtype == torch.float32 and sum(groups) == x.shape[0] and self.kernel_route(x.shape[1], max(groups)):
-            return self.forward_kernels(x, groups, normalized_affine_matrix)
-        self._check_agg()
-        return self.forward_torch(x, groups, normalized_affine_matrix)
+            return self.forward_kernels(x, groups, normalized_affine_matrix, weight)
+        self._check_agg(weight)
+        return self.forward_torch(x, groups, normalized_affine_matrix, weight)

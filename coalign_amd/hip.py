@@ -173,6 +173,19 @@ W2C_SIGNATURES = {
     "coalign_w2c_fuse": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P]),
 }
 
+# include/coalign_amd_v2v_robust.h: the tenth extension header of ABI version 2 (product library): the glue of the pose-robust V2VNet between its convolutions --
+# pooling tails, the attention's score head, the pose regression's head, pairwise matrices, the whole WeightedEM in one workgroup, the weighted aggregation
+# (csrc/v2v_robust.hip)
+V2VR_SIGNATURES = {
+    "coalign_v2vr_pool_act": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
+    "coalign_v2vr_score_head": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P]),
+    "coalign_v2vr_pose_head_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "coalign_v2vr_pose_head": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, c_size_t, P]),
+    "coalign_v2vr_pairwise": (c_int, [P, c_int, c_int, c_int, c_int, c_double, c_double, P, P, P]),
+    "coalign_v2vr_consistency": (c_int, [P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, P, P, P]),
+    "coalign_v2vr_aggregate": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P, P, P]),
+}
+
 _LAB_LIB = None
 
 
@@ -199,7 +212,7 @@ def lib() -> ctypes.CDLL:
             raise CoalignHipError(
                 f"{path} is missing and could not be built ({exc}); the CoAlign hot path has no CPU fallback") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **V2X_WINDOW_SIGNATURES, **W2C_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **V2X_WINDOW_SIGNATURES, **W2C_SIGNATURES, **V2VR_SIGNATURES}.items():
         fn = getattr(handle, name)  # AttributeError here == header / library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -223,7 +236,7 @@ def lab_lib() -> ctypes.CDLL:
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(f"{path} is missing and could not be built ({exc})") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **V2X_WINDOW_SIGNATURES, **W2C_SIGNATURES, **LAB_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **V2X_WINDOW_SIGNATURES, **W2C_SIGNATURES, **V2VR_SIGNATURES, **LAB_SIGNATURES}.items():
         fn = getattr(handle, name)
         fn.restype = res
         fn.argtypes = args

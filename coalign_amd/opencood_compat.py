@@ -16,7 +16,7 @@ import sys
 import types
 from typing import Dict
 
-from . import backbone, box_align, config, detector, encoder, evaluation, fusion, pcdet, pose, postprocess, preprocess
+from . import backbone, box_align, config, detector, encoder, evaluation, fusion, pcdet, pose, postprocess, preprocess, v2v_robust
 
 # dotted module name -> {attribute: object}
 _EXPORTS: Dict[str, Dict[str, object]] = {
@@ -25,6 +25,13 @@ _EXPORTS: Dict[str, Dict[str, object]] = {
     "opencood.models.point_pillar": {"PointPillar": detector.PointPillar},
     "opencood.models.point_pillar_disconet": {"PointPillarDiscoNet": detector.PointPillarDiscoNet},
     "opencood.models.point_pillar_baseline": {"PointPillarBaseline": detector.PointPillarBaseline},
+    "opencood.models.point_pillar_v2vnet_robust": {"PointPillarV2VNetRobust": detector.PointPillarV2VNetRobust},
+    "opencood.models.fuse_modules.v2v_fuse": {"V2VNetFusion": fusion.V2VNetFusion},
+    "opencood.models.sub_modules.v2v_robust_module": {"PoseRegression": v2v_robust.PoseRegression, "PoseRegressionWraper": v2v_robust.PoseRegressionWraper,
+                                                       "Attention": v2v_robust.Attention, "AttentionWrapper": v2v_robust.AttentionWrapper,
+                                                       "get_intersection": v2v_robust.get_intersection, "WeightedMLE": v2v_robust.weighted_mle,
+                                                       "WeightedEM": v2v_robust.weighted_em, "update_weight": v2v_robust.update_weight, "log_t": v2v_robust.log_t,
+                                                       "regroup": v2v_robust.regroup},
     "opencood.models.sub_modules.convgru": {"ConvGRU": fusion.ConvGRU, "ConvGRUCell": fusion.ConvGRUCell},
     "opencood.models.fuse_modules.disco_fuse": {"PixelWeightLayer": fusion.PixelWeightLayer},
     "opencood.models.sub_modules.pillar_vfe": {"PillarVFE": encoder.PillarVFE, "PFNLayer": encoder.PFNLayer},
@@ -38,8 +45,10 @@ _EXPORTS: Dict[str, Dict[str, object]] = {
                                                    "regroup": fusion.regroup, "warp_feature": fusion.warp_feature},
     "opencood.models.fuse_modules.fuse_utils": {"regroup": fusion.regroup},
     "opencood.utils.transformation_utils": {"normalize_pairwise_tfm": pose.normalize_pairwise_tfm, "x_to_world": pose.x_to_world,
-                                            "get_pairwise_transformation": pose.get_pairwise_transformation},
-    "opencood.utils.pose_utils": {"generate_noise": pose.generate_noise},
+                                            "get_pairwise_transformation": pose.get_pairwise_transformation,
+                                            "get_pairwise_transformation_torch": pose.get_pairwise_transformation_torch, "pose_to_tfm": pose.pose_to_tfm,
+                                            "tfm_to_xycs_torch": v2v_robust.tfm_to_xycs, "xycs_to_tfm_torch": v2v_robust.xycs_to_tfm},
+    "opencood.utils.pose_utils": {"generate_noise": pose.generate_noise, "generate_noise_torch": pose.generate_noise_torch},
     "opencood.utils.box_utils": {"nms_rotated": postprocess.nms_rotated},
     "opencood.data_utils.post_processor.voxel_postprocessor": {"VoxelPostprocessor": postprocess.VoxelPostprocessor},
     "opencood.data_utils.post_processor": {"build_postprocessor": postprocess.build_postprocessor,

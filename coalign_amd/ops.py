@@ -1876,3 +1876,118 @@ def w2c_fuse(x: torch.Tensor, theta: torch.Tensor, weights: torch.Tensor) -> tor
     with _Timed("w2c_fuse"):
         hip.check(hip.lib().coalign_w2c_fuse(_ptr(x), n, C, H, W, _ptr(th), _ptr(weights), _ptr(out), _stream()), "coalign_w2c_fuse")
     return out
+
+
+# ---- The pose-robust V2VNet between its convolutions (include/coalign_amd_v2v_robust.h, csrc/v2v_robust.hip) -------------------------------------------------
+V2VR_MAX_CAV = 16
+
+
+def v2vr_shape_ok(channels: int, hidden: int, n_agents: int, max_cav: int = 5) -> bool:
+    """The shapes the ``coalign_v2vr_*`` kernels take: C % 16 == 0 (the maps), hidden % 64 == 0 and <= 1024 (the two heads), 1 .. 8 agents in at most 16 slots."""
+    return channels > 0 and channels % 16 == 0 and hidden > 0 and hidden % 64 == 0 and hidden <= 1024 and 1 <= n_agents <= 8 and n_agents <= max_cav <= V2VR_MAX_CAV
+
+
+def _f64_dev(t: torch.Tensor, shape, what: str) -> torch.Tensor:
+    if t.dtype != torch.float64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what}: a contiguous float64 tensor {list(shape)}")
+    return t
+
+
+@_device_op
+def v2vr_pool_act(a: torch.Tensor, e: Optional[torch.Tensor] = None, n: int = 1, out_split: bool = True):
+    """lrelu(max_pool2d(a + e[p // n], 2)) in one pass (``coalign_v2vr_pool_act``): a [P, C, H, W], e [P / n, C, H, W] or None, float32 channels-last -> the
+    SplitMap [P, C, H // 2, W // 2] or the float32 channels-last map."""
+    _need_gpu(a, e)
+    P, C, H, W = _nhwc_map(a, "v2vr_pool_act a")
+    if C % 16 or H < 2 or W < 2 or (e is not None and (n < 1 or P % n or _nhwc_map(e, "v2vr_pool_act e") != (P // n, C, H, W))):
+        raise ValueError("v2vr_pool_act: a [P, C, H, W], e [P / n, C, H, W] or None, C % 16 == 0, H and W at least 2")
+    out = SplitMap.empty(P, C, H // 2, W // 2, a.device) if out_split else _nhwc_empty(P, C, H // 2, W // 2, a.device)
+    with _Timed("v2vr_pool_act"):
+        hip.check(hip.lib().coalign_v2vr_pool_act(_ptr(a), _ptr(e), P, int(n), C, H, W, V2V_OUT_SP if out_split else V2V_OUT_NHWC, _ptr(out.data if out_split else out),
+                                                  _ptr(sp_range_flag(a.device)) if out_split else None, _stream()), "coalign_v2vr_pool_act")
+    return out
+
+
+@_device_op
+def v2vr_score_head(y: torch.Tensor, n: int, max_cav: int, w: torch.Tensor, b: torch.Tensor, alpha: torch.Tensor):
+    """The attention's tail and the aggregation weights of one frame (``coalign_v2vr_score_head``): y [n n, h, H, W] float32 channels-last (the second convolution's
+    output), w [h], b [1], alpha [1] float32 on the device -> (scores [L, L], weight [L, L])."""
+    _need_gpu(y, w, b, alpha)
+    P, h, H, W = _nhwc_map(y, "v2vr_score_head")
+    if P != n * n or not v2vr_shape_ok(16, h, n, max_cav) or H < 2 or W < 2 or any(t.dtype != torch.float32 or not t.is_contiguous() for t in (w, b, alpha)) or w.numel() != h or b.numel() != 1 or alpha.numel() != 1:
+        raise ValueError("v2vr_score_head: y [n n, h, H, W], h % 64 == 0, w [h], b [1], alpha [1] float32, n <= 8, n <= max_cav <= 16")
+    scores = torch.empty((max_cav, max_cav), dtype=torch.float32, device=y.device)
+    weight = torch.empty_like(scores)
+    with _Timed("v2vr_score_head"):
+        hip.check(hip.lib().coalign_v2vr_score_head(_ptr(y), n, max_cav, h, H, W, _ptr(w), _ptr(b), _ptr(alpha), _ptr(scores), _ptr(weight), _stream()), "coalign_v2vr_score_head")
+    return scores, weight
+
+
+@_device_op
+def v2vr_pose_head(y4: "SplitMap", n: int, max_cav: int, fc, T: torch.Tensor):
+    """The pose regression's tail for all pairs of one frame (``coalign_v2vr_pose_head``): y4 the SplitMap [n n, h, H4, W4] of the strided fourth convolution,
+    fc = (W1 [h, h], b1, W2 [h, h], b2, W3 [3, h], b3) float32, T [L, L, 4, 4] float64 -> (pose_corr [L, L, 3] float32, T_new [L, L, 4, 4] float64)."""
+    if not isinstance(y4, SplitMap):
+        raise TypeError("v2vr_pose_head reads a SplitMap")
+    _need_gpu(y4.data, T, *fc)
+    P, h, H4, W4 = y4.shape
+    shapes = ((h, h), (h,), (h, h), (h,), (3, h), (3,))
+    if P != n * n or not v2vr_shape_ok(16, h, n, max_cav) or H4 < 2 or W4 < 2 or len(fc) != 6 or any(t.dtype != torch.float32 or tuple(t.shape) != s or not t.is_contiguous() for t, s in zip(fc, shapes)):
+        raise ValueError("v2vr_pose_head: y4 [n n, h, H4 >= 2, W4 >= 2], h % 64 == 0, fc = (W1 [h, h], b1, W2 [h, h], b2, W3 [3, h], b3) float32 contiguous")
+    _f64_dev(T, (max_cav, max_cav, 4, 4), "v2vr_pose_head T")
+    corr = torch.empty((max_cav, max_cav, 3), dtype=torch.float32, device=T.device)
+    T_new = torch.empty_like(T)
+    ws = torch.empty(hip.lib().coalign_v2vr_pose_head_workspace_bytes(n, h), dtype=torch.uint8, device=T.device)
+    with _Timed("v2vr_pose_head"):
+        hip.check(hip.lib().coalign_v2vr_pose_head(_ptr(y4.data), n, max_cav, h, H4, W4, *[_ptr(t) for t in fc], _ptr(T), _ptr(corr), _ptr(T_new), _ptr(ws), ws.numel(), _stream()),
+                  "coalign_v2vr_pose_head")
+    return corr, T_new
+
+
+@_device_op
+def v2vr_pairwise(poses: torch.Tensor, max_cav: int, H: int, W: int, den_x: float, den_y: float):
+    """3-dof poses [n, 3] float64 (x, y, yaw in degrees) -> (pairwise [L, L, 4, 4], normalised affine [L, L, 2, 3]) float64 (``coalign_v2vr_pairwise``)."""
+    _need_gpu(poses)
+    n = poses.shape[0]
+    _f64_dev(poses, (n, 3), "v2vr_pairwise poses")
+    pairwise = torch.empty((max_cav, max_cav, 4, 4), dtype=torch.float64, device=poses.device)
+    affine = torch.empty((max_cav, max_cav, 2, 3), dtype=torch.float64, device=poses.device)
+    with _Timed("v2vr_pairwise"):
+        hip.check(hip.lib().coalign_v2vr_pairwise(_ptr(poses), n, max_cav, H, W, float(den_x), float(den_y), _ptr(pairwise), _ptr(affine), _stream()), "coalign_v2vr_pairwise")
+    return pairwise, affine
+
+
+@_device_op
+def v2vr_consistency(poses: torch.Tensor, T_new: torch.Tensor, H: int, W: int, den_x: float, den_y: float):
+    """The whole ``WeightedEM`` of one frame in one launch (``coalign_v2vr_consistency``): poses [n, 3], T_new [L, L, 4, 4] float64 -> (corrected poses [n, 3],
+    pairwise [L, L, 4, 4], normalised affine [L, L, 2, 3]) float64."""
+    _need_gpu(poses, T_new)
+    n, L = poses.shape[0], T_new.shape[0]
+    _f64_dev(poses, (n, 3), "v2vr_consistency poses")
+    _f64_dev(T_new, (L, L, 4, 4), "v2vr_consistency T_new")
+    out = torch.empty_like(poses)
+    pairwise = torch.empty_like(T_new)
+    affine = torch.empty((L, L, 2, 3), dtype=torch.float64, device=poses.device)
+    with _Timed("v2vr_consistency"):
+        hip.check(hip.lib().coalign_v2vr_consistency(_ptr(poses), _ptr(T_new), n, L, H, W, float(den_x), float(den_y), _ptr(out), _ptr(pairwise), _ptr(affine), _stream()),
+                  "coalign_v2vr_consistency")
+    return out, pairwise, affine
+
+
+@_device_op
+def v2vr_aggregate(a: torch.Tensor, e: torch.Tensor, x: torch.Tensor, theta: torch.Tensor, weight: torch.Tensor, gru: bool = True):
+    """``v2v_aggregate`` with agg_i = sum_j m_ij * weight[i, j] in order of j (``coalign_v2vr_aggregate``): weight [>= R, L] float32 on the device, rows contiguous."""
+    _need_gpu(a, e, x, theta, weight)
+    R, C, H, W = _nhwc_map(e, "v2vr_aggregate e")
+    Rn = _nhwc_map(a, "v2vr_aggregate a")[0]
+    n = Rn // max(R, 1)
+    th = _theta_pairs(theta, n, e.device)
+    if not v2v_shape_ok(C, n) or tuple(a.shape) != (R * n, C, H, W) or th.shape[0] != R or _nhwc_map(x, "v2vr_aggregate x")[1:] != (C, H, W) or x.shape[0] < R:
+        raise ValueError("v2vr_aggregate: a [R n, C, H, W], e [R, C, H, W], x [>= R, C, H, W], theta [R, n, 2, 3], C % 16 == 0, n <= 8")
+    if weight.dtype != torch.float32 or weight.dim() != 2 or weight.shape[0] < R or not n <= weight.shape[1] <= V2VR_MAX_CAV or not weight.is_contiguous() or weight.device != e.device:
+        raise ValueError("v2vr_aggregate: weight [>= R, n <= L <= 16] float32 contiguous on the maps' device")
+    out = SplitMap.empty(R, 2 * C, H, W, e.device) if gru else _nhwc_empty(R, C, H, W, e.device)
+    with _Timed("v2vr_aggregate"):
+        hip.check(hip.lib().coalign_v2vr_aggregate(_ptr(a), _ptr(e), _ptr(x), n, R, C, H, W, _ptr(th), _ptr(weight), int(weight.shape[1]), V2V_OUT_SP if gru else V2V_OUT_NHWC,
+                                                   _ptr(out.data if gru else out), _ptr(sp_range_flag(e.device)) if gru else None, _stream()), "coalign_v2vr_aggregate")
+    return out

@@ -7,6 +7,12 @@ doubles per agent, so they stay on the host in float64 exactly like the referenc
 * ``get_pairwise_transformation`` <- opencood/utils/transformation_utils.py:22-67
 * ``normalize_pairwise_tfm``      <- opencood/utils/transformation_utils.py:69-91
 * ``generate_noise``              <- opencood/utils/pose_utils.py:43-73
+
+The pose-robust V2VNet builds its matrices from (noisy, then corrected) poses INSIDE the forward pass, in torch and in float32:
+
+* ``pose_to_tfm``                       <- opencood/utils/transformation_utils.py:93-160
+* ``get_pairwise_transformation_torch`` <- opencood/utils/transformation_utils.py:365-415
+* ``generate_noise_torch``              <- opencood/utils/pose_utils.py:108-141
 """
 from __future__ import annotations
 
@@ -98,3 +104,62 @@ def generate_noise(pos_std: float, rot_std: float, pos_mean: float = 0, rot_mean
     xy = rng.normal(pos_mean, pos_std, size=2)
     yaw = rng.normal(rot_mean, rot_std, size=1)
     return np.array([xy[0], xy[1], 0.0, 0.0, yaw[0], 0.0])
+
+
+def pose_to_tfm(pose: torch.Tensor) -> torch.Tensor:
+    """[N, 3] (x, y, yaw in degrees) or [N, 6] (x, y, z, roll, yaw, pitch; CARLA convention) -> [N, 4, 4] in the poses' dtype (float32 poses: the reference's
+    ``torch.eye`` default)."""
+    N = pose.shape[0]
+    tfm = torch.eye(4, device=pose.device, dtype=pose.dtype).view(1, 4, 4).repeat(N, 1, 1)
+    if pose.shape[1] == 3:
+        x, y, yaw = pose[:, 0], pose[:, 1], pose[:, 2]
+        tfm[:, 0, 0] = torch.cos(torch.deg2rad(yaw))
+        tfm[:, 0, 1] = -torch.sin(torch.deg2rad(yaw))
+        tfm[:, 1, 0] = torch.sin(torch.deg2rad(yaw))
+        tfm[:, 1, 1] = torch.cos(torch.deg2rad(yaw))
+        tfm[:, 0, 3] = x
+        tfm[:, 1, 3] = y
+    elif pose.shape[1] == 6:
+        x, y, z, roll, yaw, pitch = (pose[:, k] for k in range(6))
+        c_y, s_y = torch.cos(torch.deg2rad(yaw)), torch.sin(torch.deg2rad(yaw))
+        c_r, s_r = torch.cos(torch.deg2rad(roll)), torch.sin(torch.deg2rad(roll))
+        c_p, s_p = torch.cos(torch.deg2rad(pitch)), torch.sin(torch.deg2rad(pitch))
+        tfm[:, 0, 3], tfm[:, 1, 3], tfm[:, 2, 3] = x, y, z
+        tfm[:, 0, 0] = c_p * c_y
+        tfm[:, 0, 1] = c_y * s_p * s_r - s_y * c_r
+        tfm[:, 0, 2] = -c_y * s_p * c_r - s_y * s_r
+        tfm[:, 1, 0] = s_y * c_p
+        tfm[:, 1, 1] = s_y * s_p * s_r + c_y * c_r
+        tfm[:, 1, 2] = -s_y * s_p * c_r + c_y * s_r
+        tfm[:, 2, 0] = s_p
+        tfm[:, 2, 1] = -c_p * s_r
+        tfm[:, 2, 2] = c_p * c_r
+    else:
+        raise ValueError("pose_to_tfm: [N, 3] or [N, 6]")
+    return tfm
+
+
+def get_pairwise_transformation_torch(lidar_poses: torch.Tensor, max_cav: int, record_len, dof: int = 3) -> torch.Tensor:
+    """``[B, L, L, 4, 4]``; entry ``[b, i, j]`` is T_j^-1 T_i of frame b (``torch.linalg.solve``, like the reference), identity on the diagonal and in unused slots; in the poses' dtype."""
+    groups = [int(v) for v in record_len]
+    out = torch.eye(4, device=lidar_poses.device, dtype=lidar_poses.dtype).view(1, 1, 1, 4, 4).repeat(len(groups), max_cav, max_cav, 1, 1)
+    off = 0
+    for b, n in enumerate(groups):
+        t_list = pose_to_tfm(lidar_poses[off:off + n])
+        off += n
+        for i in range(n):
+            for j in range(n):
+                if i != j:
+                    out[b, i, j] = torch.linalg.solve(t_list[j], t_list[i])
+    return out
+
+
+def generate_noise_torch(pose: torch.Tensor, pos_std: float, rot_std: float, pos_mean: float = 0, rot_mean: float = 0) -> torch.Tensor:
+    """[N, 6] noise for [N, 6] poses: Gaussian on x and y; the yaw entry is a von Mises sample with concentration (180 / (pi rot_std))^2 -- in RADIANS, which the
+    model then adds to a yaw in degrees (the reference's behaviour, kept)."""
+    N = pose.shape[0]
+    noise = torch.zeros_like(pose)
+    concentration = (180 / (np.pi * rot_std)) ** 2
+    noise[:, :2] = torch.normal(pos_mean, pos_std, size=(N, 2), device=pose.device)
+    noise[:, 4] = torch.distributions.von_mises.VonMises(loc=rot_mean, concentration=concentration).sample((N,)).to(noise)
+    return noise

@@ -46,6 +46,11 @@ W2C = ("v2v_warp_split + conv3x3_sp x 3 + conv3x3_sp_s2 x 3 + w2c_score + w2c_fu
        "the SplitMap convolutions, the pooled heads with the softmax over the agents in two launches, warp and weighted sum in one; a one-agent frame is w2c_fuse alone")
 W2C_TORCH = "When2comFusion op by op in PyTorch"
 W2C_SCORE, W2C_UNREAD = "w2c_score", "never read (AdditiveAttentin.forward does not use linear_out)"
+V2VR = ("v2vr_pairwise + v2v_warp_split + [conv3x3_sp + v2vr_pool_act] x 3 + conv3x3_sp_s2 + v2vr_pose_head (pose regression over all pairs) + v2vr_consistency (the whole "
+        "weighted EM in one launch) + v2v_warp_split + conv3x3_sp + v2vr_pool_act + conv3x3_sp + v2vr_score_head (attention; its warp also serves the fusion's first "
+        "iteration) + V2VNet's message passing with v2vr_aggregate (weighted sum over the senders)")
+V2VR_TORCH = "PointPillarV2VNetRobust op by op in PyTorch"
+V2VR_HEAD, V2VR_SCORE = "v2vr_pose_head", "v2vr_score_head"
 STRIDED_SHRINK = MIOPEN + " (strided shrink-header convolution: library route)"
 SPLIT_OUT = ", SplitMap out"
 SPARSE_IN = ", sparse canvas in"
@@ -112,12 +117,26 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS, baselines: bool = False) -> Di
                 note(f"{n}.downsample.0", pointwise_text(m.downsample[0].in_channels, terms) if m.skip_pointwise() else MIOPEN + " (skip convolution outside the pointwise kernel's shapes)")
         elif isinstance(m, bb.DoubleConv):
             split, c1, c2 = m.on_split_maps(terms), m.double_conv[0], m.double_conv[2]
-            if isinstance(model, detector.PointPillarBaseline) and not m._layer_ok(c1, bb.conv3x3_shape_ok):      # DoubleConv.forward builds no weight image for it
+            if isinstance(model, (detector.PointPillarBaseline, detector.PointPillarV2VNetRobust)) and not m._layer_ok(c1, bb.conv3x3_shape_ok):      # DoubleConv.forward builds no weight image for it
                 note(f"{n}.double_conv.0", STRIDED_SHRINK if c1.stride != (1, 1) else MIOPEN + " (no weight image for the shape)", True)
                 note(f"{n}.double_conv.2", conv3x3_text(c2, terms))
                 continue
             note(f"{n}.double_conv.0", SP if split and heads_split and m is first_shrink else conv3x3_text(c1, terms) + (SPLIT_OUT if split else ""))
             note(f"{n}.double_conv.2", SP if split else conv3x3_text(c2, terms))
+        elif isinstance(model, detector.PointPillarV2VNetRobust) and isinstance(m, (nn.Conv2d, nn.Linear)) and n.startswith(("pose_reg_net.", "attention_net.", "fusion_net.")):
+            ok = model.kernel_route(model.out_channel, 1, terms)      # one decision for the three parts: the model's forward takes the kernels for all of them or for none
+            if isinstance(m, nn.Linear) and n.startswith("fusion_net."):
+                continue                                                # (fusion_net.mlp: noted with the fusion below)
+            if isinstance(m, nn.Linear):
+                head = V2VR_HEAD + " (all pairs in one workgroup, every row read once, fp32)" if n.startswith("pose_reg_net.") else V2VR_SCORE + " (cropped global max, linear, sigmoid and the weights, fp32)"
+                note(n, head if ok else ROCBLAS.split(" (")[0] + " (nn.Linear, PointPillarV2VNetRobust op by op)", not ok)
+            elif n.startswith("fusion_net."):
+                what = (" (V2VNet: the warped-map and the ego columns as two C -> C convolutions)" if n.endswith("msg_cnn") else
+                        " (V2VNet: update-gate rows of conv_gates stacked on conv_can, one convolution per GRU cell)")
+                note(n, SP + what if ok else MIOPEN + " (V2VNetFusion op by op)", not ok)
+            else:
+                first = " (the warped-map and the ego columns as two C -> hidden convolutions over all pairs; bias, pooling and LeakyReLU in v2vr_pool_act)" if n.endswith("model.0") else ""
+                note(n, (SP_S2 + " (LeakyReLU, pooling and the mean in v2vr_pose_head)" if m.stride[0] == 2 else SP + first) if ok else MIOPEN + " (PointPillarV2VNetRobust op by op)", not ok)
         elif isinstance(m, nn.Conv2d) and n.startswith("fusion_net.") and isinstance(model.fusion_net, DiscoFusion):
             ok = model.fusion_net.kernel_route(model.out_channel)      # the four 1x1 layers of PixelWeightLayer run inside the fusion launch
             note(n, "disco_fuse (pixel-weight MLP layer inside the fusion launch)" if ok else MIOPEN + " (DiscoFusion op by op)", not ok)
@@ -180,7 +199,20 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS, baselines: bool = False) -> Di
                   if detector.compressor_sparse_route(model, terms) else
                   "matrix-core encoder (linearised PFN, split-bf16), persistent dense canvas" if bb.emu_active(terms) else "matrix-core encoder, NCHW strip writer")
     fusion = None
-    if isinstance(getattr(model, "fusion_net", None), V2VNetFusion):         # ONE single-scale module on the shrunk map
+    if isinstance(model, detector.PointPillarV2VNetRobust):                    # pose regression, EM, attention and the weighted V2VNet on the shrunk map
+        f = model.fusion_net
+        ok = model.kernel_route(model.out_channel, 1, terms)
+        note("fusion_net.mlp", pointwise_text(f.mlp.in_features, terms) + ", 1 x 1 on the fused map" if ok else ROCBLAS.split(" (")[0] + " (nn.Linear, V2VNetFusion op by op)", not ok)
+        if ok:
+            fusion = V2VR
+        else:
+            hidden = model.pose_reg_net.pose_regression.model[0].out_channels
+            why = ("the three warps normalise differently (robust vs v2vfusion downsample_rate x discrete_ratio)" if not model.one_normalisation() else
+                   f"{model.out_channel} channels or hidden {hidden} outside C % 64 == 0" if model.out_channel % 64 or hidden % 64 else
+                   "the fusion's own conditions (3 x 3 GRU kernels, widths) or the SplitMap arithmetic (fp16 x 2) is not in force")
+            fusion = V2VR_TORCH + f" ({why})"
+            fallbacks.append("fusion")
+    elif isinstance(getattr(model, "fusion_net", None), V2VNetFusion):         # ONE single-scale module on the shrunk map
         f = model.fusion_net
         ok = f.kernel_route(model.out_channel, 1, terms)
         note("fusion_net.mlp", pointwise_text(f.mlp.in_features, terms) + ", 1 x 1 on the fused map" if ok else ROCBLAS.split(" (")[0] + " (nn.Linear, V2VNetFusion op by op)", not ok)

@@ -62,15 +62,16 @@ def make_poses(rng: np.random.RandomState, n_agents: int, noise: Optional[Sequen
 
 def make_frame(hypes: dict, n_agents: Sequence[int] | int, pillars_per_agent: int = 8000, seed: int = 303,
                num_points_mode: str = "geometric", noise: Optional[Sequence[float]] = None,
-               infra_agent: bool = False, spread_xy=(20.0, 10.0), spread_yaw=30.0) -> Dict:
-    """Batch dict for ``model.forward``.  ``n_agents`` may be a list (one entry per frame in the batch)."""
+               infra_agent: bool = False, spread_xy=(20.0, 10.0), spread_yaw=30.0, with_poses: bool = False) -> Dict:
+    """Batch dict for ``model.forward``.  ``n_agents`` may be a list (one entry per frame in the batch).  ``with_poses``: also ``lidar_pose`` [sum(n), 6] float32,
+    the poses the pairwise matrices were made of (``point_pillar_v2vnet_robust`` builds its own matrices from them)."""
     rng = np.random.RandomState(seed)
     record = [n_agents] if isinstance(n_agents, int) else list(n_agents)
     margs = hypes["model"]["args"]
     nx, ny, _ = [int(v) for v in margs["point_pillar_scatter"]["grid_size"]]
     L = int(hypes.get("train_params", {}).get("max_cav", 5))
     L = max(L, max(record))
-    feats, coords, npts, pair = [], [], [], []
+    feats, coords, npts, pair, all_poses = [], [], [], [], []
     agent = 0
     for n in record:
         for _ in range(n):
@@ -80,6 +81,8 @@ def make_frame(hypes: dict, n_agents: Sequence[int] | int, pillars_per_agent: in
             agent += 1
         poses = make_poses(rng, n, noise=noise, infra_agent=infra_agent, spread_xy=spread_xy, spread_yaw=spread_yaw)
         pair.append(get_pairwise_transformation(poses, L))
+        all_poses.extend(poses)
+    extra = {"lidar_pose": torch.from_numpy(np.stack(all_poses)).float()} if with_poses else {}
     return {
         "processed_lidar": {
             "voxel_features": torch.from_numpy(np.concatenate(feats)),
@@ -88,6 +91,7 @@ def make_frame(hypes: dict, n_agents: Sequence[int] | int, pillars_per_agent: in
         },
         "record_len": torch.tensor(record, dtype=torch.int64),
         "pairwise_t_matrix": torch.from_numpy(np.stack(pair)),
+        **extra,
     }
 
 
@@ -432,3 +436,53 @@ def when2com_parameters_(module: torch.nn.Module, seed: int = 0, input_scale: fl
                 if name in ("attention_net.linear_feat.weight", "attention_net.linear_context.weight"):
                     v = v * float(attention_gain)
             t.copy_(torch.from_numpy(np.ascontiguousarray(v)).to(t.dtype))
+
+
+ATTENTION_LOGIT_GAIN = 1.6
+
+
+def v2v_robust_parameters_(model: torch.nn.Module, seed: int = 0, input_scale: float = 1.0) -> None:
+    """Test weights for the three parts of a ``PointPillarV2VNetRobust`` -- or for anything that has ``fusion_net`` / ``pose_reg_net`` / ``attention_net`` members, or for
+    a lone ``PoseRegressionWraper`` / ``AttentionWrapper`` -- keyed by ``state_dict`` name, that keep every part VISIBLE: the attention's scores spread inside
+    (0.1, 0.9) and differ between pairs, the regression's outputs are of the order of 0.1 - 0.5 m and 1 - 3 degrees, the fusion's weights are ``v2v_parameters_``.
+    Convolutions and hidden linears get unit gain over their fan-in (the first convolution of each net divided by ``input_scale``, the magnitude of the maps), so
+    every activation stays of order one; the attention's last linear has zero-sum weights -- its input is ``hidden`` maxima, all positive and of one common level,
+    which a zero-sum row cancels, leaving the differences between pairs -- with a gain that spreads the logits over about +-1.5; the regression's last linear has
+    rows of gain 0.3 / 0.3 / 2.0."""
+    import zlib
+    nets = []
+    for name in ("pose_reg_net", "attention_net"):
+        if hasattr(model, name) and isinstance(getattr(model, name), torch.nn.Module) and hasattr(getattr(model, name), "downsample_rate"):
+            nets.append(getattr(model, name))
+    if hasattr(model, "fusion_net") and nets:
+        v2v_parameters_(model.fusion_net, seed=seed, input_scale=input_scale)
+    if not nets:
+        nets = [model]
+    with torch.no_grad():
+        for net in nets:
+            sd = net.state_dict()
+            for name in sorted(sd.keys()):
+                t = sd[name]
+                g = torch.Generator().manual_seed((zlib.crc32((type(net).__name__ + "." + name).encode()) + seed) & 0x7FFFFFFF)
+                shape = tuple(t.shape)
+                if name == "alpha":
+                    continue
+                fan_in = t[0].numel() if t.dim() > 1 else t.numel()
+                if name.endswith("bias") and name != "attention_net.model.3.bias":
+                    v = (torch.rand(shape, generator=g) - 0.5) * 0.2
+                elif name.endswith("model.0.weight"):
+                    v = torch.randn(shape, generator=g) * (1.0 / fan_in) ** 0.5 / float(input_scale)
+                elif name == "attention_net.model.3.weight":                       # every output channel with the same gain: the maxima the logit sums share one level
+                    v = torch.randn(shape, generator=g)
+                    v = v - v.flatten(1).mean(dim=1).view(-1, 1, 1, 1)               # (zero-sum rows: the positive mean of the pooled activations cancels)
+                    v = v / v.flatten(1).norm(dim=1).view(-1, 1, 1, 1) * 1.5 ** 0.5
+                elif name == "attention_net.model.3.bias":
+                    v = torch.zeros(shape)
+                elif name == "attention_net.model.8.weight":                       # the logit: zero-sum weights over the pooled maxima, so that their common level cancels
+                    v = torch.randn(shape, generator=g)
+                    v = (v - v.mean()) * ATTENTION_LOGIT_GAIN / fan_in ** 0.5
+                elif name == "pose_regression.model.18.weight":
+                    v = torch.randn(shape, generator=g) * (1.0 / fan_in) ** 0.5 * torch.tensor([[0.3], [0.3], [2.0]])
+                else:
+                    v = torch.randn(shape, generator=g) * (1.5 / fan_in) ** 0.5
+                t.copy_(v.to(t.dtype))
