@@ -29,7 +29,7 @@ LAB_LIB_PATH = os.path.join(LIB_DIR, "libcoalign_hip_lab.so")
 # cause).  `python -m coalign_amd.build --labvec`; COALIGN_LAB=vec loads it.  tools/pk_f32_recheck.sh runs the experiment.
 LABVEC_LIB_PATH = os.path.join(LIB_DIR, "libcoalign_hip_labvec.so")
 INCLUDE = os.path.join(REPO, "include")
-SOURCES = ["status.cpp", "pillar_scatter.hip", "pillar_sparse.hip", "warp_fuse.hip", "warp_fuse_nhwc.hip", "disco_fuse.hip", "v2v_fuse.hip", "v2v_robust.hip", "v2x_attn.hip", "v2x_window.hip", "w2c_fuse.hip", "decode.hip", "nms.hip", "epilogue.hip", "voxelize.hip", "pose_graph.hip", "pose_graph_build.hip", "conv3x3.hip", "conv3x3_emu.hip", "conv3x3_sp.hip", "conv3x3_sp_s2.hip", "conv3x3_narrow.hip", "pointwise.hip"]
+SOURCES = ["status.cpp", "pillar_scatter.hip", "pillar_sparse.hip", "warp_fuse.hip", "warp_fuse_nhwc.hip", "disco_fuse.hip", "v2v_fuse.hip", "v2v_robust.hip", "v2x_attn.hip", "v2x_window.hip", "w2c_fuse.hip", "w2comm.hip", "decode.hip", "nms.hip", "epilogue.hip", "voxelize.hip", "pose_graph.hip", "pose_graph_build.hip", "conv3x3.hip", "conv3x3_emu.hip", "conv3x3_sp.hip", "conv3x3_sp_s2.hip", "conv3x3_narrow.hip", "pointwise.hip"]
 # Kernels that were measured and NOT adopted live in the laboratory library only: the Winograd F(2x2, 3x3) convolution (1.14 x / 0.89 x / 1.05 x
 # against the direct kernel per stage) -- include/coalign_amd_lab.h, coalign_amd.hip.lab_lib(), tests/test_round4_gpu.py keep it testable.
 LAB_ONLY_SOURCES = ["conv3x3_wino.hip"]
@@ -68,7 +68,7 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False, vectori
     flags = [f for f in FLAGS if not (vectorize and f in ("-fno-slp-vectorize", "-fno-vectorize"))]
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(LIB_DIR, exist_ok=True)
-    headers = [os.path.join(INCLUDE, "coalign_amd.h"), os.path.join(INCLUDE, "coalign_amd_lab.h"), os.path.join(INCLUDE, "coalign_amd_narrow.h"), os.path.join(INCLUDE, "coalign_amd_narrow_sparse.h"), os.path.join(INCLUDE, "coalign_amd_align.h"), os.path.join(INCLUDE, "coalign_amd_stage1.h"), os.path.join(INCLUDE, "coalign_amd_disco.h"), os.path.join(INCLUDE, "coalign_amd_v2v.h"), os.path.join(INCLUDE, "coalign_amd_v2x.h"), os.path.join(INCLUDE, "coalign_amd_v2x_window.h"), os.path.join(INCLUDE, "coalign_amd_w2c.h"), os.path.join(INCLUDE, "coalign_amd_v2v_robust.h"), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "v2x_tiles.h"), os.path.join(CSRC, "warp_taps.h"), os.path.join(CSRC, "v2v_lanes.h"), os.path.join(CSRC, "stage1_internal.h"), os.path.abspath(__file__)]
+    headers = [os.path.join(INCLUDE, "coalign_amd.h"), os.path.join(INCLUDE, "coalign_amd_lab.h"), os.path.join(INCLUDE, "coalign_amd_narrow.h"), os.path.join(INCLUDE, "coalign_amd_narrow_sparse.h"), os.path.join(INCLUDE, "coalign_amd_align.h"), os.path.join(INCLUDE, "coalign_amd_stage1.h"), os.path.join(INCLUDE, "coalign_amd_disco.h"), os.path.join(INCLUDE, "coalign_amd_v2v.h"), os.path.join(INCLUDE, "coalign_amd_v2x.h"), os.path.join(INCLUDE, "coalign_amd_v2x_window.h"), os.path.join(INCLUDE, "coalign_amd_w2c.h"), os.path.join(INCLUDE, "coalign_amd_v2v_robust.h"), os.path.join(INCLUDE, "coalign_amd_where2comm.h"), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "v2x_tiles.h"), os.path.join(CSRC, "warp_taps.h"), os.path.join(CSRC, "nhwc_lanes.h"), os.path.join(CSRC, "v2v_lanes.h"), os.path.join(CSRC, "stage1_internal.h"), os.path.abspath(__file__)]
     hipcc = _hipcc()
 
     def compile_one(src: str) -> str:

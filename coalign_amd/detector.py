@@ -21,7 +21,7 @@ from . import backbone as _bb
 from . import ops
 from .backbone import BaseBEVBackbone, BasicBlock, DownsampleConv, NaiveCompressor, ResNetBEVBackbone, _cache_of, _fast_ok
 from .encoder import PillarVFE, PointPillarScatter, host_ints
-from .fusion import AttFusion, DiscoFusion, MaxFusion, V2VNetFusion, V2XViTFusion, When2comFusion, fuse_multiscale
+from .fusion import AttFusion, DiscoFusion, MaxFusion, V2VNetFusion, V2XViTFusion, When2comFusion, Where2commFusion, fuse_multiscale
 from . import v2v_robust
 from .pose import generate_noise_torch, get_pairwise_transformation_torch, normalize_pairwise_tfm
 from .v2v_robust import AttentionWrapper, PoseRegressionWraper
@@ -178,6 +178,11 @@ class PointPillarBaselineMultiscale(nn.Module):
 
     def encode(self, data_dict: dict):
         """Per-agent part: pillars -> canvas -> multiscale features.  Returns (feature list, normalised affine)."""
+        spatial_features, affine = self._spatial_features(data_dict)
+        return self.backbone.get_multiscale_feature(spatial_features), affine
+
+    def _spatial_features(self, data_dict: dict):
+        """pillars -> canvas (-> compressor): what the backbone reads, and the normalised affine."""
         batch_dict = _single_agent_batch(dict(data_dict, record_len=host_ints(data_dict["record_len"])))      # (with the device voxeliser's streaming keys and FramePipeline's frame record)
         # round 4: the encoder hands a SparseCanvas (one launch, no dense canvas) to a backbone whose first block reads it
         resnet = getattr(self.backbone, "resnet", None)
@@ -197,7 +202,7 @@ class PointPillarBaselineMultiscale(nn.Module):
             opener = resnet.layer0[0] if resnet is not None and hasattr(resnet, "layer0") else None
             want_split = bool(not self.training and isinstance(opener, BasicBlock) and opener.takes_split_maps() and opener.conv1.in_channels % 16 == 0)
             spatial_features = self.naive_compressor(spatial_features, out_split=True) if want_split else self.naive_compressor(spatial_features)
-        return self.backbone.get_multiscale_feature(spatial_features), affine
+        return spatial_features, affine
 
     def _fuse_scales(self, feature_list, record_len, affine, rows=None):
         """The per-scale fusion launches are independent: on the GPU the coarser scales (few workgroups, latency bound)
@@ -451,6 +456,95 @@ class PointPillarBaseline(nn.Module):
         return self.fuse_and_head(feats, record_len, affine)
 
 
+class PointPillarWhere2comm(PointPillarBaselineMultiscale):
+    """Where2comm on PointPillars.  THIS MODEL CLASS IS THIS PROJECT'S: the reference snapshot ships the fusion module (``Where2comm``,
+    opencood/models/fuse_modules/where2comm_attn.py:174-341, with ``Communication``, opencood/models/comm_modules/where2comm.py:9-78) and neither a model class nor
+    a yaml that constructs it.  Layout and constructor keys are ``PointPillarBaselineMultiscale``'s -- pillar encoder, ``ResNetBEVBackbone`` or ``BaseBEVBackbone``,
+    optional shrink header and compressor, 1 x 1 heads -- with a ``where2comm`` section (the module's argument dict) in place of ``fusion_method``; ``fusion_net`` is
+    ONE ``fusion.Where2commFusion``.
+
+    Forward: every agent's multi-scale maps; decode, shrink header and ``cls_head`` on EVERY agent give the single-agent logits the masks are made of;
+    ``multi_scale: true``: masked fusion of the backbone's levels, then decode, shrink header and heads on the fused map; otherwise: masked fusion of the agents'
+    shrunk maps, then the heads.  Output: the other models' dict plus ``comm_rates``, a 0-d device tensor.  ``encode`` / ``fuse_and_head`` and the two ``accepts_*``
+    flags keep ``PointPillarBaselineMultiscale``'s contracts; the single-agent logits travel as the LAST entry of the feature list."""
+
+    def __init__(self, args: dict):
+        if "where2comm" not in args:
+            raise NotImplementedError("point_pillar_where2comm needs the model's 'where2comm' section (the arguments of the Where2comm module), which this config lacks")
+        super().__init__(dict(args, fusion_method="max"))          # (the parent's per-level list of parameter-free modules is replaced right below)
+        del self.fusion_net
+        self.fusion_net = Where2commFusion(args["where2comm"])
+        self.multi_scale = bool(self.fusion_net.multi_scale)
+        if self.multi_scale and self.fusion_net.num_levels != self.backbone.num_levels:
+            raise ValueError(f"where2comm.layer_nums names {self.fusion_net.num_levels} levels, the backbone has {self.backbone.num_levels}")
+
+    def _fusion_channels(self) -> list:
+        return [b[0].conv1.out_channels if isinstance(b[0], BasicBlock) else b[1].out_channels for b in self._levels()] if self.multi_scale else [self.out_channel]
+
+    def _levels(self):
+        resnet = getattr(self.backbone, "resnet", None)
+        return [getattr(resnet, f"layer{i}") for i in range(resnet.layernum)] if resnet is not None else list(self.backbone.blocks)
+
+    def kernel_route(self, n_agents: int = 1) -> bool:
+        """The static half of the fusion's decision (``routes.plan`` asks it): the module's, on this model's widths, backbone kind and anchor count."""
+        return self.fusion_net.kernel_route(self._fusion_channels(), n_agents, hasattr(self.backbone, "resnet"), self.cls_head.out_channels)
+
+    def kernel_route_reason(self) -> Optional[str]:
+        """Why ``kernel_route`` says no, in words (None when it says yes, or for the module's mode alone)."""
+        f, ch = self.fusion_net, self._fusion_channels()
+        if f.multi_scale and not hasattr(self.backbone, "resnet"):
+            return "a plain BaseBEVBackbone feeds every block the masked map of the one before: the levels cannot be fused in one launch"
+        if len(ch) > 3 or any(c not in (64, 128, 256) for c in ch):
+            return f"maps of {ch} channels outside the kernel's 64 / 128 / 256, at most three levels"
+        mods = list(f.fuse_modules) if f.multi_scale else [f.fuse_modules]
+        if any(getattr(m, "feature_dim", c) != c for m, c in zip(mods, ch)):
+            return "an attention whose feature_dim differs from its map's channels"
+        if f.communication and not ops.w2comm_masks_shape_ok(self.cls_head.out_channels, [1], f.naive_communication.kernel_size(), len(ch)):
+            return "a smoothing kernel (even, or larger than 9) or an anchor count (more than 8) the mask kernel does not take"
+        return None
+
+    def _decode_shrink(self, feats, for_heads: bool):
+        """Up-sampling heads and shrink header: on every agent's levels (for the logits and the single-scale fusion: a float32 map) or on the fused levels."""
+        want_split = bool(self.shrink_flag and len(feats) > 0 and all(getattr(m, "is_cuda", False) for m in feats) and self.shrink_conv.takes_split_maps())
+        x = self.backbone.decode_multiscale_feature(feats, out_split=True) if want_split else self.backbone.decode_multiscale_feature(feats)
+        if self.shrink_flag:
+            x = self.shrink_conv(x, out_split=for_heads and isinstance(x, ops.SplitMap) and heads_take_split_map(self))
+        elif isinstance(x, ops.SplitMap):
+            x = x.dense()
+        return x
+
+    def encode(self, data_dict: dict):
+        """Per-agent part.  Returns ([the maps the fusion reads ..., the single-agent logits], normalised affine): the backbone's levels in multi-scale mode on a
+        backbone with ``.resnet``, the canvas on a plain ``BaseBEVBackbone`` (whose later blocks read the MASKED maps, where2comm_attn.py:262), else the shrunk map."""
+        spatial_features, affine = self._spatial_features(data_dict)
+        feats = self.backbone.get_multiscale_feature(spatial_features)
+        x = self._decode_shrink(feats, for_heads=False)
+        psm = _run_heads(self, x)["cls_preds"]
+        if not self.multi_scale:
+            return [x, psm], affine
+        if hasattr(self.backbone, "resnet"):
+            return [*feats, psm], affine
+        return [spatial_features.dense() if isinstance(spatial_features, (ops.SparseCanvas, ops.SplitMap)) else spatial_features, psm], affine
+
+    def fuse_and_head(self, feature_list, record_len, affine, rows=None) -> dict:
+        """Ego part: the masked fusion, (decode and shrink header,) the heads."""
+        *maps, psm = feature_list
+        if not self.multi_scale:
+            x, rates, _ = self.fusion_net.fuse(maps[0], psm, record_len, affine, rows=rows)
+        elif hasattr(self.backbone, "resnet"):
+            fused, rates = self.fusion_net.fuse(None, psm, record_len, affine, self.backbone, feats=maps, rows=rows, decode=False)
+            x = self._decode_shrink(fused, for_heads=True) if isinstance(fused, list) else self._shrink_decoded(fused)
+        else:
+            x, rates, _ = self.fusion_net.fuse(maps[0], psm, record_len, affine, self.backbone, rows=rows)
+            x = self._shrink_decoded(x)
+        out = _run_heads(self, x)
+        out["comm_rates"] = torch.as_tensor(rates, device=psm.device)
+        return out
+
+    def _shrink_decoded(self, x):
+        return self.shrink_conv(x) if self.shrink_flag else x
+
+
 class PointPillarV2VNetRobust(nn.Module):
     """V2VNet with learned pose correction (opencood/models/point_pillar_v2vnet_robust.py:21-332), the baseline CoAlign is compared with under pose noise: pillar
     encoder, ``BaseBEVBackbone``, shrink header, optional ``NaiveCompressor(256, rate)`` when the integer ``compression`` > 0, then on the shrunk maps the pose
@@ -699,6 +793,7 @@ BASELINE_REGISTRY = {
     "point_pillar_disconet": PointPillarDiscoNet,
     "point_pillar_baseline": PointPillarBaseline,
     "point_pillar_v2vnet_robust": PointPillarV2VNetRobust,
+    "point_pillar_where2comm": PointPillarWhere2comm,
 }
 
 

@@ -7,7 +7,8 @@ parameters; all their arithmetic is the fused gfx950 kernel ``coalign_warp_fuse`
 (opencood/models/fuse_modules/disco_fuse.py:76-99) and runs on ``coalign_disco_fuse``.  ``V2VNetFusion`` owns ``msg_cnn``, a ``ConvGRU``
 (opencood/models/sub_modules/convgru.py) and ``mlp``; its convolutions run on ``coalign_conv3x3_sp``, what lies between them on the three ``coalign_v2v_*`` kernels.
 ``V2XViTFusion`` (fusion_in_one.py:295-352) and its transformer blocks live in :mod:`coalign_amd.v2xvit` and are re-exported here, as is ``When2comFusion``
-(``When2commFusion``, fusion_in_one.py:354-431) of :mod:`coalign_amd.when2com`.
+(``When2commFusion``, fusion_in_one.py:354-431) of :mod:`coalign_amd.when2com` and ``Where2commFusion`` (``Where2comm``, fuse_modules/where2comm_attn.py:174-341) of
+:mod:`coalign_amd.where2comm`.
 """
 from __future__ import annotations
 
@@ -23,6 +24,7 @@ from .backbone import Conv3x3Pack, PointwisePack, _cache_of, fold_bn
 from .encoder import host_ints
 from .v2xvit import V2XViTFusion  # noqa: F401  (fusion.V2XViTFusion: the house address of every fusion module)
 from .when2com import When2comFusion  # noqa: F401  (fusion.When2comFusion)
+from .where2comm import Where2comm as Where2commFusion  # noqa: F401  (fusion.Where2commFusion: the name the reference's lss_submodule.py imports)
 
 
 def regroup(x: torch.Tensor, record_len) -> List[torch.Tensor]:

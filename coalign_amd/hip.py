@@ -186,6 +186,14 @@ V2VR_SIGNATURES = {
     "coalign_v2vr_aggregate": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P, P, P]),
 }
 
+# include/coalign_amd_where2comm.h: the eleventh extension header of ABI version 2 (product library): Where2comm's confidence-masked fusion -- the communication
+# masks and rates of every agent at every backbone level in one launch, the warp and fusion of the masked maps in one launch per frame (csrc/w2comm.hip)
+W2COMM_SIGNATURES = {
+    "coalign_w2comm_masks": (c_int, [P, c_int, c_int, c_int, c_int, POINTER(c_int32), c_int, P, P, c_int, c_float, c_int, POINTER(P), P, P]),
+    "coalign_w2comm_fuse_nhwc": (c_int, [c_int, POINTER(P), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(P), POINTER(P), POINTER(c_int32),
+                                         POINTER(c_int32), c_int, P, POINTER(c_int32), c_int, P]),
+}
+
 _LAB_LIB = None
 
 
@@ -212,7 +220,7 @@ def lib() -> ctypes.CDLL:
             raise CoalignHipError(
                 f"{path} is missing and could not be built ({exc}); the CoAlign hot path has no CPU fallback") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **V2X_WINDOW_SIGNATURES, **W2C_SIGNATURES, **V2VR_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **V2X_WINDOW_SIGNATURES, **W2C_SIGNATURES, **V2VR_SIGNATURES, **W2COMM_SIGNATURES}.items():
         fn = getattr(handle, name)  # AttributeError here == header / library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -236,7 +244,7 @@ def lab_lib() -> ctypes.CDLL:
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(f"{path} is missing and could not be built ({exc})") from exc
     handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **V2X_WINDOW_SIGNATURES, **W2C_SIGNATURES, **V2VR_SIGNATURES, **LAB_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **V2X_WINDOW_SIGNATURES, **W2C_SIGNATURES, **V2VR_SIGNATURES, **W2COMM_SIGNATURES, **LAB_SIGNATURES}.items():
         fn = getattr(handle, name)
         fn.restype = res
         fn.argtypes = args

@@ -16,7 +16,7 @@ import sys
 import types
 from typing import Dict
 
-from . import backbone, box_align, config, detector, encoder, evaluation, fusion, pcdet, pose, postprocess, preprocess, v2v_robust
+from . import backbone, box_align, config, detector, encoder, evaluation, fusion, pcdet, pose, postprocess, preprocess, v2v_robust, where2comm
 
 # dotted module name -> {attribute: object}
 _EXPORTS: Dict[str, Dict[str, object]] = {
@@ -26,6 +26,9 @@ _EXPORTS: Dict[str, Dict[str, object]] = {
     "opencood.models.point_pillar_disconet": {"PointPillarDiscoNet": detector.PointPillarDiscoNet},
     "opencood.models.point_pillar_baseline": {"PointPillarBaseline": detector.PointPillarBaseline},
     "opencood.models.point_pillar_v2vnet_robust": {"PointPillarV2VNetRobust": detector.PointPillarV2VNetRobust},
+    "opencood.models.fuse_modules.where2comm_attn": {"Where2comm": where2comm.Where2comm, "AttenFusion": where2comm.AttenFusion, "MaxFusion": where2comm.MaxFusion,
+                                                    "ScaledDotProductAttention": where2comm.ScaledDotProductAttention},
+    "opencood.models.comm_modules.where2comm": {"Communication": where2comm.Communication},
     "opencood.models.fuse_modules.v2v_fuse": {"V2VNetFusion": fusion.V2VNetFusion},
     "opencood.models.sub_modules.v2v_robust_module": {"PoseRegression": v2v_robust.PoseRegression, "PoseRegressionWraper": v2v_robust.PoseRegressionWraper,
                                                        "Attention": v2v_robust.Attention, "AttentionWrapper": v2v_robust.AttentionWrapper,

@@ -1991,3 +1991,77 @@ def v2vr_aggregate(a: torch.Tensor, e: torch.Tensor, x: torch.Tensor, theta: tor
         hip.check(hip.lib().coalign_v2vr_aggregate(_ptr(a), _ptr(e), _ptr(x), n, R, C, H, W, _ptr(th), _ptr(weight), int(weight.shape[1]), V2V_OUT_SP if gru else V2V_OUT_NHWC,
                                                    _ptr(out.data if gru else out), _ptr(sp_range_flag(e.device)) if gru else None, _stream()), "coalign_v2vr_aggregate")
     return out
+
+
+# ---- Where2comm's confidence-masked fusion (include/coalign_amd_where2comm.h, csrc/w2comm.hip) ------------------------------------------------------------------
+W2COMM_MAX_GROUPS, W2COMM_MAX_K, W2COMM_MAX_LEVELS, W2COMM_MAX_ANCHORS = 64, 9, 3, 8
+
+
+def w2comm_masks_shape_ok(anchors: int, group_len: Sequence[int], k: int, levels: int, hw=None) -> bool:
+    """What ``coalign_w2comm_masks`` takes: 1 .. 8 anchors, 1 .. 64 frames of 1 .. 8 agents, k = 0 or odd and <= 9, 1 .. 3 levels that every halving leaves a pixel."""
+    ok = 1 <= anchors <= W2COMM_MAX_ANCHORS and 1 <= len(group_len) <= W2COMM_MAX_GROUPS and all(1 <= int(g) <= 8 for g in group_len)
+    ok = ok and (k == 0 or (k % 2 == 1 and 0 < k <= W2COMM_MAX_K)) and 1 <= levels <= W2COMM_MAX_LEVELS
+    return bool(ok and (hw is None or (hw[0] >> (levels - 1) >= 1 and hw[1] >> (levels - 1) >= 1)))
+
+
+@_device_op
+def w2comm_masks(psm: torch.Tensor, group_len: Sequence[int], weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], thre: float, levels: int = 1):
+    """The communication masks and rates of a batch in one launch (``coalign_w2comm_masks``): psm [n_total, A, H, W] float32, the single-agent classification logits;
+    ``weight`` [k, k] (any leading ones: ``gaussian_filter.weight`` as stored) and ``bias`` [1] float32 on the device, or both None for no smoothing ->
+    (masks: per level l a uint8 tensor [n_total, H >> l, W >> l] of 0 / 1, rates [len(group_len)] float32)."""
+    _need_gpu(psm, weight, bias)
+    if psm.dim() != 4 or psm.dtype != torch.float32:
+        raise ValueError("w2comm_masks: psm [n_total, A, H, W] float32")
+    p = psm.contiguous()
+    n_total, A, H, W = p.shape
+    groups = [int(g) for g in group_len]
+    k = 0
+    if weight is not None:
+        k = int(weight.shape[-1])
+        if bias is None or weight.numel() != k * k or bias.numel() != 1 or weight.dtype != torch.float32 or bias.dtype != torch.float32 or weight.device != p.device or bias.device != p.device:
+            raise ValueError("w2comm_masks: weight [k, k] and bias [1] float32 on the map's device")
+        weight, bias = weight.contiguous(), bias.contiguous()
+    if sum(groups) != n_total:
+        raise ValueError("w2comm_masks: group_len must sum to psm's agents")
+    levels = int(levels)
+    masks = [torch.empty((n_total, H >> l, W >> l), dtype=torch.uint8, device=p.device) for l in range(max(0, min(levels, W2COMM_MAX_LEVELS)))]
+    rates = torch.empty(len(groups), dtype=torch.float32, device=p.device)
+    gl = (ctypes.c_int32 * max(1, len(groups)))(*groups)
+    mp = (ctypes.c_void_p * max(1, len(masks)))(*[m.data_ptr() for m in masks])
+    with _Timed("w2comm_masks"):
+        hip.check(hip.lib().coalign_w2comm_masks(_ptr(p), n_total, A, H, W, gl, len(groups), _ptr(weight), _ptr(bias), k, float(thre), levels, mp, _ptr(rates),
+                                                 _stream()), "coalign_w2comm_masks")
+    return masks, rates
+
+
+@_device_op
+def w2comm_fuse_nhwc(xs: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], theta: torch.Tensor, mode: int, rows: Optional[Sequence[int]] = None) -> list:
+    """``warp_fuse_nhwc`` of ONE frame on maps multiplied by their masks, without the product (``coalign_w2comm_fuse_nhwc``): ``xs[i]`` [n, C_i, H_i, W_i] channels-last
+    float32, ``masks[i]`` [n, H_i, W_i] uint8 (row r belongs to row r of ``xs[i]``), theta [n, 2, 3] f64, mode FUSE_ATT / FUSE_MAX -> per scale [1, C_i, H_i, W_i]
+    channels-last."""
+    _need_gpu(*xs, *masks, theta)
+    k = len(xs)
+    n = xs[0].shape[0]
+    if not 1 <= k <= 3 or any(not warp_fuse_nhwc_ok(x) or x.shape[0] != n for x in xs):
+        raise ValueError("w2comm_fuse_nhwc needs 1-3 channels-last float32 maps [n <= 8, C in {64, 128, 256}, H, W] of one frame")
+    if len(masks) != k or any(m.dtype != torch.uint8 or tuple(m.shape) != (n, x.shape[2], x.shape[3]) or not m.is_contiguous() or m.device != x.device for m, x in zip(masks, xs)):
+        raise ValueError("w2comm_fuse_nhwc: one contiguous uint8 mask [n, H, W] per map, on the map's device")
+    if mode not in (FUSE_ATT, FUSE_MAX):
+        raise ValueError("w2comm_fuse_nhwc fuses (FUSE_ATT | FUSE_MAX)")
+    th = theta.to(device=xs[0].device, dtype=torch.float64).contiguous()
+    if th.shape[0] != n:
+        raise ValueError("one theta row per agent")
+    outs = [torch.empty((1, x.shape[1], x.shape[2], x.shape[3]), dtype=torch.float32, device=x.device, memory_format=torch.channels_last) for x in xs]
+    vp = ctypes.c_void_p * k
+    i32 = ctypes.c_int32 * k
+    rw = None
+    if rows is not None:
+        if len(rows) != n:
+            raise ValueError("rows must have one entry per agent")
+        rw = (ctypes.c_int32 * n)(*[int(r) for r in rows])
+    with _Timed("w2comm_fuse_nhwc"):
+        hip.check(hip.lib().coalign_w2comm_fuse_nhwc(k, vp(*[x.data_ptr() for x in xs]), i32(*[x.shape[1] for x in xs]), i32(*[x.shape[2] for x in xs]),
+                                                     i32(*[x.shape[3] for x in xs]), vp(*[m.data_ptr() for m in masks]), vp(*[o.data_ptr() for o in outs]),
+                                                     i32(*[x.shape[2] for x in xs]), i32(*[x.shape[3] for x in xs]), n, _ptr(th), rw, mode, _stream()),
+                  "coalign_w2comm_fuse_nhwc")
+    return outs

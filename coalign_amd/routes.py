@@ -3,7 +3,7 @@
 The detector picks its kernels per layer at run time; a layer whose shape a hand-written kernel does not take falls back to MIOpen / the per-scale NCHW fusion kernel /
 the fp32 VALU encoder -- correct, slower, and until round 3 silent.  ``plan(hypes)`` builds the model of a hypes dictionary, asks every module the decision function its
 ``forward`` dispatches on (``backbone.conv3x3_route`` / ``pointwise_split``, ``BasicBlock.route``, ``DoubleConv.on_split_maps``, the decode mixin's ``heads_pointwise`` /
-``heads_write_split``, ``NaiveCompressor.split_widths``, ``detector.heads_route`` / ``sparse_canvas_route`` / ``compressor_sparse_route`` / ``fusion_route``, ``DiscoFusion.kernel_route``, ``V2VNetFusion.kernel_route``, ``V2XViTFusion.kernel_route`` / ``window_kernel_reason``, ``When2comFusion.kernel_route`` / ``kernel_shape_reason``, ``PillarVFE.matrix_core_ok``) with the arithmetic
+``heads_write_split``, ``NaiveCompressor.split_widths``, ``detector.heads_route`` / ``sparse_canvas_route`` / ``compressor_sparse_route`` / ``fusion_route``, ``DiscoFusion.kernel_route``, ``V2VNetFusion.kernel_route``, ``V2XViTFusion.kernel_route`` / ``window_kernel_reason``, ``When2comFusion.kernel_route`` / ``kernel_shape_reason``, ``PointPillarWhere2comm.kernel_route`` / ``kernel_route_reason``, ``PillarVFE.matrix_core_ok``) with the arithmetic
 mode passed in, and words the answers -- this module holds no shape rule of its own -- so that a yaml that would leave the fast path shows up in a CPU test
 (tests/test_host_cpu.py walks the reference's ``hypes_yaml/**/pointpillar*.yaml`` with it) instead of in a profile.
 The line of the merged 1x1 heads names the kernel that reads a float32 map (pointwise within its Cin limit, else rocBLAS, listed as a fallback): where a one-layer shrink header
@@ -22,7 +22,7 @@ import torch.nn as nn
 from . import backbone as bb
 from . import detector
 from .detector import BASELINE_REGISTRY, MODEL_REGISTRY, build_model
-from .fusion import DiscoFusion, V2VNetFusion, V2XViTFusion, When2comFusion
+from .fusion import DiscoFusion, V2VNetFusion, V2XViTFusion, When2comFusion, Where2commFusion
 
 EMU, F32, MIOPEN, ROCBLAS, POINTWISE = "conv3x3_emu (split 16-bit matrix cores)", "conv3x3 (fp32 matrix cores) / MIOpen by shape", "MIOpen", "rocBLAS (1x1 heads)", "pointwise"
 WINO = "conv3x3_wino (Winograd F(2x2,3x3), split-bf16 matrix cores)"
@@ -51,6 +51,11 @@ V2VR = ("v2vr_pairwise + v2v_warp_split + [conv3x3_sp + v2vr_pool_act] x 3 + con
         "iteration) + V2VNet's message passing with v2vr_aggregate (weighted sum over the senders)")
 V2VR_TORCH = "PointPillarV2VNetRobust op by op in PyTorch"
 V2VR_HEAD, V2VR_SCORE = "v2vr_pose_head", "v2vr_score_head"
+W2COMM = ("w2comm_masks + w2comm_fuse_nhwc: the communication masks of every agent and level and the rates in one launch, then per frame the warp and fusion of "
+          "the masked maps of all levels in one launch (channels-last; no masked map is written)")
+W2COMM_PLAIN = "warp_fuse_nhwc: all scales in one launch (channels-last); no communication section: no masks, rate 0"
+W2COMM_TORCH = "Where2comm op by op in PyTorch"
+W2COMM_MASKS = "w2comm_masks (the smoothing runs inside the mask launch, fp32)"
 STRIDED_SHRINK = MIOPEN + " (strided shrink-header convolution: library route)"
 SPLIT_OUT = ", SplitMap out"
 SPARSE_IN = ", sparse canvas in"
@@ -160,6 +165,9 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS, baselines: bool = False) -> Di
                 note(n, f"{W2C_SCORE} ({part}, fp32)", False)
             else:
                 note(n, ROCBLAS.split(" (")[0] + " (nn.Linear, When2comFusion op by op)", True)
+        elif isinstance(m, nn.Conv2d) and n.startswith("fusion_net.") and isinstance(model.fusion_net, Where2commFusion):      # naive_communication.gaussian_filter
+            ok = model.kernel_route()
+            note(n, W2COMM_MASKS if ok else MIOPEN + " (Where2comm op by op)", not ok)
         elif isinstance(m, nn.Linear) and n.startswith("fusion_net.") and isinstance(model.fusion_net, V2XViTFusion):
             ok = model.fusion_net.kernel_route(model.out_channel)
             leaf = n.split(".")
@@ -237,6 +245,13 @@ def plan(hypes: dict, terms: int = DEFAULT_TERMS, baselines: bool = False) -> Di
             fusion = W2C
         else:
             fusion = W2C_TORCH + f" ({f.kernel_shape_reason(model.out_channel, 1, terms) or 'training mode or force_torch'})"
+            fallbacks.append("fusion")
+    elif isinstance(getattr(model, "fusion_net", None), Where2commFusion):     # ONE module: the backbone's levels (multi_scale) or the shrunk map
+        f = model.fusion_net
+        if model.kernel_route() and (not f.multi_scale or (bb.NHWC_STAGE_OUTPUTS and bb.emu_active(terms))):      # (channels-last stage outputs)
+            fusion = W2COMM if f.communication else W2COMM_PLAIN
+        else:
+            fusion = W2COMM_TORCH + f" ({model.kernel_route_reason() or 'stage outputs not channels-last, training mode or force_torch'})"
             fallbacks.append("fusion")
     elif isinstance(getattr(model, "fusion_net", None), (detector.MaxFusion, detector.AttFusion)):      # point_pillar_baseline: ONE module, the NCHW kernel
         fusion = "warp_fuse: one launch (NCHW, LDS-staged patches)"
