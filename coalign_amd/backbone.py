@@ -222,6 +222,21 @@ def pointwise_split(cin: int, terms: Optional[int] = None) -> bool:
     return bool(POINTWISE_EMU and _terms(terms) in (3, 16) and cin % 16 == 0)
 
 
+# The names ``routes.plan`` prints for the kernels several families share (a family's own wording lives beside its route decision: the ``plan_fusion`` / ``plan_layer``
+# hooks of the fusion modules and of the two models decided at model level); ``routes`` re-exports them.
+MIOPEN, ROCBLAS, POINTWISE = "MIOpen", "rocBLAS (1x1 heads)", "pointwise"
+LINEAR_LIBRARY = ROCBLAS.split(" (")[0] + " (nn.Linear"
+SP = "conv3x3_sp (SplitMap input: operands by LDS-DMA, fp16 x 2)"
+SP_S2 = "conv3x3_sp_s2 (SplitMap input and output, stride 2, fp16 x 2)"
+SPLIT_OUT = ", SplitMap out"
+TORCH_MODE = "training mode or force_torch"      # why a family is op by op when its ``kernel_shape_reason`` has nothing to say
+
+
+def pointwise_text(cin: int, terms: Optional[int]) -> str:
+    """``pointwise_split`` in words."""
+    return POINTWISE + (" (split-bf16 matrix cores)" if pointwise_split(cin, terms) else " (fp32 matrix cores)")
+
+
 def conv3x3_shape_ok(cin: int, cout: int, stride: int = 1) -> bool:      # a Conv3x3Pack is built for these layers and no others
     return cout % 64 == 0 and cin % 8 == 0 and stride in (1, 2)
 

@@ -8,6 +8,7 @@ explicit ``fmaf`` where fusing is wanted) and so the float64 NMS clipping is bit
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -34,6 +35,8 @@ SOURCES = ["status.cpp", "pillar_scatter.hip", "pillar_sparse.hip", "warp_fuse.h
 # against the direct kernel per stage) -- include/coalign_amd_lab.h, coalign_amd.hip.lab_lib(), tests/test_round4_gpu.py keep it testable.
 LAB_ONLY_SOURCES = ["conv3x3_wino.hip"]
 ARCH = "gfx950"
+# include/: one header per signature table of coalign_amd.hip (its HEADERS mapping is keyed by these names, in this order; the laboratory header comes last)
+ABI_HEADERS = ("coalign_amd.h", "coalign_amd_narrow.h", "coalign_amd_narrow_sparse.h", "coalign_amd_align.h", "coalign_amd_stage1.h", "coalign_amd_disco.h", "coalign_amd_v2v.h", "coalign_amd_v2x.h", "coalign_amd_v2x_window.h", "coalign_amd_w2c.h", "coalign_amd_v2v_robust.h", "coalign_amd_where2comm.h", "coalign_amd_lab.h")
 # per-source extras.  pillar_scatter.hip: its matrix-core encoder reduces the accumulators with VALU right after each instruction
 # pair -- results in VGPRs (not AGPRs) save 64 v_accvgpr_read per pass; -fno-honor-nans drops the canonicalising v_max the compiler
 # puts in front of every two-operand fmaxf of a raw matrix result (20 per pass; the file tests for NaN nowhere, its selects are explicit).
@@ -68,7 +71,8 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False, vectori
     flags = [f for f in FLAGS if not (vectorize and f in ("-fno-slp-vectorize", "-fno-vectorize"))]
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(LIB_DIR, exist_ok=True)
-    headers = [os.path.join(INCLUDE, "coalign_amd.h"), os.path.join(INCLUDE, "coalign_amd_lab.h"), os.path.join(INCLUDE, "coalign_amd_narrow.h"), os.path.join(INCLUDE, "coalign_amd_narrow_sparse.h"), os.path.join(INCLUDE, "coalign_amd_align.h"), os.path.join(INCLUDE, "coalign_amd_stage1.h"), os.path.join(INCLUDE, "coalign_amd_disco.h"), os.path.join(INCLUDE, "coalign_amd_v2v.h"), os.path.join(INCLUDE, "coalign_amd_v2x.h"), os.path.join(INCLUDE, "coalign_amd_v2x_window.h"), os.path.join(INCLUDE, "coalign_amd_w2c.h"), os.path.join(INCLUDE, "coalign_amd_v2v_robust.h"), os.path.join(INCLUDE, "coalign_amd_where2comm.h"), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "v2x_tiles.h"), os.path.join(CSRC, "warp_taps.h"), os.path.join(CSRC, "nhwc_lanes.h"), os.path.join(CSRC, "v2v_lanes.h"), os.path.join(CSRC, "stage1_internal.h"), os.path.abspath(__file__)]
+    # every header: the ABI's by name (a missing one is an error), include/*.h and csrc/*.h by glob (a shared header that was forgotten here meant stale objects)
+    headers = sorted({os.path.join(INCLUDE, h) for h in ABI_HEADERS} | set(glob.glob(os.path.join(INCLUDE, "*.h"))) | set(glob.glob(os.path.join(CSRC, "*.h")))) + [os.path.abspath(__file__)]
     hipcc = _hipcc()
 
     def compile_one(src: str) -> str:

@@ -129,80 +129,136 @@ def _single_agent_batch(data_dict: dict) -> dict:
     return batch_dict
 
 
-class PointPillarBaselineMultiscale(nn.Module):
-    def __init__(self, args: dict):
-        super().__init__()
-        self.pillar_vfe = PillarVFE(args["pillar_vfe"], num_point_features=4, voxel_size=args["voxel_size"],
-                                    point_cloud_range=args["lidar_range"])
+class _PillarTrunk(nn.Module):
+    """What every detector here is built of: pillar encoder + scatter, a BEV backbone, an optional shrink header, the 1 x 1 heads.  The ``_build_*`` helpers register
+    their submodules when CALLED: each model calls them in its own order, which fixes its ``state_dict`` order and the random numbers a seeded construction hands out."""
+
+    def _build_pillars(self, args: dict) -> None:
+        self.pillar_vfe = PillarVFE(args["pillar_vfe"], num_point_features=4, voxel_size=args["voxel_size"], point_cloud_range=args["lidar_range"])
         self.scatter = PointPillarScatter(args["point_pillar_scatter"])
-        bb = args["base_bev_backbone"]
-        self.backbone = ResNetBEVBackbone(bb, 64) if bb.get("resnet", True) else BaseBEVBackbone(bb, 64)
         self.voxel_size = args["voxel_size"]
-        self.fusion_net = nn.ModuleList()
-        for i in range(len(bb["layer_nums"])):
-            if args["fusion_method"] == "max":
-                self.fusion_net.append(MaxFusion())
-            elif args["fusion_method"] == "att":
-                self.fusion_net.append(AttFusion(args["att"]["feat_dim"][i]))
-            else:
-                raise NotImplementedError(f"fusion_method '{args['fusion_method']}' is outside the CoAlign hot path (att | max)")
-        self.out_channel = sum(bb["num_upsample_filter"])
+
+    def _build_backbone(self, args: dict, resnet: Optional[bool] = None) -> None:      # resnet: what a config without base_bev_backbone.resnet gets; None: BaseBEVBackbone whatever it says
+        bb = args["base_bev_backbone"]
+        self.backbone = ResNetBEVBackbone(bb, 64) if resnet is not None and bb.get("resnet", resnet) else BaseBEVBackbone(bb, 64)
+
+    def _build_shrink(self, args: dict) -> None:
+        self.out_channel = sum(args["base_bev_backbone"]["num_upsample_filter"])
         self.shrink_flag = "shrink_header" in args
         if self.shrink_flag:
             self.shrink_conv = DownsampleConv(args["shrink_header"])
             self.out_channel = args["shrink_header"]["dim"][-1]
-        self.compression = "compression" in args
-        if self.compression:
-            self.naive_compressor = NaiveCompressor(64, args["compression"])
-        self.cls_head = nn.Conv2d(self.out_channel, args["anchor_number"], kernel_size=1)
-        self.reg_head = nn.Conv2d(self.out_channel, 7 * args["anchor_number"], kernel_size=1)
+
+    def _build_heads(self, args: dict, width: Optional[int] = None, uncertainty_dim: int = 0) -> None:
+        width = self.out_channel if width is None else width
+        self.cls_head = nn.Conv2d(width, args["anchor_number"], kernel_size=1)
+        self.reg_head = nn.Conv2d(width, 7 * args["anchor_number"], kernel_size=1)
+        if uncertainty_dim:
+            self.unc_head = nn.Conv2d(width, uncertainty_dim * args["anchor_number"], kernel_size=1)
         self.use_dir = "dir_args" in args
         if self.use_dir:
-            self.dir_head = nn.Conv2d(self.out_channel, args["dir_args"]["num_bins"] * args["anchor_number"], kernel_size=1)
-        if args.get("backbone_fix"):
-            self.backbone_fix()
+            self.dir_head = nn.Conv2d(width, args["dir_args"]["num_bins"] * args["anchor_number"], kernel_size=1)
 
-    def backbone_fix(self):
-        frozen = [self.pillar_vfe, self.scatter, self.backbone, self.cls_head, self.reg_head]
-        if self.compression:
-            frozen.append(self.naive_compressor)
-        if self.shrink_flag:
-            frozen.append(self.shrink_conv)
-        for m in frozen:
+    def _frozen_parts(self) -> list:
+        parts = [self.pillar_vfe, self.scatter, self.backbone, self.cls_head, self.reg_head]
+        return parts + ([self.naive_compressor] if getattr(self, "compression", False) else []) + ([self.shrink_conv] if self.shrink_flag else [])
+
+    def backbone_fix(self, frozen: bool = True) -> None:
+        for m in self._frozen_parts():
             for p in m.parameters():
-                p.requires_grad = False
+                p.requires_grad = not frozen
 
-    # -- stages, exposed separately so the sharded runner can place them on different ranks ----------------
+    def _single_agent_map(self, data_dict: dict) -> torch.Tensor:
+        """The single-agent detectors' pillars -> canvas -> backbone -> concatenated up-sampled map."""
+        return self.backbone(self.scatter(self.pillar_vfe(_single_agent_batch(data_dict))))["spatial_features_2d"]
+
+    def _decode_shrink(self, feats, out_split: bool = False):
+        """Up-sampling heads and shrink header.  A shrink header on the SplitMap route gets the concatenated map from the up-sampling heads as ONE SplitMap (round 5);
+        its last convolution writes channels-last float32, which a fusion kernel reads in place, or -- ``out_split``, for a map that feeds the heads: the caller
+        passes ``heads_take_split_map(self)`` -- a SplitMap again."""
+        want_split = bool(self.shrink_flag and len(feats) > 0 and all(getattr(m, "is_cuda", False) for m in feats) and self.shrink_conv.takes_split_maps())
+        x = self.backbone.decode_multiscale_feature(feats, out_split=True) if want_split else self.backbone.decode_multiscale_feature(feats)
+        if self.shrink_flag:
+            return self.shrink_conv(x, out_split=out_split and isinstance(x, ops.SplitMap))
+        return x.dense() if isinstance(x, ops.SplitMap) else x
+
+
+class _Collaborative(_PillarTrunk):
+    """The detectors of several agents: ``encode`` (per agent) and ``fuse_and_head`` (ego) are exposed separately so the sharded runner can place them on different
+    ranks; ``FramePipeline`` and the inference drivers run every subclass through the same two flags and two stages."""
     accepts_normalized_affine = True      # encode() takes data_dict['normalized_affine_matrix'] in place of normalising pairwise_t_matrix itself (FramePipeline)
-    accepts_pillar_frame = True           # encode() hands processed_lidar['pillar_frame'] (ops.PillarFrameRecord) to PillarVFE: FramePipeline may read frames in place
+    accepts_pillar_frame = True           # encode() hands processed_lidar['pillar_frame'] (ops.PillarFrameRecord) to PillarVFE, whose dense-canvas route refuses it: FramePipeline then copies frames
+    plan_words_library_shrink = False     # routes.plan words a shrink-header convolution DoubleConv.forward builds no weight image for as a library layer (the single-scale baselines)
 
-    def encode(self, data_dict: dict):
-        """Per-agent part: pillars -> canvas -> multiscale features.  Returns (feature list, normalised affine)."""
-        spatial_features, affine = self._spatial_features(data_dict)
-        return self.backbone.get_multiscale_feature(spatial_features), affine
-
-    def _spatial_features(self, data_dict: dict):
-        """pillars -> canvas (-> compressor): what the backbone reads, and the normalised affine."""
+    def _spatial_features(self, data_dict: dict, want_affine: bool = True):
+        """pillars -> canvas: what the backbone (or the compressor in front of it) reads, and the normalised affine."""
         batch_dict = _single_agent_batch(dict(data_dict, record_len=host_ints(data_dict["record_len"])))      # (with the device voxeliser's streaming keys and FramePipeline's frame record)
-        # round 4: the encoder hands a SparseCanvas (one launch, no dense canvas) to a backbone whose first block reads it
-        resnet = getattr(self.backbone, "resnet", None)
-        keep_sparse = self.pillar_vfe.sparse_canvas
+        # round 4: the encoder hands a SparseCanvas (one launch, no dense canvas) to a backbone whose first block, or a compressor whose encoder, reads it
+        keep_sparse = getattr(self.pillar_vfe, "sparse_canvas", False)      # (False also for a stand-in encoder without the switch: the CPU tests of the baselines)
         self.pillar_vfe.sparse_canvas = sparse_canvas_route(self) or compressor_sparse_route(self)
         try:
             batch_dict = self.scatter(self.pillar_vfe(batch_dict))
         finally:
             self.pillar_vfe.sparse_canvas = keep_sparse
         spatial_features = batch_dict["spatial_features"]
-        H0, W0 = spatial_features.shape[2:]
-        affine = data_dict.get("normalized_affine_matrix")      # FramePipeline: normalised on the host from the dataset's host copy of the matrix (same float64 steps)
-        if affine is None:
+        affine = data_dict.get("normalized_affine_matrix") if want_affine else None      # FramePipeline: normalised on the host from the dataset's host copy of the matrix (same float64 steps)
+        if affine is None and want_affine:
+            H0, W0 = spatial_features.shape[2:]
             affine = normalize_pairwise_tfm(data_dict["pairwise_t_matrix"], H0, W0, self.voxel_size[0])
-        if self.compression:
-            # the compressor hands the first ResNet block a SplitMap when that block reads one: its strided opener + skip then run as one launch on it
-            opener = resnet.layer0[0] if resnet is not None and hasattr(resnet, "layer0") else None
-            want_split = bool(not self.training and isinstance(opener, BasicBlock) and opener.takes_split_maps() and opener.conv1.in_channels % 16 == 0)
-            spatial_features = self.naive_compressor(spatial_features, out_split=True) if want_split else self.naive_compressor(spatial_features)
         return spatial_features, affine
+
+    def forward(self, data_dict: dict) -> dict:
+        record_len = host_ints(data_dict["record_len"])
+        feats, affine = self.encode(dict(data_dict, record_len=record_len))
+        return self.fuse_and_head(feats, record_len, affine)
+
+
+class PointPillarBaselineMultiscale(_Collaborative):
+    def __init__(self, args: dict):
+        super().__init__()
+        self._build_pillars(args)
+        self._build_backbone(args, resnet=True)
+        self.fusion_net = nn.ModuleList()
+        for i in range(len(args["base_bev_backbone"]["layer_nums"])):
+            if args["fusion_method"] == "max":
+                self.fusion_net.append(MaxFusion())
+            elif args["fusion_method"] == "att":
+                self.fusion_net.append(AttFusion(args["att"]["feat_dim"][i]))
+            else:
+                raise NotImplementedError(f"fusion_method '{args['fusion_method']}' is outside the CoAlign hot path (att | max)")
+        self._build_shrink(args)
+        self.compression = "compression" in args
+        if self.compression:
+            self.naive_compressor = NaiveCompressor(64, args["compression"])
+        self._build_heads(args)
+        if args.get("backbone_fix"):
+            self.backbone_fix()
+
+    def _level_channels(self) -> list:
+        """The backbone's own widths, one per level."""
+        resnet = getattr(self.backbone, "resnet", None)
+        levels = [getattr(resnet, f"layer{i}") for i in range(resnet.layernum)] if resnet is not None else list(self.backbone.blocks)
+        return [b[0].conv1.out_channels if isinstance(b[0], BasicBlock) else b[1].out_channels for b in levels]
+
+    def plan_fusion(self, channels=None, terms: Optional[int] = None):
+        """-> (``routes.plan``'s fusion line, whether it is a fallback, {layers noted with it})."""
+        if _bb.NHWC_STAGE_OUTPUTS and _bb.emu_active(terms) and fusion_route(self, self._level_channels()):      # (channels-last stage outputs)
+            return "warp_fuse_nhwc: all scales in one launch (channels-last)", False, {}
+        return "warp_fuse: one launch per scale (NCHW, LDS-staged patches)", True, {}
+
+    def encode(self, data_dict: dict):
+        """Per-agent part: pillars -> canvas (-> compressor) -> multiscale features.  Returns (feature list, normalised affine)."""
+        spatial_features, affine = self._spatial_features(data_dict)
+        return self.backbone.get_multiscale_feature(self._compress(spatial_features)), affine
+
+    def _compress(self, spatial_features):
+        if not self.compression:
+            return spatial_features
+        # the compressor hands the first ResNet block a SplitMap when that block reads one: its strided opener + skip then run as one launch on it
+        resnet = getattr(self.backbone, "resnet", None)
+        opener = resnet.layer0[0] if resnet is not None and hasattr(resnet, "layer0") else None
+        want_split = bool(not self.training and isinstance(opener, BasicBlock) and opener.takes_split_maps() and opener.conv1.in_channels % 16 == 0)
+        return self.naive_compressor(spatial_features, out_split=True) if want_split else self.naive_compressor(spatial_features)
 
     def _fuse_scales(self, feature_list, record_len, affine, rows=None):
         """The per-scale fusion launches are independent: on the GPU the coarser scales (few workgroups, latency bound)
@@ -238,79 +294,44 @@ class PointPillarBaselineMultiscale(nn.Module):
     def fuse_and_head(self, feature_list, record_len, affine, rows=None) -> dict:
         """Ego part: per-scale warp + fusion, deblocks, shrink header, heads.  ``rows``: see ``AttFusion.forward``."""
         fused = self._fuse_scales(feature_list, record_len, affine, rows)
-        # round 5: a shrink header on the SplitMap route gets the concatenated map from the up-sampling heads already split
-        want_split = bool(self.shrink_flag and len(fused) > 0 and all(getattr(m, "is_cuda", False) for m in fused) and self.shrink_conv.takes_split_maps())
-        x = self.backbone.decode_multiscale_feature(fused, out_split=True) if want_split else self.backbone.decode_multiscale_feature(fused)
-        if self.shrink_flag:
-            x = self.shrink_conv(x, out_split=isinstance(x, ops.SplitMap) and heads_take_split_map(self))
-        elif isinstance(x, ops.SplitMap):
-            x = x.dense()
-        return _run_heads(self, x)
-
-    def forward(self, data_dict: dict) -> dict:
-        record_len = host_ints(data_dict["record_len"])
-        feats, affine = self.encode(dict(data_dict, record_len=record_len))
-        return self.fuse_and_head(feats, record_len, affine)
+        return _run_heads(self, self._decode_shrink(fused, out_split=heads_take_split_map(self)))
 
 
 class CoAlign(PointPillarBaselineMultiscale):
     pass
 
 
-class PointPillar(nn.Module):
+class PointPillar(_PillarTrunk):
     """Single-agent PointPillar (late-fusion config)."""
 
     def __init__(self, args: dict):
         super().__init__()
-        self.pillar_vfe = PillarVFE(args["pillar_vfe"], num_point_features=4, voxel_size=args["voxel_size"],
-                                    point_cloud_range=args["lidar_range"])
-        self.scatter = PointPillarScatter(args["point_pillar_scatter"])
-        bb = args["base_bev_backbone"]
-        self.backbone = ResNetBEVBackbone(bb, 64) if bb.get("resnet", False) else BaseBEVBackbone(bb, 64)
-        self.out_channel = sum(bb["num_upsample_filter"])
-        self.shrink_flag = "shrink_header" in args
-        if self.shrink_flag:
-            self.shrink_conv = DownsampleConv(args["shrink_header"])
-            self.out_channel = args["shrink_header"]["dim"][-1]
-        self.cls_head = nn.Conv2d(self.out_channel, args["anchor_number"], kernel_size=1)
-        self.reg_head = nn.Conv2d(self.out_channel, 7 * args["anchor_number"], kernel_size=1)
-        self.use_dir = "dir_args" in args
-        if self.use_dir:
-            self.dir_head = nn.Conv2d(self.out_channel, args["dir_args"]["num_bins"] * args["anchor_number"], kernel_size=1)
+        self._build_pillars(args)
+        self._build_backbone(args, resnet=False)
+        self._build_shrink(args)
+        self._build_heads(args)
 
     def forward(self, data_dict: dict) -> dict:
-        batch_dict = self.backbone(self.scatter(self.pillar_vfe(_single_agent_batch(data_dict))))
-        x = batch_dict["spatial_features_2d"]
-        if self.shrink_flag:
-            x = self.shrink_conv(x)
-        return _run_heads(self, x)
+        x = self._single_agent_map(data_dict)
+        return _run_heads(self, self.shrink_conv(x) if self.shrink_flag else x)
 
 
-class PointPillarUncertainty(nn.Module):
+class PointPillarUncertainty(_PillarTrunk):
     """Stage-1 single-agent detector of CoAlign's box alignment (opencood/models/point_pillar_uncertainty.py:15-84): PointPillar
     with a fourth 1x1 head ``unc_head`` predicting ``uncertainty_dim`` log-variances (x, y[, yaw]) per anchor."""
 
     def __init__(self, args: dict):
         super().__init__()
-        self.pillar_vfe = PillarVFE(args["pillar_vfe"], num_point_features=4, voxel_size=args["voxel_size"],
-                                    point_cloud_range=args["lidar_range"])
-        self.scatter = PointPillarScatter(args["point_pillar_scatter"])
-        self.backbone = BaseBEVBackbone(args["base_bev_backbone"], 64)
+        self._build_pillars(args)
+        self._build_backbone(args)
         self.uncertainty_dim = args["uncertainty_dim"]
-        width = 128 * 3                                          # hard-coded in the reference (:26-37)
-        self.cls_head = nn.Conv2d(width, args["anchor_number"], kernel_size=1)
-        self.reg_head = nn.Conv2d(width, 7 * args["anchor_number"], kernel_size=1)
-        self.unc_head = nn.Conv2d(width, self.uncertainty_dim * args["anchor_number"], kernel_size=1)
-        self.use_dir = "dir_args" in args
-        if self.use_dir:
-            self.dir_head = nn.Conv2d(width, args["dir_args"]["num_bins"] * args["anchor_number"], kernel_size=1)
+        self._build_heads(args, width=128 * 3, uncertainty_dim=self.uncertainty_dim)      # (the width is hard-coded in the reference, :26-37)
 
     def forward(self, data_dict: dict) -> dict:
-        batch_dict = self.backbone(self.scatter(self.pillar_vfe(_single_agent_batch(data_dict))))
-        return _run_heads(self, batch_dict["spatial_features_2d"])
+        return _run_heads(self, self._single_agent_map(data_dict))
 
 
-class PointPillarDiscoNet(nn.Module):
+class PointPillarDiscoNet(_Collaborative):
     """DiscoNet on PointPillars (opencood/models/point_pillar_disconet.py:19-96): pillar encoder, ``BaseBEVBackbone``, shrink header, ONE single-scale
     ``DiscoFusion`` on the shrunk map, 1 x 1 heads.  Same constructor keys, ``state_dict`` names and outputs (``feature`` / ``cls_preds`` / ``reg_preds`` [/ ``dir_preds``])
     as the reference; the ``teacher_processed_lidar`` keys, which the reference's forward reads and never uses, are not required.  ``encode`` / ``fuse_and_head`` and
@@ -319,57 +340,24 @@ class PointPillarDiscoNet(nn.Module):
     def __init__(self, args: dict):
         super().__init__()
         self.discrete_ratio = args["voxel_size"][0]
-        self.pillar_vfe = PillarVFE(args["pillar_vfe"], num_point_features=4, voxel_size=args["voxel_size"],
-                                    point_cloud_range=args["lidar_range"])
-        self.scatter = PointPillarScatter(args["point_pillar_scatter"])
-        self.backbone = BaseBEVBackbone(args["base_bev_backbone"], 64)
-        self.out_channel = sum(args["base_bev_backbone"]["num_upsample_filter"])
-        self.voxel_size = args["voxel_size"]
-        self.shrink_flag = "shrink_header" in args
-        if self.shrink_flag:
-            self.shrink_conv = DownsampleConv(args["shrink_header"])
-            self.out_channel = args["shrink_header"]["dim"][-1]
+        self._build_pillars(args)
+        self._build_backbone(args)
+        self._build_shrink(args)
         self.fusion_net = DiscoFusion(self.out_channel)
-        self.cls_head = nn.Conv2d(self.out_channel, args["anchor_number"], kernel_size=1)
-        self.reg_head = nn.Conv2d(self.out_channel, 7 * args["anchor_number"], kernel_size=1)
-        self.use_dir = "dir_args" in args
-        if self.use_dir:
-            self.dir_head = nn.Conv2d(self.out_channel, args["dir_args"]["num_bins"] * args["anchor_number"], kernel_size=1)
-
-    accepts_normalized_affine = True      # encode() takes data_dict['normalized_affine_matrix'] in place of normalising pairwise_t_matrix itself
-    accepts_pillar_frame = True           # encode() hands processed_lidar['pillar_frame'] to PillarVFE (whose dense-canvas route refuses it: FramePipeline then copies frames)
+        self._build_heads(args)
 
     def encode(self, data_dict: dict):
         """Per-agent part: pillars -> canvas -> backbone -> shrink header.  Returns ([the agents' maps, channels-last float32 on the SplitMap route], normalised affine)."""
-        batch_dict = self.scatter(self.pillar_vfe(_single_agent_batch(dict(data_dict, record_len=host_ints(data_dict["record_len"])))))
-        spatial_features = batch_dict["spatial_features"]
-        H0, W0 = spatial_features.shape[2:]
-        affine = data_dict.get("normalized_affine_matrix")
-        if affine is None:
-            affine = normalize_pairwise_tfm(data_dict["pairwise_t_matrix"], H0, W0, self.voxel_size[0])
-        feats = self.backbone.get_multiscale_feature(spatial_features)
-        # the up-sampling heads hand a shrink header on the SplitMap route ONE SplitMap; its second convolution (conv3x3_sp) writes the channels-last float32 map
-        # the fusion kernel reads in place
-        want_split = bool(self.shrink_flag and all(getattr(m, "is_cuda", False) for m in feats) and self.shrink_conv.takes_split_maps())
-        x = self.backbone.decode_multiscale_feature(feats, out_split=True) if want_split else self.backbone.decode_multiscale_feature(feats)
-        if self.shrink_flag:
-            x = self.shrink_conv(x)
-        elif isinstance(x, ops.SplitMap):
-            x = x.dense()
-        return [x], affine
+        spatial_features, affine = self._spatial_features(data_dict)
+        return [self._decode_shrink(self.backbone.get_multiscale_feature(spatial_features))], affine
 
     def fuse_and_head(self, feature_list, record_len, affine, rows=None) -> dict:
         """Ego part: the pixel-weight fusion of the agents' maps, then the heads on the fused map."""
         fused = self.fusion_net(feature_list[0], record_len, affine, rows=rows)
         return dict({"feature": fused}, **_run_heads(self, fused))
 
-    def forward(self, data_dict: dict) -> dict:
-        record_len = host_ints(data_dict["record_len"])
-        feats, affine = self.encode(dict(data_dict, record_len=record_len))
-        return self.fuse_and_head(feats, record_len, affine)
 
-
-class PointPillarBaseline(nn.Module):
+class PointPillarBaseline(_Collaborative):
     """The single-scale collaborative baselines on PointPillars (opencood/models/point_pillar_baseline.py:17-138: F-Cooper, self-attention, DiscoNet without
     distillation, V2VNet, V2X-ViT, When2com): pillar encoder, ``BaseBEVBackbone`` or ``ResNetBEVBackbone``, shrink header, optional ``NaiveCompressor``, ONE fusion
     module on the shrunk map chosen by ``fusion_method`` (max | att | disconet | v2vnet | v2xvit | when2comm), 1 x 1 heads.  Same constructor keys, ``state_dict``
@@ -377,15 +365,12 @@ class PointPillarBaseline(nn.Module):
     with ``NotImplementedError``); any other name is refused at construction -- the reference would build a model without ``fusion_net`` and fail in ``forward``.
     ``encode`` / ``fuse_and_head`` and the two ``accepts_*`` flags follow ``PointPillarDiscoNet``'s contracts: ``FramePipeline`` and the inference drivers run it
     unchanged.  The fusion receives the whole [L, L] affine matrix (V2VNet reads every receiver's row)."""
+    plan_words_library_shrink = True
 
     def __init__(self, args: dict):
         super().__init__()
-        self.pillar_vfe = PillarVFE(args["pillar_vfe"], num_point_features=4, voxel_size=args["voxel_size"],
-                                    point_cloud_range=args["lidar_range"])
-        self.scatter = PointPillarScatter(args["point_pillar_scatter"])
-        bb = args["base_bev_backbone"]
-        self.backbone = ResNetBEVBackbone(bb, 64) if bb.get("resnet", False) else BaseBEVBackbone(bb, 64)
-        self.voxel_size = args["voxel_size"]
+        self._build_pillars(args)
+        self._build_backbone(args, resnet=False)
         method = args["fusion_method"]
         if method == "max":
             self.fusion_net = MaxFusion()
@@ -405,55 +390,23 @@ class PointPillarBaseline(nn.Module):
             self.fusion_net = When2comFusion(args["when2comm"])
         else:
             raise NotImplementedError(f"fusion_method '{method}' of point_pillar_baseline is not built here (max | att | disconet | v2vnet | v2xvit | when2comm)")
-        self.out_channel = sum(bb["num_upsample_filter"])
-        self.shrink_flag = "shrink_header" in args
-        if self.shrink_flag:
-            self.shrink_conv = DownsampleConv(args["shrink_header"])
-            self.out_channel = args["shrink_header"]["dim"][-1]
+        self._build_shrink(args)
         self.compression = "compression" in args
         if self.compression:
             self.naive_compressor = NaiveCompressor(self.out_channel, args["compression"])
-        self.cls_head = nn.Conv2d(self.out_channel, args["anchor_number"], kernel_size=1)
-        self.reg_head = nn.Conv2d(self.out_channel, 7 * args["anchor_number"], kernel_size=1)
-        self.use_dir = "dir_args" in args
-        if self.use_dir:
-            self.dir_head = nn.Conv2d(self.out_channel, args["dir_args"]["num_bins"] * args["anchor_number"], kernel_size=1)
+        self._build_heads(args)
         if args.get("backbone_fix"):
             self.backbone_fix()
 
-    backbone_fix = PointPillarBaselineMultiscale.backbone_fix
-
-    accepts_normalized_affine = True      # encode() takes data_dict['normalized_affine_matrix'] in place of normalising pairwise_t_matrix itself
-    accepts_pillar_frame = True           # encode() hands processed_lidar['pillar_frame'] to PillarVFE (whose dense-canvas route refuses it: FramePipeline then copies frames)
-
     def encode(self, data_dict: dict):
         """Per-agent part: pillars -> canvas -> backbone -> shrink header (-> compressor).  Returns ([the agents' map], normalised affine)."""
-        batch_dict = self.scatter(self.pillar_vfe(_single_agent_batch(dict(data_dict, record_len=host_ints(data_dict["record_len"])))))
-        spatial_features = batch_dict["spatial_features"]
-        H0, W0 = spatial_features.shape[2:]
-        affine = data_dict.get("normalized_affine_matrix")
-        if affine is None:
-            affine = normalize_pairwise_tfm(data_dict["pairwise_t_matrix"], H0, W0, self.voxel_size[0])
-        feats = self.backbone.get_multiscale_feature(spatial_features)
-        # (a stride-1 shrink header on the SplitMap route takes ONE SplitMap from the up-sampling heads and writes channels-last float32, which the fusion reads in place)
-        want_split = bool(self.shrink_flag and all(getattr(m, "is_cuda", False) for m in feats) and self.shrink_conv.takes_split_maps())
-        x = self.backbone.decode_multiscale_feature(feats, out_split=True) if want_split else self.backbone.decode_multiscale_feature(feats)
-        if self.shrink_flag:
-            x = self.shrink_conv(x)
-        elif isinstance(x, ops.SplitMap):
-            x = x.dense()
-        if self.compression:
-            x = self.naive_compressor(x)
-        return [x], affine
+        spatial_features, affine = self._spatial_features(data_dict)
+        x = self._decode_shrink(self.backbone.get_multiscale_feature(spatial_features))
+        return [self.naive_compressor(x) if self.compression else x], affine
 
     def fuse_and_head(self, feature_list, record_len, affine, rows=None) -> dict:
         """Ego part: the fusion of the agents' maps, then the heads on the fused map."""
         return _run_heads(self, self.fusion_net(feature_list[0], record_len, affine, rows=rows))
-
-    def forward(self, data_dict: dict) -> dict:
-        record_len = host_ints(data_dict["record_len"])
-        feats, affine = self.encode(dict(data_dict, record_len=record_len))
-        return self.fuse_and_head(feats, record_len, affine)
 
 
 class PointPillarWhere2comm(PointPillarBaselineMultiscale):
@@ -478,47 +431,38 @@ class PointPillarWhere2comm(PointPillarBaselineMultiscale):
         if self.multi_scale and self.fusion_net.num_levels != self.backbone.num_levels:
             raise ValueError(f"where2comm.layer_nums names {self.fusion_net.num_levels} levels, the backbone has {self.backbone.num_levels}")
 
-    def _fusion_channels(self) -> list:
-        return [b[0].conv1.out_channels if isinstance(b[0], BasicBlock) else b[1].out_channels for b in self._levels()] if self.multi_scale else [self.out_channel]
-
-    def _levels(self):
-        resnet = getattr(self.backbone, "resnet", None)
-        return [getattr(resnet, f"layer{i}") for i in range(resnet.layernum)] if resnet is not None else list(self.backbone.blocks)
+    def _route_args(self, n_agents: int):      # the module decides on this model's widths, backbone kind and anchor count
+        return self._level_channels() if self.multi_scale else [self.out_channel], n_agents, hasattr(self.backbone, "resnet"), self.cls_head.out_channels
 
     def kernel_route(self, n_agents: int = 1) -> bool:
-        """The static half of the fusion's decision (``routes.plan`` asks it): the module's, on this model's widths, backbone kind and anchor count."""
-        return self.fusion_net.kernel_route(self._fusion_channels(), n_agents, hasattr(self.backbone, "resnet"), self.cls_head.out_channels)
+        """The static half of the fusion's decision (``routes.plan`` asks it)."""
+        return self.fusion_net.kernel_route(*self._route_args(n_agents))
 
-    def kernel_route_reason(self) -> Optional[str]:
+    def kernel_route_reason(self, n_agents: int = 1) -> Optional[str]:
         """Why ``kernel_route`` says no, in words (None when it says yes, or for the module's mode alone)."""
-        f, ch = self.fusion_net, self._fusion_channels()
-        if f.multi_scale and not hasattr(self.backbone, "resnet"):
-            return "a plain BaseBEVBackbone feeds every block the masked map of the one before: the levels cannot be fused in one launch"
-        if len(ch) > 3 or any(c not in (64, 128, 256) for c in ch):
-            return f"maps of {ch} channels outside the kernel's 64 / 128 / 256, at most three levels"
-        mods = list(f.fuse_modules) if f.multi_scale else [f.fuse_modules]
-        if any(getattr(m, "feature_dim", c) != c for m, c in zip(mods, ch)):
-            return "an attention whose feature_dim differs from its map's channels"
-        if f.communication and not ops.w2comm_masks_shape_ok(self.cls_head.out_channels, [1], f.naive_communication.kernel_size(), len(ch)):
-            return "a smoothing kernel (even, or larger than 9) or an anchor count (more than 8) the mask kernel does not take"
-        return None
+        return self.fusion_net.kernel_shape_reason(*self._route_args(n_agents))
 
-    def _decode_shrink(self, feats, for_heads: bool):
-        """Up-sampling heads and shrink header: on every agent's levels (for the logits and the single-scale fusion: a float32 map) or on the fused levels."""
-        want_split = bool(self.shrink_flag and len(feats) > 0 and all(getattr(m, "is_cuda", False) for m in feats) and self.shrink_conv.takes_split_maps())
-        x = self.backbone.decode_multiscale_feature(feats, out_split=True) if want_split else self.backbone.decode_multiscale_feature(feats)
-        if self.shrink_flag:
-            x = self.shrink_conv(x, out_split=for_heads and isinstance(x, ops.SplitMap) and heads_take_split_map(self))
-        elif isinstance(x, ops.SplitMap):
-            x = x.dense()
-        return x
+    def plan_fusion(self, channels=None, terms: Optional[int] = None):
+        """-> (``routes.plan``'s fusion line, whether it is a fallback, {layers noted with it})."""
+        f = self.fusion_net
+        if self.kernel_route() and (not f.multi_scale or (_bb.NHWC_STAGE_OUTPUTS and _bb.emu_active(terms))):      # (channels-last stage outputs)
+            return (f.KERNELS if f.communication else f.KERNELS_PLAIN), False, {}
+        return f"{f.TORCH} ({self.kernel_route_reason() or 'stage outputs not channels-last, ' + _bb.TORCH_MODE})", True, {}
+
+    def plan_layer(self, name: str, layer: nn.Module, channels=None, terms: Optional[int] = None):
+        """-> (line, fallback) of ``naive_communication.gaussian_filter``."""
+        if not isinstance(layer, nn.Conv2d):
+            return None
+        ok = self.kernel_route()
+        return (self.fusion_net.MASKS if ok else _bb.MIOPEN + " (Where2comm op by op)"), not ok
 
     def encode(self, data_dict: dict):
         """Per-agent part.  Returns ([the maps the fusion reads ..., the single-agent logits], normalised affine): the backbone's levels in multi-scale mode on a
         backbone with ``.resnet``, the canvas on a plain ``BaseBEVBackbone`` (whose later blocks read the MASKED maps, where2comm_attn.py:262), else the shrunk map."""
         spatial_features, affine = self._spatial_features(data_dict)
+        spatial_features = self._compress(spatial_features)
         feats = self.backbone.get_multiscale_feature(spatial_features)
-        x = self._decode_shrink(feats, for_heads=False)
+        x = self._decode_shrink(feats)          # (for the logits and the single-scale fusion: a float32 map)
         psm = _run_heads(self, x)["cls_preds"]
         if not self.multi_scale:
             return [x, psm], affine
@@ -533,7 +477,7 @@ class PointPillarWhere2comm(PointPillarBaselineMultiscale):
             x, rates, _ = self.fusion_net.fuse(maps[0], psm, record_len, affine, rows=rows)
         elif hasattr(self.backbone, "resnet"):
             fused, rates = self.fusion_net.fuse(None, psm, record_len, affine, self.backbone, feats=maps, rows=rows, decode=False)
-            x = self._decode_shrink(fused, for_heads=True) if isinstance(fused, list) else self._shrink_decoded(fused)
+            x = self._decode_shrink(fused, out_split=heads_take_split_map(self)) if isinstance(fused, list) else self._shrink_decoded(fused)
         else:
             x, rates, _ = self.fusion_net.fuse(maps[0], psm, record_len, affine, self.backbone, rows=rows)
             x = self._shrink_decoded(x)
@@ -545,7 +489,7 @@ class PointPillarWhere2comm(PointPillarBaselineMultiscale):
         return self.shrink_conv(x) if self.shrink_flag else x
 
 
-class PointPillarV2VNetRobust(nn.Module):
+class PointPillarV2VNetRobust(_Collaborative):
     """V2VNet with learned pose correction (opencood/models/point_pillar_v2vnet_robust.py:21-332), the baseline CoAlign is compared with under pose noise: pillar
     encoder, ``BaseBEVBackbone``, shrink header, optional ``NaiveCompressor(256, rate)`` when the integer ``compression`` > 0, then on the shrunk maps the pose
     regression over all pairs (``pose_reg_net``), the globally consistent poses (``v2v_robust.weighted_em``), the attention scores (``attention_net``, with
@@ -567,68 +511,47 @@ class PointPillarV2VNetRobust(nn.Module):
     Maps whose H, W differ from robust.H, robust.W, or lie below 24 x 24 (the smallest map the regression's pooling accepts), are refused with
     ``NotImplementedError``.  Three routes: ``forward_torch`` (the reference op by op), ``forward_reduced`` (the exact identities of ``v2v_robust`` and
     ``V2VNetFusion.forward_reduced`` in torch ops), ``forward_kernels`` (CUDA float32 in eval mode when ``kernel_route`` holds; ``force_torch`` is the test aid)."""
+    accepts_normalized_affine = accepts_pillar_frame = False      # (its ``encode`` returns the maps alone and ``forward`` reads the poses: no pipeline stage pair)
+    plan_words_library_shrink = True
+    plan_prefixes = ("pose_reg_net.", "attention_net.", "fusion_net.")      # the submodules ``plan_layer`` words: ONE decision serves the three parts
 
     def __init__(self, args: dict):
         super().__init__()
         self.max_cav = args["max_cav"]
-        self.pillar_vfe = PillarVFE(args["pillar_vfe"], num_point_features=4, voxel_size=args["voxel_size"], point_cloud_range=args["lidar_range"])
-        self.scatter = PointPillarScatter(args["point_pillar_scatter"])
-        self.backbone = BaseBEVBackbone(args["base_bev_backbone"], 64)
-        self.voxel_size = args["voxel_size"]
-        self.out_channel = sum(args["base_bev_backbone"]["num_upsample_filter"])
-        self.shrink_flag = "shrink_header" in args
-        if self.shrink_flag:
-            self.shrink_conv = DownsampleConv(args["shrink_header"])
-            self.out_channel = args["shrink_header"]["dim"][-1]
+        self._build_pillars(args)
+        self._build_backbone(args)
+        self._build_shrink(args)
         self.compression = args.get("compression", 0) > 0
         if self.compression:
             self.naive_compressor = NaiveCompressor(256, args["compression"])
         self.fusion_net = V2VNetFusion(args["v2vfusion"])
         self.fusion_downsample_rate, self.fusion_discrete_ratio = args["v2vfusion"]["downsample_rate"], args["v2vfusion"]["voxel_size"][0]
-        self.cls_head = nn.Conv2d(self.out_channel, args["anchor_number"], kernel_size=1)
-        self.reg_head = nn.Conv2d(self.out_channel, 7 * args["anchor_number"], kernel_size=1)
+        self._build_heads({k: v for k, v in args.items() if k != "dir_args"})      # (no direction head, whatever the config says)
         robust = args["robust"]
         self.downsample_rate, self.discrete_ratio, self.H, self.W = robust["downsample_rate"], robust["discrete_ratio"], robust["H"], robust["W"]
         self.affine_parameter = {"H": self.H, "W": self.W, "downsample_rate": self.downsample_rate, "discrete_ratio": self.discrete_ratio}
         self.pose_reg_net = PoseRegressionWraper(robust["feature_dim"] * 2, robust["hidden_dim"], self.affine_parameter)
         self.attention_net = AttentionWrapper(robust["feature_dim"] * 2, robust["hidden_dim"], self.affine_parameter, robust.get("learnable_alpha", True))
         self.stage = args["stage"]
-        self.use_dir = False
         self.force_torch = False      # measurement / test aid: take the op-by-op route whatever the device
         if self.stage == 1:
             self.backbone_fix()
         if self.stage == 2:
             self.backbone_unfix()
 
-    def _trunk(self):
-        parts = [self.pillar_vfe, self.scatter, self.backbone, self.fusion_net, self.cls_head, self.reg_head, self.attention_net]
-        return parts + ([self.naive_compressor] if self.compression else []) + ([self.shrink_conv] if self.shrink_flag else [])
-
-    def backbone_fix(self) -> None:
+    def _frozen_parts(self) -> list:
         """Stage 1 trains the pose regression alone: everything else is frozen (point_pillar_v2vnet_robust.py:81-110)."""
-        for m in self._trunk():
-            for p in m.parameters():
-                p.requires_grad = False
+        return super()._frozen_parts() + [self.fusion_net, self.attention_net]
 
     def backbone_unfix(self) -> None:
-        for m in self._trunk():
-            for p in m.parameters():
-                p.requires_grad = True
+        self.backbone_fix(False)
 
     # ---- encoder -------------------------------------------------------------------------------------------------------------------------------------------
     def encode(self, data_dict: dict) -> torch.Tensor:
         """Per-agent part: pillars -> canvas -> backbone -> shrink header (-> compressor): the agents' maps [N, C, H, W]."""
-        batch_dict = self.scatter(self.pillar_vfe(_single_agent_batch(dict(data_dict, record_len=host_ints(data_dict["record_len"])))))
-        feats = self.backbone.get_multiscale_feature(batch_dict["spatial_features"])
-        want_split = bool(self.shrink_flag and all(getattr(m, "is_cuda", False) for m in feats) and self.shrink_conv.takes_split_maps())
-        x = self.backbone.decode_multiscale_feature(feats, out_split=True) if want_split else self.backbone.decode_multiscale_feature(feats)
-        if self.shrink_flag:
-            x = self.shrink_conv(x)
-        elif isinstance(x, ops.SplitMap):
-            x = x.dense()
-        if self.compression:
-            x = self.naive_compressor(x)
-        return x
+        spatial_features, _ = self._spatial_features(data_dict, want_affine=False)
+        x = self._decode_shrink(self.backbone.get_multiscale_feature(spatial_features))
+        return self.naive_compressor(x) if self.compression else x
 
     # ---- noise ---------------------------------------------------------------------------------------------------------------------------------------------
     def noise_generator(self, lidar_pose: torch.Tensor, all_strong: bool = False):
@@ -653,10 +576,34 @@ class PointPillarV2VNetRobust(nn.Module):
         """The three warps (pose regression, attention, fusion) normalise alike: ONE affine per pose set serves them, and one warp the attention and the fusion."""
         return float(self.fusion_downsample_rate) * float(self.fusion_discrete_ratio) == float(self.downsample_rate) * float(self.discrete_ratio)
 
+    def kernel_shape_reason(self, channels: int, n_agents: int = 1, terms: Optional[int] = None) -> Optional[str]:
+        """None when the three parts' kernels take (channels, n_agents) in the arithmetic in force, else why not, in words (``routes.plan`` prints it)."""
+        if not self.one_normalisation():
+            return "the three warps normalise differently (robust vs v2vfusion downsample_rate x discrete_ratio)"
+        nets = (self.pose_reg_net, self.attention_net)
+        widths = next((w for w in (net.widths_reason(channels) for net in nets) if w is not None), None)
+        if widths is not None or (self.fusion_net.kernel_shape_reason(channels, n_agents, terms) is None
+                                  and all(net.kernel_shape_reason(channels, n_agents, terms, self.max_cav) is None for net in nets)):
+            return widths
+        return "the fusion's own conditions (3 x 3 GRU kernels, widths) or the SplitMap arithmetic (fp16 x 2) is not in force"
+
     def kernel_route(self, channels: int, n_agents: int = 1, terms: Optional[int] = None) -> bool:
         """The static half of the decision (``routes.plan`` asks it): the fusion's, both small nets' and the shapes' conditions; ``forward`` adds a CUDA float32 map."""
-        return bool(not self.training and not self.force_torch and self.one_normalisation() and self.fusion_net.kernel_route(channels, n_agents, terms)
-                    and self.pose_reg_net.kernel_route(channels, n_agents, terms, self.max_cav) and self.attention_net.kernel_route(channels, n_agents, terms, self.max_cav))
+        parts = (self, self.fusion_net, self.pose_reg_net, self.attention_net)      # (each part's own mode and ``force_torch`` count, as in its own ``kernel_route``)
+        return bool(not any(m.training or m.force_torch for m in parts) and self.kernel_shape_reason(channels, n_agents, terms) is None)
+
+    def plan_fusion(self, channels: int, terms: Optional[int] = None):
+        """-> (``routes.plan``'s fusion line, whether it is a fallback, {layers noted with it}): pose regression, EM, attention and the weighted V2VNet on the shrunk map."""
+        ok = self.kernel_route(channels, 1, terms)
+        line = v2v_robust.KERNELS if ok else f"{v2v_robust.TORCH} ({self.kernel_shape_reason(channels, 1, terms) or _bb.TORCH_MODE})"
+        return line, not ok, self.fusion_net.plan_mlp(terms, ok)
+
+    def plan_layer(self, name: str, layer: nn.Module, channels: int, terms: Optional[int] = None):
+        """-> (line, fallback) of a convolution or linear of the three parts: the model's forward takes the kernels for all of them or for none."""
+        ok = self.kernel_route(channels, 1, terms)
+        if name.startswith("fusion_net."):
+            return self.fusion_net.plan_layer(name, layer, channels, terms, ok)
+        return (self.pose_reg_net if name.startswith("pose_reg_net.") else self.attention_net).plan_layer(name, layer, terms, ok)
 
     def _fusion_affine(self, T: torch.Tensor, H: int, W: int) -> torch.Tensor:
         return normalize_pairwise_tfm(T, H, W, self.fusion_discrete_ratio, self.fusion_downsample_rate)

@@ -84,6 +84,10 @@ def fuse_multiscale(xs: Sequence[torch.Tensor], record_len, affine: torch.Tensor
 
 
 class MaxFusion(nn.Module):
+    def plan_fusion(self, channels: int, terms: Optional[int] = None):
+        """``routes.plan``'s fusion line of ONE parameter-free module on the shrunk map (point_pillar_baseline: max | att): the NCHW kernel, listed as a fallback."""
+        return "warp_fuse: one launch (NCHW, LDS-staged patches)", True, {}
+
     def forward(self, x: torch.Tensor, record_len, pairwise_t_matrix: torch.Tensor, rows=None) -> torch.Tensor:
         """``rows`` (not in the reference): row of ``x`` holding logical agent i, for agent-sharded callers."""
         groups = host_ints(record_len)
@@ -91,6 +95,8 @@ class MaxFusion(nn.Module):
 
 
 class AttFusion(nn.Module):
+    plan_fusion = MaxFusion.plan_fusion
+
     def __init__(self, feature_dims: int):
         super().__init__()
         self.feature_dims = feature_dims
@@ -161,9 +167,28 @@ class DiscoFusion(nn.Module):
         self.pixel_weight_layer = PixelWeightLayer(feature_dims)
         self.force_torch = False      # measurement / test aid: take the op-by-op route whatever the device
 
+    KERNELS, TORCH = "disco_fuse: warp + pixel-weight MLP + softmax in one launch", "DiscoFusion op by op in PyTorch"
+
+    def kernel_shape_reason(self, channels: int, n_agents: int = 1) -> Optional[str]:
+        """None when ``coalign_disco_fuse`` takes (channels, n_agents), else why not, in words (``routes.plan`` prints it)."""
+        if not ops.disco_fuse_shape_ok(channels, 1):
+            return "channels outside the kernel's C % 32 == 0, 32 .. 384"
+        return None if ops.disco_fuse_shape_ok(channels, n_agents) else f"{n_agents} agents in a frame outside 1 .. 8"
+
     def kernel_route(self, channels: int, n_agents: int = 1) -> bool:
         """The static half of the decision (``routes.plan`` asks it): eval mode and a shape the kernel takes.  ``forward`` adds: a CUDA float32 map, packable weights."""
-        return bool(not self.training and not self.force_torch and ops.disco_fuse_shape_ok(channels, n_agents))
+        return bool(not self.training and not self.force_torch and self.kernel_shape_reason(channels, n_agents) is None)
+
+    def plan_fusion(self, channels: int, terms: Optional[int] = None):
+        """-> (``routes.plan``'s fusion line, whether it is a fallback, {layers noted with it: (line, fallback)})."""
+        if self.kernel_route(channels):
+            return self.KERNELS, False, {}
+        return f"{self.TORCH} ({self.kernel_shape_reason(channels) or _bb.TORCH_MODE})", True, {}
+
+    def plan_layer(self, name: str, layer: nn.Module, channels: int, terms: Optional[int] = None):
+        """-> (line, fallback) of one of this module's layers: the four 1 x 1 layers of ``PixelWeightLayer`` run inside the fusion launch."""
+        ok = self.kernel_route(channels)
+        return ("disco_fuse (pixel-weight MLP layer inside the fusion launch)" if ok else _bb.MIOPEN + " (DiscoFusion op by op)"), not ok
 
     def forward_torch(self, xx: torch.Tensor, record_len, normalized_affine_matrix: torch.Tensor, folded: bool = False) -> torch.Tensor:
         _, C, H, W = xx.shape
@@ -309,9 +334,39 @@ class V2VNetFusion(nn.Module):
         """The static half of the decision (``routes.plan`` asks it): eval mode, 3 x 3 GRU kernels, widths ``conv3x3_sp`` takes (C % 64 == 0, 2C <= its 1024-channel
         limit), at most 8 agents, the SplitMap arithmetic in force.  ``forward`` adds: a CUDA float32 map."""
         self._check_agg(static=True)
-        k3 = all(tuple(c.conv_gates.kernel_size) == (3, 3) for c in self.conv_gru.cell_list)
-        widths = channels == self.msg_cnn.out_channels and channels % 64 == 0 and _bb.sp_channels_ok(2 * channels, 2 * channels) and ops.v2v_shape_ok(channels, n_agents)
-        return bool(not self.training and not self.force_torch and k3 and widths and _bb.split_maps_active(terms))
+        return bool(not self.training and not self.force_torch and self.kernel_shape_reason(channels, n_agents, terms) is None)
+
+    KERNELS = "v2v_warp_split + conv3x3_sp + v2v_aggregate + conv3x3_sp + v2v_gate per iteration, one launch per stage over all (receiver, sender) pairs"
+    TORCH = "V2VNetFusion op by op in PyTorch"
+
+    def kernel_shape_reason(self, channels: int, n_agents: int = 1, terms: Optional[int] = None) -> Optional[str]:
+        """None when the kernels take (channels, n_agents) in the arithmetic in force, else why not, in words (``routes.plan`` prints it)."""
+        if not all(tuple(c.conv_gates.kernel_size) == (3, 3) for c in self.conv_gru.cell_list):
+            return "GRU kernels other than 3 x 3"
+        if channels != self.msg_cnn.out_channels or channels % 64 or not _bb.sp_channels_ok(2 * channels, 2 * channels) or not ops.v2v_shape_ok(channels, 1):
+            return f"{channels} channels outside C % 64 == 0, C <= 512"
+        if not ops.v2v_shape_ok(channels, n_agents):
+            return f"{n_agents} agents in a frame outside 1 .. 8"
+        return None if _bb.split_maps_active(terms) else "the SplitMap arithmetic (fp16 x 2) is not in force"
+
+    def plan_mlp(self, terms: Optional[int], ok: bool) -> dict:
+        """``mlp``'s line, noted with the fusion line (after the walk of the layers)."""
+        return {"fusion_net.mlp": (_bb.pointwise_text(self.mlp.in_features, terms) + ", 1 x 1 on the fused map" if ok else _bb.LINEAR_LIBRARY + ", V2VNetFusion op by op)", not ok)}
+
+    def plan_fusion(self, channels: int, terms: Optional[int] = None):
+        """-> (``routes.plan``'s fusion line, whether it is a fallback, {layers noted with it: (line, fallback)})."""
+        ok = self.kernel_route(channels, 1, terms)
+        return (self.KERNELS if ok else f"{self.TORCH} ({self.kernel_shape_reason(channels, 1, terms) or _bb.TORCH_MODE})"), not ok, self.plan_mlp(terms, ok)
+
+    def plan_layer(self, name: str, layer: nn.Module, channels: int, terms: Optional[int] = None, ok: Optional[bool] = None):
+        """-> (line, fallback) of msg_cnn and the GRU cells' convolutions; None for ``mlp``, which is noted with the fusion line.  ``ok``: the decision of a model
+        that takes the kernels for all of its parts or for none (the pose-robust V2VNet), in place of this module's own."""
+        if not isinstance(layer, nn.Conv2d):
+            return None
+        ok = self.kernel_route(channels, 1, terms) if ok is None else ok
+        what = (" (V2VNet: the warped-map and the ego columns as two C -> C convolutions)" if name.endswith("msg_cnn") else
+                " (V2VNet: update-gate rows of conv_gates stacked on conv_can, one convolution per GRU cell)")
+        return (_bb.SP + what if ok else _bb.MIOPEN + " (V2VNetFusion op by op)"), not ok
 
     # ---- the reference's loops, op by op -----------------------------------------------------------------------------------------------------------------
     def forward_torch(self, x: torch.Tensor, record_len, normalized_affine_matrix: torch.Tensor, weight: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -194,7 +194,19 @@ W2COMM_SIGNATURES = {
                                          POINTER(c_int32), c_int, P, POINTER(c_int32), c_int, P]),
 }
 
+# header under include/ -> its table, in the order of the ABI's growth: what both loaders bind (coalign_amd_lab.h's LAB_SIGNATURES: the laboratory library alone)
+HEADERS = dict(zip(_build.ABI_HEADERS[:-1], (SIGNATURES, NARROW_SIGNATURES, NARROW_SPARSE_SIGNATURES, ALIGN_SIGNATURES, STAGE1_SIGNATURES, DISCO_SIGNATURES, V2V_SIGNATURES,
+                                             V2X_SIGNATURES, V2X_WINDOW_SIGNATURES, W2C_SIGNATURES, V2VR_SIGNATURES, W2COMM_SIGNATURES)))
 _LAB_LIB = None
+
+
+def _bind(handle: ctypes.CDLL, tables) -> ctypes.CDLL:
+    for table in tables:
+        for name, (res, args) in table.items():
+            fn = getattr(handle, name)  # AttributeError here == header / library mismatch
+            fn.restype = res
+            fn.argtypes = args
+    return handle
 
 
 class CoalignHipError(RuntimeError):
@@ -219,11 +231,7 @@ def lib() -> ctypes.CDLL:
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(
                 f"{path} is missing and could not be built ({exc}); the CoAlign hot path has no CPU fallback") from exc
-    handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **V2X_WINDOW_SIGNATURES, **W2C_SIGNATURES, **V2VR_SIGNATURES, **W2COMM_SIGNATURES}.items():
-        fn = getattr(handle, name)  # AttributeError here == header / library mismatch
-        fn.restype = res
-        fn.argtypes = args
+    handle = _bind(ctypes.CDLL(path), HEADERS.values())
     if handle.coalign_abi_version() != 2:
         raise CoalignHipError(f"ABI version mismatch: library reports {handle.coalign_abi_version()}, binding expects 2")
     _LIB = handle
@@ -243,11 +251,7 @@ def lab_lib() -> ctypes.CDLL:
             _build.build(lab=True)
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(f"{path} is missing and could not be built ({exc})") from exc
-    handle = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **NARROW_SIGNATURES, **NARROW_SPARSE_SIGNATURES, **ALIGN_SIGNATURES, **STAGE1_SIGNATURES, **DISCO_SIGNATURES, **V2V_SIGNATURES, **V2X_SIGNATURES, **V2X_WINDOW_SIGNATURES, **W2C_SIGNATURES, **V2VR_SIGNATURES, **W2COMM_SIGNATURES, **LAB_SIGNATURES}.items():
-        fn = getattr(handle, name)
-        fn.restype = res
-        fn.argtypes = args
+    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), LAB_SIGNATURES])
     _LAB_LIB = handle
     return handle
 

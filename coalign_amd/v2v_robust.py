@@ -78,6 +78,13 @@ def xycs_to_tfm(xycs: torch.Tensor) -> torch.Tensor:
     return tfm
 
 
+# what ``routes.plan`` prints for the pose-robust model's fusion (``detector.PointPillarV2VNetRobust.plan_fusion``)
+KERNELS = ("v2vr_pairwise + v2v_warp_split + [conv3x3_sp + v2vr_pool_act] x 3 + conv3x3_sp_s2 + v2vr_pose_head (pose regression over all pairs) + v2vr_consistency (the whole "
+           "weighted EM in one launch) + v2v_warp_split + conv3x3_sp + v2vr_pool_act + conv3x3_sp + v2vr_score_head (attention; its warp also serves the fusion's first "
+           "iteration) + V2VNet's message passing with v2vr_aggregate (weighted sum over the senders)")
+TORCH = "PointPillarV2VNetRobust op by op in PyTorch"
+
+
 # ---- part 1: pose regression ---------------------------------------------------------------------------------------------------------------------------------
 class PoseRegression(nn.Module):
     """[N, 2C, H, W] -> [N, 3] (dx, dy, dyaw) (v2v_robust_module.py:19-60)."""
@@ -115,13 +122,33 @@ class _PairNet(nn.Module):
         C = conv.in_channels // 2
         return conv.weight[:, :C].contiguous(), conv.weight[:, C:].contiguous(), conv.bias
 
-    def kernel_route(self, channels: int, n_agents: int = 1, terms: Optional[int] = None, max_cav: int = 5) -> bool:
-        """The static half of the decision: eval mode, C and hidden multiples of 64 within ``conv3x3_sp``'s limits, at most 8 agents, SplitMap arithmetic in force."""
+    def widths_reason(self, channels: int) -> Optional[str]:
+        """None when C and hidden are multiples of 64 within ``conv3x3_sp``'s and the heads' limits, else the words of the pose-robust model's plan."""
         conv = self._net()[0]
         hidden = conv.out_channels
-        widths = (conv.in_channels == 2 * channels and channels % 64 == 0 and hidden % 64 == 0 and _bb.sp_channels_ok(channels, hidden) and _bb.sp_channels_ok(hidden, hidden)
-                  and ops.v2vr_shape_ok(channels, hidden, n_agents, max(max_cav, n_agents)))
-        return bool(not self.training and not self.force_torch and widths and _bb.split_maps_active(terms))
+        if (conv.in_channels == 2 * channels and channels % 64 == 0 and hidden % 64 == 0 and _bb.sp_channels_ok(channels, hidden) and _bb.sp_channels_ok(hidden, hidden)
+                and ops.v2vr_shape_ok(channels, hidden, 1)):
+            return None
+        return f"{channels} channels or hidden {hidden} outside C % 64 == 0"
+
+    def kernel_shape_reason(self, channels: int, n_agents: int = 1, terms: Optional[int] = None, max_cav: int = 5) -> Optional[str]:
+        """None when the kernels take (channels, n_agents) in the arithmetic in force, else why not, in words."""
+        why = self.widths_reason(channels)
+        if why is None and not ops.v2vr_shape_ok(channels, self._net()[0].out_channels, n_agents, max(max_cav, n_agents)):
+            why = f"{n_agents} agents in a frame outside 1 .. 8, or more than {ops.V2VR_MAX_CAV} slots"
+        return why if why is not None or _bb.split_maps_active(terms) else "the SplitMap arithmetic (fp16 x 2) is not in force"
+
+    def kernel_route(self, channels: int, n_agents: int = 1, terms: Optional[int] = None, max_cav: int = 5) -> bool:
+        """The static half of the decision: eval mode, C and hidden multiples of 64 within ``conv3x3_sp``'s limits, at most 8 agents, SplitMap arithmetic in force."""
+        return bool(not self.training and not self.force_torch and self.kernel_shape_reason(channels, n_agents, terms, max_cav) is None)
+
+    def plan_layer(self, name: str, layer: nn.Module, terms: Optional[int], ok: bool):
+        """-> (``routes.plan``'s line, fallback) of one convolution or linear of the net, given the model's ONE decision for its three parts."""
+        if isinstance(layer, nn.Linear):
+            return (self.HEAD if ok else _bb.LINEAR_LIBRARY + ", PointPillarV2VNetRobust op by op)"), not ok
+        first = " (the warped-map and the ego columns as two C -> hidden convolutions over all pairs; bias, pooling and LeakyReLU in v2vr_pool_act)" if name.endswith("model.0") else ""
+        kernel = _bb.SP_S2 + " (LeakyReLU, pooling and the mean in v2vr_pose_head)" if layer.stride[0] == 2 else _bb.SP + first
+        return (kernel if ok else _bb.MIOPEN + " (PointPillarV2VNetRobust op by op)"), not ok
 
     def _thetas(self, pairwise_t_matrix_b: torch.Tensor, Hr, Wr, H: int, W: int) -> torch.Tensor:
         return normalize_tfm(pairwise_t_matrix_b, Hr, Wr, H, W, self.downsample_rate, self.discrete_ratio)
@@ -139,6 +166,8 @@ class _PairNet(nn.Module):
 class PoseRegressionWraper(_PairNet):
     """features [sum(cav), C, H, W], record_len, pairwise_t_matrix [B, L, L, 4, 4] -> (pose_corr_matrix [B, L, L, 3], pairwise_t_matrix_new [B, L, L, 4, 4]):
     every receiver i and sender j, the diagonal included (v2v_robust_module.py:64-114)."""
+
+    HEAD = "v2vr_pose_head (all pairs in one workgroup, every row read once, fp32)"
 
     def __init__(self, in_ch: int, hidden_ch: int, affine_parameter: dict):
         super().__init__()
@@ -323,6 +352,8 @@ class Attention(nn.Module):
 class AttentionWrapper(_PairNet):
     """features, record_len, pairwise_t_matrix [B, L, L, 4, 4] -> (scores [B, L, L], weight [B, L, L]): scores[b, i, j] rates sender j in receiver i's frame,
     weight = score / (sum_j score + alpha + 1e-4) (v2v_robust_module.py:348-407).  ``alpha``: a learnable [1] parameter (0.15) or the constant 0.35."""
+
+    HEAD = "v2vr_score_head (cropped global max, linear, sigmoid and the weights, fp32)"
 
     def __init__(self, in_ch: int, hidden_ch: int, affine_parameter: dict, learnable_alpha: bool = True):
         super().__init__()

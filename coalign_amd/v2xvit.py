@@ -29,7 +29,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .backbone import _cache_of
+from .backbone import LINEAR_LIBRARY, TORCH_MODE, _cache_of
 from .encoder import host_ints
 
 # Measurement switch: the pyramid window attention and split attention of the kernel route on ``ops.v2x_window_attention`` (csrc/v2x_window.hip) instead of torch
@@ -558,6 +558,38 @@ class V2XViTFusion(nn.Module):
             return False
         enc = self.fusion_net.encoder
         return bool(hw is None or not enc.use_roi_mask or enc.sttf.positions(int(hw[0]), int(hw[1]))[2])
+
+    KERNELS = ("v2x_agent_attention per encoder layer: LayerNorm + folded q | k' | v' projection + softmax over the agents + output projection + residual in two launches; "
+               "pyramid window attention, split attention and feed-forward as torch ops on the device (library kernels)")
+    KERNELS_WINDOW = ("v2x_agent_attention + v2x_window_attention per encoder layer: the agent attention in two launches, the pyramid window attention with its split attention "
+                      "(LayerNorm + folded 9C x C projection, attention inside the 4 / 8 / 16 windows, branch weights, output projections + residual) in three or four; "
+                      "the feed-forward is still torch ops on the device (library kernels)")
+    TORCH = "V2XViTFusion op by op in PyTorch"
+    ATT, WIN, UNREAD = "v2x_agent_attention", "v2x_window_attention", "never read (every agent is of type 0; prior_feed has no caller)"
+
+    def plan_fusion(self, channels: int, terms: Optional[int] = None):
+        """-> (``routes.plan``'s fusion line, whether it is a fallback, {layers noted with it: (line, fallback)})."""
+        if self.kernel_route(channels):
+            return (self.KERNELS_WINDOW if self.window_kernel_reason(channels) is None else self.KERNELS), False, {}
+        return f"{self.TORCH} ({self.kernel_shape_reason(channels) or TORCH_MODE})", True, {}
+
+    def plan_layer(self, name: str, layer: nn.Module, channels: int, terms: Optional[int] = None):
+        """-> (line, fallback) of one of the transformer's linears."""
+        if not isinstance(layer, nn.Linear):
+            return None
+        ok, leaf = self.kernel_route(channels), name.split(".")
+        typed = leaf[-2] in ("q_linears", "k_linears", "v_linears", "a_linears")
+        if name.endswith("prior_feed") or (typed and leaf[-1] != "0"):
+            return self.UNREAD, False
+        if typed:
+            part = "output projection" if leaf[-2] == "a_linears" else "one third of the folded q | k' | v' projection"
+            return (f"{self.ATT} ({part}, fp16 x 2 on the matrix cores)" if ok else LINEAR_LIBRARY + ", V2XViTFusion op by op)"), not ok
+        if ok and (".pwmsa." in name or ".split_attn." in name) and self.window_kernel_reason(channels) is None:
+            part = ("one third of the folded 9C x C projection, fp16 x 2 on the matrix cores" if leaf[-1] == "to_qkv" else "output projection, fp16 x 2 on the matrix cores"
+                    if ".to_out." in name else "split attention's branch weights, fp32")
+            return f"{self.WIN} ({part})", False
+        block = "pyramid window attention" if ".pwmsa." in name else "split attention" if ".split_attn." in name else "feed-forward" if ".net." in name else "agent attention" if ".to_" in name else "time encoding"
+        return LINEAR_LIBRARY + f", {block}: torch op on the device)", True
 
     # ---- the reference's forward, op by op -----------------------------------------------------------------------------------------------------------------
     def forward_torch(self, x: torch.Tensor, record_len, normalized_affine_matrix: torch.Tensor) -> torch.Tensor:

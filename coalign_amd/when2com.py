@@ -164,6 +164,32 @@ class When2comFusion(nn.Module):
         """The static half of the decision (``routes.plan`` asks it): eval mode and a shape the kernels take.  ``forward`` adds: a CUDA float32 map."""
         return bool(not self.training and not self.force_torch and self.kernel_shape_reason(channels, n_agents, terms) is None)
 
+    KERNELS = ("v2v_warp_split + conv3x3_sp x 3 + conv3x3_sp_s2 x 3 + w2c_score + w2c_fuse per frame: the warped maps as SplitMaps, policy_net4 and the stacked key | query block on "
+               "the SplitMap convolutions, the pooled heads with the softmax over the agents in two launches, warp and weighted sum in one; a one-agent frame is w2c_fuse alone")
+    TORCH = "When2comFusion op by op in PyTorch"
+    SCORE, UNREAD = "w2c_score", "never read (AdditiveAttentin.forward does not use linear_out)"
+
+    def plan_fusion(self, channels: int, terms: Optional[int] = None):
+        """-> (``routes.plan``'s fusion line, whether it is a fallback, {layers noted with it: (line, fallback)})."""
+        if self.kernel_route(channels, 1, terms):
+            return self.KERNELS, False, {}
+        return f"{self.TORCH} ({self.kernel_shape_reason(channels, 1, terms) or _bb.TORCH_MODE})", True, {}
+
+    def plan_layer(self, name: str, layer: nn.Module, channels: int, terms: Optional[int] = None):
+        """-> (line, fallback) of one of this module's convolutions or linears."""
+        ok = self.kernel_route(channels, 1, terms)
+        if isinstance(layer, nn.Conv2d):
+            what = (" (When2com: stacked under key_net.conv1 in one launch; the ego's rows are read)" if name.startswith("fusion_net.query_net.") else
+                    " (When2com: query_net.conv1 stacked under it in one launch)" if name.startswith("fusion_net.key_net.") else " (When2com: every agent's warped map)")
+            return ((_bb.SP_S2 if layer.stride[0] == 2 else _bb.SP + _bb.SPLIT_OUT) + what if ok else _bb.MIOPEN + " (When2comFusion op by op)"), not ok
+        if name.endswith("attention_net.linear_out"):
+            return self.UNREAD, False
+        if not ok:
+            return _bb.LINEAR_LIBRARY + ", When2comFusion op by op)", True
+        part = ("first layer, 4480 inputs spread over 256 workgroups" if name.endswith("fc.0") else "second layer" if name.endswith("fc.2") else
+                "folded with the attention's linear into one 128 x 128 matrix" if name.endswith("fc.4") else "folded into the key / query net's last layer")
+        return f"{self.SCORE} ({part}, fp32)", False
+
     # ---- the reference, op by op ----------------------------------------------------------------------------------------------------------------------------------
     def frame_torch(self, x: torch.Tensor, theta: torch.Tensor):
         """One frame: x [N, C, H, W], theta [N, 2, 3] (the ego's row) -> (fused [1, C, H, W], logits [N], weights [N])."""

@@ -14,7 +14,7 @@ mask of the batch's agent number b (``Where2comm.frame_masks``); ``round`` is re
 the rate is the integer tensor 0.  Refused: ``agg_operator.mode: Transformer`` (it cannot run in the reference either, see ``Where2comm.__init__``)."""
 from __future__ import annotations
 
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -155,17 +155,31 @@ class Where2comm(nn.Module):
     def _modules_of(self) -> List[nn.Module]:
         return list(self.fuse_modules) if self.multi_scale else [self.fuse_modules]
 
+    KERNELS = ("w2comm_masks + w2comm_fuse_nhwc: the communication masks of every agent and level and the rates in one launch, then per frame the warp and fusion of "
+               "the masked maps of all levels in one launch (channels-last; no masked map is written)")
+    KERNELS_PLAIN = "warp_fuse_nhwc: all scales in one launch (channels-last); no communication section: no masks, rate 0"
+    TORCH = "Where2comm op by op in PyTorch"
+    MASKS = "w2comm_masks (the smoothing runs inside the mask launch, fp32)"
+
+    def kernel_shape_reason(self, channels: Sequence[int], n_agents: int = 1, resnet: bool = True, anchors: int = 1) -> Optional[str]:
+        """None when the kernels take maps of ``channels`` (one entry per level) from ``n_agents`` agents, else why not, in words (``routes.plan`` prints it)."""
+        channels, mods = list(channels), self._modules_of()
+        if self.multi_scale and not resnet:
+            return "a plain BaseBEVBackbone feeds every block the masked map of the one before: the levels cannot be fused in one launch"
+        if len(channels) != len(mods) or not 1 <= len(channels) <= 3 or any(c not in (64, 128, 256) for c in channels):
+            return f"maps of {channels} channels outside the kernel's 64 / 128 / 256, at most three levels"
+        if any(isinstance(m, AttenFusion) and m.feature_dim != c for m, c in zip(mods, channels)):
+            return "an attention whose feature_dim differs from its map's channels"
+        if not 1 <= n_agents <= 8:
+            return f"{n_agents} agents in a frame outside 1 .. 8"
+        if self.communication and not ops.w2comm_masks_shape_ok(anchors, [n_agents], self.naive_communication.kernel_size(), len(channels)):
+            return "a smoothing kernel (even, or larger than 9) or an anchor count (more than 8) the mask kernel does not take"
+        return None
+
     def kernel_route(self, channels: Sequence[int], n_agents: int = 1, resnet: bool = True, anchors: int = 1) -> bool:
-        """The static half of the decision (``routes.plan`` asks it): eval mode, maps of 64 / 128 / 256 channels (at most three levels, one in single-scale mode), plain
-        attention (``feature_dim`` = the map's channels), at most 8 agents per frame, a backbone with ``.resnet`` in multi-scale mode, a smoothing kernel the mask kernel
-        takes.  ``fuse`` adds: CUDA float32 channels-last maps, levels that halve exactly, logits of the kernel's anchor count."""
-        channels = list(channels)
-        mods = self._modules_of()
-        ok = len(channels) == len(mods) and 1 <= len(channels) <= 3 and all(c in (64, 128, 256) for c in channels) and 1 <= n_agents <= 8
-        ok = ok and all(not isinstance(m, AttenFusion) or m.feature_dim == c for m, c in zip(mods, channels)) and (resnet or not self.multi_scale)
-        if self.communication:
-            ok = ok and ops.w2comm_masks_shape_ok(anchors, [n_agents], self.naive_communication.kernel_size(), len(channels))
-        return bool(ok and not self.training and not self.force_torch)
+        """The static half of the decision (``routes.plan`` asks it): eval mode and shapes the kernels take.  ``fuse`` adds: CUDA float32 channels-last maps, levels that
+        halve exactly, logits of the kernel's anchor count."""
+        return bool(not self.training and not self.force_torch and self.kernel_shape_reason(channels, n_agents, resnet, anchors) is None)
 
     def _kernel_inputs_ok(self, xs: Sequence[torch.Tensor], rm: torch.Tensor, groups: Sequence[int], backbone) -> bool:
         anchors = rm.shape[1] if self.communication else 1
