@@ -15,6 +15,22 @@
 //                  channels, reads the cell map once (16 B), gathers the (rare, 5-6 % occupancy) pillar rows
 //                  and issues 16 B non-temporal stores, so the dominant traffic -- the dense canvas the
 //                  convolution backbone consumes -- is written exactly once, fully coalesced.
+//
+// Routes and their limits (tests/test_pillar_limits_gpu.py holds every route to a float64 evaluation at each of them):
+//   NCHW op           any P and C.  P <= 64 and C <= 64: cell map + the fused pillar_canvas_kernel (P <= 32, no distance, COALIGN_PILLAR_MFMA != 0: the matrix-core
+//                     encoder; else the fp32 VALU encoder, one pillar per wavefront for 32 < P <= 64); P > 64 or C > 64: pfn_kernel (points and channels in chunks
+//                     of 64) + canvas_kernel.
+//   channels-last op  P <= 32 and C <= 64, else COALIGN_ERR_UNSUPPORTED.  pillar_rows_mx_kernel unless the distance feature is on (not affine in the point), a tensor
+//                     reaches 2^32 bytes (32-bit byte offsets) or COALIGN_PILLAR_MFMA=0: then pillar_rows_nhwc_kernel (VALU).
+//   persistent, stream  additionally C % 4 == 0 (the previous frame's rows are cleared with 16-byte stores), else COALIGN_ERR_BAD_SHAPE.
+//   runs              pillar_rows_mx_kernel: a wavefront owns ceil(pairs / wavefronts) consecutive pillar pairs, at most kRunPairs = 32 (one lane per pillar builds the
+//                     records), streamed through LDS in rounds of kRound = 5 pairs.  launch_rows: two rounds per wavefront up to 512 workgroups, then longer runs,
+//                     beyond 32 pairs per wavefront more workgroups.  An odd pillar count leaves the last pair without its B pillar (its lanes store nothing).
+//   operands          the split-bf16 contraction has fp32's exponent range: no bound on |p - centre| or the intensity short of fp32 overflow; three bf16 terms carry
+//                     the full 24-bit significand (a term that is zero or below bf16's range only drops bits below 2^-24 of the operand).  Every feature set:
+//                     Cin = (4 or 1) + 6 (+ 1 distance) <= 11.  P < 32: the missing slots are never loaded (VALU) or loaded from slot P - 1 and zeroed (matrix core).
+//   counts            voxel_num_points >= 1: a count of 0 divides by zero in the reference; the matrix-core encoder answers relu(shift) there, the VALU encoder whatever
+//                     0 / 0 propagates to.  Counts above P are clamped to P for the rows, the mean still divides by the count as given (pillar_vfe.py:118-120).
 #include <stdlib.h>
 
 #include "common.h"

@@ -27,6 +27,24 @@
 // two that puts the largest of the four into [2^13, 2^14), wh = fp16(w), wl = fp16(w - wh).  sum_k (dh wh + dh wl + dl wh) in the fp32 accumulator drops only
 // dl wl (< 2^-20 of a product); 2^-(k_c + 6) rides on the sign factor of the epilogue (exact).  The A operands are the lane's own point after two
 // v_permlane32_swap.  Against float64 the features stay within 2e-6 of their scale (the bracket, evaluated in fp32 as before, carries the magnitude).
+//
+// Limits (tests/test_pillar_limits_gpu.py holds the kernel to float64 at each of them; nothing beyond the operating range is tested):
+//   shapes    1 <= P <= 32 (P < 32: the missing slots are loaded from slot P - 1 and zeroed before the mean), 1 <= C <= 64 (any C, also not a multiple of 4), no
+//             distance feature (it is not affine in the point: such configurations use pillar_scatter.hip), pillars * P * 16 and pillars * C * 4 below 2^32 bytes.
+//   runs      a wavefront owns a contiguous run of at most kRunPairs = 32 pillar pairs (one lane per pillar builds the records) and streams it through LDS in rounds
+//             of kRound = 4 pairs, the first two rounds issued before anything waits, kGroup = 2 pairs per straight-line region; an odd pillar count leaves the last
+//             pair without its B pillar (nothing is stored for it).  encode_sparse sizes the grid so that no run exceeds 32 pairs.
+//   operands  d = (p - centre) * 2^6 and intensity * 2^6 are rounded to fp16, whose largest finite value is 65 504: the split is finite for |p - centre| < 1023.5 m and
+//             intensity < 1023.5.  Inside a 0.4 m x 0.4 m cell |d| <= 12.8 in x and y; in z |d| <= 128 (4 m cells, OPV2V) or 160 (5 m cells, DAIR-V2X); intensity in
+//             [0, 1] gives d <= 64, raw 8-bit intensities up to 255 give d <= 16 320.  dh keeps 11 bits of d and dl up to 11 more; where dl falls below fp16's
+//             smallest normal number 2^-14 (offsets of about 2 mm = 0.128 / 2^6 m and less) it is subnormal with the spacing 2^-24: the pair then resolves d to 2^-25,
+//             i.e. 2^-31 m = 4.7e-10 m absolute (the "5e-10 m" above).  Offsets of exactly 0 are exact.  Points that coincide with each other are fine (their
+//             offset to the MEAN is not an operand: the mean enters through the fp32 bracket).
+//   weights   the largest of a channel's four summed weights is scaled into [2^13, 2^14) (wh <= 2^14 < 65 504); the exponent k_c is clamped to [-60, 60], and a channel
+//             whose four summed weights are all zero takes k_c = 0 (its operands are zero, the bracket and the shift remain).  A weight 2^-20 of the channel's largest
+//             still has a normal wh (about 2^-7 after the scaling) and a subnormal wl (spacing 2^-24): it is resolved to 2^-25, that is 2^-38 of the channel's largest weight.
+//   counts    voxel_num_points >= 1; 0 yields relu(shift) (documented deviation: the reference divides by zero).  A device-side count (M_dev, frame->M) is clamped to
+//             [0, M_capacity]; rows at and beyond it are neither read nor written, and the frame tag advances once per launch whatever the count.
 #include <stdlib.h>
 
 #include "common.h"

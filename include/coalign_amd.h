@@ -58,6 +58,10 @@ const char *coalign_last_hip_error(void);
  *                 element is written (zeros where no pillar).  If two pillars of one agent share a cell the one
  *                 with the larger row index wins (the reference's sequential CPU indexing semantics).
  * workspace       coalign_pillar_scatter_workspace_bytes(n_agents, ny, nx) bytes
+ * Limits: any P >= 1 and C >= 1 here; the channels-last entry below answers COALIGN_ERR_UNSUPPORTED unless P <= 32 and C <= 64, the persistent and the stream
+ *   entry COALIGN_ERR_BAD_SHAPE unless also C % 4 == 0.  voxel_num_points >= 1 (a count of 0 divides by zero in the reference; the result is then unspecified
+ *   here).  The matrix-core encoder behind P <= 32, C <= 64 without the distance feature splits its operands into three bf16 terms: fp32's exponent range, no
+ *   bound on the point offsets or the intensity.  Against a float64 evaluation of the reference's formula the rows stay within 2e-6 of their largest magnitude.
  */
 size_t coalign_pillar_scatter_workspace_bytes(int n_agents, int ny, int nx);
 int coalign_pillar_vfe_scatter(const float *voxel_features, const int32_t *voxel_num_points, const int32_t *voxel_coords,
@@ -445,7 +449,12 @@ int coalign_fill_words(void *p, size_t n_words, uint32_t value, void *stream);
 
 /* (1b) Round 4: PillarVFE + PointPillarScatter as ONE launch with a SPARSE canvas (csrc/pillar_sparse.hip).  Replaces the same reference modules as (1)
  * (pillar_vfe.py:31-53,105-155, point_pillar_scatter.py:15-72) for callers that consume the canvas through (9d) / (10b) below.
- *   pillar_features [M_capacity, C] out: the feature rows (C <= 64, P <= 32; the linearised PFN evaluated exactly in fp32 on v_mfma_f32_32x32x2_f32).
+ *   pillar_features [M_capacity, C] out: the feature rows (1 <= C <= 64, 1 <= P <= 32, else COALIGN_ERR_BAD_SHAPE; since round 5 the linearised PFN runs as one
+ *     v_mfma_f32_32x32x16_f16 per pillar and 32 channels on a 22-bit fp16 split of its operands, the per-pillar terms in fp32).  Operating range of that split:
+ *     (p - cell centre) * 2^6 and intensity * 2^6 are rounded to fp16, largest finite value 65 504, so |p - centre| and the intensity must stay below 1023.5; points
+ *     inside their cell give at most 12.8 (x, y: 0.4 m cells), 128 / 160 (z: 4 m / 5 m cells), intensities up to 1 / 255 give 64 / 16 320.  Offsets below about 2 mm
+ *     keep an absolute resolution of 4.7e-10 m.  Within that range the rows stay within 2e-6 of their largest magnitude against float64.  voxel_num_points >= 1
+ *     (0 yields relu(shift): the reference divides by zero).  Rows at and beyond the device-side count are neither read nor written.
  *   stamps: coalign_sparse_canvas_stamp_bytes(n_agents, ny, nx) bytes, 8-byte aligned, ZERO-INITIALISED ONCE by the caller and then owned by this
  *     sequence of calls: 64-bit words (frame tag << 32) | pillar row per cell, entered by atomicMax -- the larger row of a cell wins, the reference's rule.
  *   state: coalign_sparse_canvas_state_bytes() bytes (int32[528] since round 6; [2] before), zero-initialised once: state[0] = tag of the last completed call, the rest

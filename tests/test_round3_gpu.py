@@ -13,6 +13,7 @@ from coalign_amd import ops
 from coalign_amd.config import builtin_config
 from coalign_amd.detector import build_model, to_device
 from coalign_amd.synthetic import fill_parameters_, make_frame
+from tests.pillar_reference import pfn_f64
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -22,21 +23,7 @@ P = "pillar_vfe.pfn_layers.0."
 
 def _pfn64(pl, sd, margs):
     """PillarVFE (pillar_vfe.py:105-155, PFNLayer :31-53) evaluated in float64 from the float32 inputs: the yardstick for both encoders."""
-    vf = pl["voxel_features"].double()
-    npts = pl["voxel_num_points"].double()
-    cd = pl["voxel_coords"]
-    vs, r = margs["voxel_size"], margs["lidar_range"]
-    mean = vf[:, :, :3].sum(1, keepdim=True) / npts.view(-1, 1, 1)
-    f32 = lambda v: torch.tensor(v, dtype=torch.float32)
-    ctr = torch.stack([cd[:, 3].float() * f32(vs[0]) + f32(vs[0] / 2 + r[0]), cd[:, 2].float() * f32(vs[1]) + f32(vs[1] / 2 + r[1]),
-                       cd[:, 1].float() * f32(vs[2]) + f32(vs[2] / 2 + r[2])], 1).double()           # the float32 centre the reference forms
-    f = torch.cat([vf, vf[:, :, :3] - mean, vf[:, :, :3] - ctr[:, None, :]], -1)
-    mask = (torch.arange(vf.shape[1])[None, :] < pl["voxel_num_points"][:, None]).double()[..., None]
-    f = f * mask
-    x = f @ sd[P + "linear.weight"].double().t()
-    alpha = sd[P + "norm.weight"].double() / torch.sqrt(sd[P + "norm.running_var"].double() + 1e-3)
-    x = (x - sd[P + "norm.running_mean"].double()) * alpha + sd[P + "norm.bias"].double()
-    return torch.relu(x).max(1)[0]
+    return pfn_f64(pl["voxel_features"], pl["voxel_num_points"], pl["voxel_coords"], sd, margs["voxel_size"], margs["lidar_range"])
 
 
 def _run_pillar(pl, sd, margs, n_agents, cl, use_abs=True):
@@ -108,18 +95,7 @@ def test_matrix_core_encoder_without_absolute_xyz():
     g = torch.Generator().manual_seed(2)
     sd = {P + "linear.weight": torch.randn(64, 7, generator=g) * 0.3, P + "norm.weight": torch.randn(64, generator=g), P + "norm.bias": torch.randn(64, generator=g) * 0.1,
           P + "norm.running_mean": torch.randn(64, generator=g) * 0.1, P + "norm.running_var": torch.rand(64, generator=g) + 0.5}
-    vf = pl["voxel_features"].double()
-    mean = vf[:, :, :3].sum(1, keepdim=True) / pl["voxel_num_points"].double().view(-1, 1, 1)
-    vs, r = margs["voxel_size"], margs["lidar_range"]
-    cd = pl["voxel_coords"]
-    f32 = lambda v: torch.tensor(v, dtype=torch.float32)
-    ctr = torch.stack([cd[:, 3].float() * f32(vs[0]) + f32(vs[0] / 2 + r[0]), cd[:, 2].float() * f32(vs[1]) + f32(vs[1] / 2 + r[1]),
-                       cd[:, 1].float() * f32(vs[2]) + f32(vs[2] / 2 + r[2])], 1).double()
-    f = torch.cat([vf[:, :, 3:], vf[:, :, :3] - mean, vf[:, :, :3] - ctr[:, None, :]], -1)
-    f = f * (torch.arange(32)[None, :] < pl["voxel_num_points"][:, None]).double()[..., None]
-    x = f @ sd[P + "linear.weight"].double().t()
-    alpha = sd[P + "norm.weight"].double() / torch.sqrt(sd[P + "norm.running_var"].double() + 1e-3)
-    want = torch.relu((x - sd[P + "norm.running_mean"].double()) * alpha + sd[P + "norm.bias"].double()).max(1)[0]
+    want = pfn_f64(pl["voxel_features"], pl["voxel_num_points"], pl["voxel_coords"], sd, margs["voxel_size"], margs["lidar_range"], use_absolute_xyz=False)
     for cl in (True, False):
         feats, _ = _run_pillar(pl, sd, margs, 2, cl, use_abs=False)
         assert float((feats.cpu().double() - want).abs().max()) <= 2e-6 * float(want.abs().max())
@@ -128,7 +104,10 @@ def test_matrix_core_encoder_without_absolute_xyz():
 _PILLAR_TESTS = ["tests/test_hip_parity.py::test_pillar_golden_mini", "tests/test_hip_parity.py::test_pillar_fullsize_vs_oracle_and_reference",
                  "tests/test_hip_parity.py::test_pillar_edge_cases", "tests/test_hip_parity.py::test_pillar_dense_duplicates_and_unfused_route",
                  "tests/test_round2_gpu.py::test_pillar_channels_last_canvas_equals_nchw", "tests/test_round2_gpu.py::test_pillar_persistent_canvas_equals_fresh_canvas",
-                 "tests/test_round3_gpu.py::test_matrix_core_encoder_against_float64"]
+                 "tests/test_round3_gpu.py::test_matrix_core_encoder_against_float64",
+                 # the limit suite's default-flag cases (small counts, shapes, input range): the VALU encoder against the same float64 yardstick
+                 "tests/test_pillar_limits_gpu.py::test_small_pillar_counts", "tests/test_pillar_limits_gpu.py::test_shapes_with_the_default_flags",
+                 "tests/test_pillar_limits_gpu.py::test_input_range"]
 
 
 def test_valu_pillar_encoder_in_a_subprocess():
