@@ -20,6 +20,7 @@
 #include "common.h"
 #include "warp_taps.h"
 #include "nhwc_lanes.h"
+#include "w2comm_fuse_tile.h"
 #include "coalign_amd_where2comm.h"
 
 namespace {
@@ -139,132 +140,31 @@ __global__ __launch_bounds__(kMaskThreads) void w2comm_masks_kernel(const MaskAr
 }
 
 // ---- (2) masked warp + fusion, channels-last ---------------------------------------------------------------------------------------------------------------------
-constexpr int kMaxScales = 3;
-
-struct ScaleArgs {
-    const float *x;       // [n, H, W, C] of this frame
-    const uint8_t *mask;  // [n, H, W]
-    float *out;           // [Ho, Wo, C]
-    int C, H, W, Ho, Wo, tiles_x, ntiles, first_block, n_blocks, log2C;
-    float sqrt_dim, inv_sqrt_dim;
-};
-
+// The tile itself is w2comm_fuse_tile.h's (shared with w2comm_msg.hip); this is its source policy for dense planes of one tensor behind a row table.
 struct FuseArgs {
     ScaleArgs s[kMaxScales];
     const double *theta;  // [n, 2, 3]
     int n_scales, n, mode;
     int rows[8];
-};
+    static constexpr bool kPacked = false;
 
-template <int NA, int LPP>
-__device__ __forceinline__ void fuse_tile(const FuseArgs &f, const ScaleArgs &a, int tile, int wave, int lane) {
-    constexpr int PPW = 64 / LPP;
-    const int li = lane % LPP, pi = lane / LPP;
-    const int c_lo = 4 * li, hi4 = a.C / 8;
-    const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
-    const int oy = ty * 4 + wave;
-    if (oy >= a.Ho) return;                        // wave-uniform
-    const int ox_raw = tx * PPW + pi;
-    const bool pix_ok = ox_raw < a.Wo;
-    const int ox = pix_ok ? ox_raw : a.Wo - 1;
-    float X[NA][8];
-    const size_t plane = (size_t)a.H * a.W * a.C;
-    const int my_agent = min(li, f.n - 1);
-    Taps mine = make_taps(a, f.theta, my_agent, ox, oy);                             // lane li of the pixel: agent li's taps
-    {
-        // x_j * mask_j (where2comm_attn.py:269, :275, :334) folded into the weights: the byte of each tap's source pixel, in the row of x that holds agent li.
-        // A clamped tap lies inside the plane and its weight is zero already.
-        int row = f.rows[0];
+    // The mask byte of each tap's source pixel, in the row of x that holds the agent.
+    __device__ __forceinline__ void mask_taps(const ScaleArgs &a, int, int agent, Taps &t) const {
+        int row = rows[0];
 #pragma unroll
-        for (int i = 1; i < 8; ++i) row = my_agent == i ? f.rows[i] : row;
+        for (int i = 1; i < 8; ++i) row = agent == i ? rows[i] : row;
         const uint8_t *m = a.mask + (size_t)row * (a.H * a.W);
-        mine.w00 *= (float)m[mine.o00 >> a.log2C];
-        mine.w01 *= (float)m[mine.o01 >> a.log2C];
-        mine.w10 *= (float)m[mine.o10 >> a.log2C];
-        mine.w11 *= (float)m[mine.o11 >> a.log2C];
+        t.w00 *= (float)m[t.o00 >> a.log2C];
+        t.w01 *= (float)m[t.o01 >> a.log2C];
+        t.w10 *= (float)m[t.o10 >> a.log2C];
+        t.w11 *= (float)m[t.o11 >> a.log2C];
     }
-    Taps cur = taps_of_agent<LPP>(mine, 0), nxt;
-    float4 vc[8], vn[8];
-    issue(cur, a.x + f.rows[0] * plane + c_lo, hi4, vc);
-#pragma unroll
-    for (int n = 0; n < NA; ++n) {
-        if (n < f.n) {
-            if (n + 1 < NA && n + 1 < f.n) {   // the next agent's taps are in flight while this one is blended
-                nxt = taps_of_agent<LPP>(mine, n + 1);
-                issue(nxt, a.x + f.rows[(n + 1) % 8] * plane + c_lo, hi4, vn);
-            }
-            blend(cur, vc, X[n]);
-            if (n + 1 < NA && n + 1 < f.n) {
-                cur = nxt;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) vc[j] = vn[j];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) X[n][j] = 0.f;
-        }
-    }
-    const size_t opix = ((size_t)oy * a.Wo + ox) * a.C + c_lo;
-    float o[8];
-    if (f.mode == COALIGN_FUSE_ATT) {              // AttenFusion (where2comm_attn.py:44-54): the arithmetic of warp_fuse_nhwc.hip, instruction for instruction
-        float s[NA];
-        float smax = -INFINITY;
-#pragma unroll
-        for (int n = 0; n < NA; ++n) {
-            float p = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) p = fmaf(X[0][j], X[n][j], p);
-            s[n] = (LPP == 16) ? group_sum<LPP>(p) / a.sqrt_dim : group_sum<LPP>(p) * a.inv_sqrt_dim;
-            if (n < f.n) smax = fmaxf(smax, s[n]);
-        }
-        float den = 0.f;
-#pragma unroll
-        for (int n = 0; n < NA; ++n) {
-            s[n] = (n < f.n) ? __builtin_amdgcn_exp2f((s[n] - smax) * 1.44269504088896341f) : 0.f;
-            den += s[n];
-        }
-        const float inv_den = 1.0f / den;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = 0.f;
-#pragma unroll
-        for (int n = 0; n < NA; ++n) {
-            const float sn = s[n] * inv_den;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = fmaf(sn, X[n][j], o[j]);
-        }
-    } else {                                        // MaxFusion (where2comm_attn.py:56-61)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = -INFINITY;
-#pragma unroll
-        for (int n = 0; n < NA; ++n)
-            if (n < f.n) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = fmaxf(o[j], X[n][j]);
-            }
-    }
-    if (pix_ok) {
-        coalign::store_stream(reinterpret_cast<float4 *>(a.out + opix), make_float4(o[0], o[1], o[2], o[3]));
-        coalign::store_stream(reinterpret_cast<float4 *>(a.out + opix + a.C / 2), make_float4(o[4], o[5], o[6], o[7]));
-    }
-}
+    __device__ __forceinline__ const float *plane(const ScaleArgs &a, int, int n) const { return a.x + rows[n] * ((size_t)a.H * a.W * a.C); }
+};
 
 template <int NA>
 __global__ __launch_bounds__(256) void w2comm_fuse_nhwc_kernel(const FuseArgs f) {
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int bid = blockIdx.x;
-#pragma unroll
-    for (int k = 0; k < kMaxScales; ++k) {
-        if (k < f.n_scales && bid >= f.s[k].first_block && bid < f.s[k].first_block + f.s[k].n_blocks) {
-            const ScaleArgs &a = f.s[k];
-            const int tile = coalign::xcd_remap(bid - a.first_block, a.n_blocks);   // first_block and n_blocks are multiples of 8
-            if (tile >= a.ntiles) return;
-            const int lpp = a.C / 8;
-            if (lpp == 8) fuse_tile<NA, 8>(f, a, tile, wave, lane);
-            else if (lpp == 16) fuse_tile<NA, 16>(f, a, tile, wave, lane);
-            else fuse_tile<NA, 32>(f, a, tile, wave, lane);
-            return;
-        }
-    }
+    COALIGN_W2COMM_FUSE_BLOCK(NA, f);
 }
 
 }  // namespace
@@ -327,32 +227,18 @@ extern "C" int coalign_w2comm_fuse_nhwc(int n_scales, const float *const *x, con
         }
         f.rows[i] = r;
     }
-    // heaviest tiles first: order the scales by channel count, descending
-    int order[kMaxScales] = {0, 1, 2};
-    for (int i = 0; i < n_scales; ++i)
-        for (int j = i + 1; j < n_scales; ++j)
-            if (C[order[j]] > C[order[i]]) { const int t = order[i]; order[i] = order[j]; order[j] = t; }
-    int next_block = 0;
-    for (int k = 0; k < n_scales; ++k) {
-        const int i = order[k];
+    for (int i = 0; i < n_scales; ++i) {
         if (!x[i] || !out[i] || !masks[i]) return COALIGN_ERR_NULL_POINTER;
         if (C[i] < 1 || H[i] < 1 || W[i] < 1 || Ho[i] < 1 || Wo[i] < 1) return COALIGN_ERR_BAD_SHAPE;
         if (C[i] != 64 && C[i] != 128 && C[i] != 256) return COALIGN_ERR_UNSUPPORTED;
         if ((size_t)C[i] * H[i] * W[i] > (size_t)INT32_MAX) return COALIGN_ERR_BAD_SHAPE;
         if ((reinterpret_cast<uintptr_t>(x[i]) | reinterpret_cast<uintptr_t>(out[i])) & 15) return COALIGN_ERR_UNSUPPORTED;
-        ScaleArgs &a = f.s[k];
-        a.x = x[i]; a.mask = masks[i]; a.out = out[i]; a.C = C[i]; a.H = H[i]; a.W = W[i]; a.Ho = Ho[i]; a.Wo = Wo[i];
-        a.log2C = C[i] == 64 ? 6 : C[i] == 128 ? 7 : 8;
-        a.tiles_x = (Wo[i] + (512 / C[i]) - 1) / (512 / C[i]);       // 64 lanes / (C / 8 lanes per pixel) pixels per wave
-        a.ntiles = a.tiles_x * ((Ho[i] + 3) / 4);
-        a.n_blocks = (a.ntiles + 7) / 8 * 8;
-        a.first_block = next_block;
-        a.sqrt_dim = (float)sqrt((double)C[i]);
-        a.inv_sqrt_dim = 1.0f / a.sqrt_dim;
-        next_block += a.n_blocks;
     }
+    int order[kMaxScales];
+    const int n_blocks = plan_scales(f.s, order, n_scales, C, H, W, Ho, Wo, out);      // heaviest tiles first
+    for (int k = 0; k < n_scales; ++k) { f.s[k].x = x[order[k]]; f.s[k].mask = masks[order[k]]; }
     for (int k = n_scales; k < kMaxScales; ++k) f.s[k] = f.s[0];
-    const dim3 grid(next_block), block(256);
+    const dim3 grid(n_blocks), block(256);
     if (n == 1) hipLaunchKernelGGL(w2comm_fuse_nhwc_kernel<1>, grid, block, 0, stream, f);
     else if (n == 2) hipLaunchKernelGGL(w2comm_fuse_nhwc_kernel<2>, grid, block, 0, stream, f);
     else if (n == 3) hipLaunchKernelGGL(w2comm_fuse_nhwc_kernel<3>, grid, block, 0, stream, f);

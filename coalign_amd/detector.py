@@ -419,7 +419,13 @@ class PointPillarWhere2comm(PointPillarBaselineMultiscale):
     Forward: every agent's multi-scale maps; decode, shrink header and ``cls_head`` on EVERY agent give the single-agent logits the masks are made of;
     ``multi_scale: true``: masked fusion of the backbone's levels, then decode, shrink header and heads on the fused map; otherwise: masked fusion of the agents'
     shrunk maps, then the heads.  Output: the other models' dict plus ``comm_rates``, a 0-d device tensor.  ``encode`` / ``fuse_and_head`` and the two ``accepts_*``
-    flags keep ``PointPillarBaselineMultiscale``'s contracts; the single-agent logits travel as the LAST entry of the feature list."""
+    flags keep ``PointPillarBaselineMultiscale``'s contracts; the single-agent logits travel as the LAST entry of the feature list.
+
+    ``packed_wire`` (False; settable on the class, an instance, or by the model arguments' optional ``packed_wire`` key): ``fuse_and_head`` goes through MESSAGES --
+    every non-ego agent's masked pixels packed into a ``where2comm.W2Message``, the fusion reading the ego's dense maps and the messages -- to the same heads, and the
+    output gains ``messages`` (per frame, the list of its non-ego agents' messages) and ``comm_bytes`` (a 0-d int64 device tensor: the messages' sizes summed on the
+    device from their counts).  A route the message kernels do not serve raises; nothing falls back.  With the flag off nothing differs, ``state_dict`` included."""
+    packed_wire = False
 
     def __init__(self, args: dict):
         if "where2comm" not in args:
@@ -428,6 +434,8 @@ class PointPillarWhere2comm(PointPillarBaselineMultiscale):
         del self.fusion_net
         self.fusion_net = Where2commFusion(args["where2comm"])
         self.multi_scale = bool(self.fusion_net.multi_scale)
+        if "packed_wire" in args:
+            self.packed_wire = bool(args["packed_wire"])
         if self.multi_scale and self.fusion_net.num_levels != self.backbone.num_levels:
             raise ValueError(f"where2comm.layer_nums names {self.fusion_net.num_levels} levels, the backbone has {self.backbone.num_levels}")
 
@@ -446,7 +454,12 @@ class PointPillarWhere2comm(PointPillarBaselineMultiscale):
         """-> (``routes.plan``'s fusion line, whether it is a fallback, {layers noted with it})."""
         f = self.fusion_net
         if self.kernel_route() and (not f.multi_scale or (_bb.NHWC_STAGE_OUTPUTS and _bb.emu_active(terms))):      # (channels-last stage outputs)
+            if self.packed_wire:          # (served only with a communication section; otherwise the refusal, in the words ``fuse`` raises with)
+                reason = f.packed_route_reason(*self._route_args(1))
+                return (f.KERNELS_PACKED, False, {}) if reason is None else (f"packed wire refused ({reason})", True, {})
             return (f.KERNELS if f.communication else f.KERNELS_PLAIN), False, {}
+        if self.packed_wire:
+            return f"packed wire refused ({f.packed_route_reason(*self._route_args(1)) or 'stage outputs not channels-last, ' + _bb.TORCH_MODE})", True, {}
         return f"{f.TORCH} ({self.kernel_route_reason() or 'stage outputs not channels-last, ' + _bb.TORCH_MODE})", True, {}
 
     def plan_layer(self, name: str, layer: nn.Module, channels=None, terms: Optional[int] = None):
@@ -473,16 +486,23 @@ class PointPillarWhere2comm(PointPillarBaselineMultiscale):
     def fuse_and_head(self, feature_list, record_len, affine, rows=None) -> dict:
         """Ego part: the masked fusion, (decode and shrink header,) the heads."""
         *maps, psm = feature_list
+        wire, messages = ("packed" if self.packed_wire else "dense"), None
         if not self.multi_scale:
-            x, rates, _ = self.fusion_net.fuse(maps[0], psm, record_len, affine, rows=rows)
+            x, rates, extra = self.fusion_net.fuse(maps[0], psm, record_len, affine, rows=rows, wire=wire)
+            messages = extra.get("messages")
         elif hasattr(self.backbone, "resnet"):
-            fused, rates = self.fusion_net.fuse(None, psm, record_len, affine, self.backbone, feats=maps, rows=rows, decode=False)
+            fused, rates, *sent = self.fusion_net.fuse(None, psm, record_len, affine, self.backbone, feats=maps, rows=rows, decode=False, wire=wire)
+            messages = sent[0] if sent else None
             x = self._decode_shrink(fused, out_split=heads_take_split_map(self)) if isinstance(fused, list) else self._shrink_decoded(fused)
         else:
-            x, rates, _ = self.fusion_net.fuse(maps[0], psm, record_len, affine, self.backbone, rows=rows)
+            x, rates, extra = self.fusion_net.fuse(maps[0], psm, record_len, affine, self.backbone, rows=rows, wire=wire)
+            messages = extra.get("messages")
             x = self._shrink_decoded(x)
         out = _run_heads(self, x)
         out["comm_rates"] = torch.as_tensor(rates, device=psm.device)
+        if self.packed_wire:
+            out["messages"] = messages
+            out["comm_bytes"] = sum((m.nbytes_device() for frame in messages for m in frame), torch.zeros((), dtype=torch.int64, device=psm.device))
         return out
 
     def _shrink_decoded(self, x):

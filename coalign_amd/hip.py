@@ -194,6 +194,17 @@ W2COMM_SIGNATURES = {
                                          POINTER(c_int32), c_int, P, POINTER(c_int32), c_int, P]),
 }
 
+# csrc/coalign_amd_where2comm_msg.h (build.MSG_HEADER): the twelfth extension header of ABI version 2 (product library): Where2comm's messages -- bitmaps, rank
+# tables and counts of every agent and level in one launch, the masked pixels' rows packed in one launch, and the fusion that reads dense and packed sources
+# (csrc/w2comm_msg.hip).  The reference has no counterpart.
+W2COMM_MSG_SIGNATURES = {
+    "coalign_w2comm_msg_index": (c_int, [c_int, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(P), POINTER(P), POINTER(P), P, P]),
+    "coalign_w2comm_msg_pack": (c_int, [c_int, c_int, POINTER(P), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(P), POINTER(P), POINTER(P), P]),
+    "coalign_w2comm_fuse_packed": (c_int, [c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(P), POINTER(P), POINTER(P), POINTER(P),
+                                           POINTER(c_int32), POINTER(c_int32), c_int, P, c_int, P]),
+}
+MSG_HEADER = _build.MSG_HEADER
+
 # header under include/ -> its table, in the order of the ABI's growth: what both loaders bind (coalign_amd_lab.h's LAB_SIGNATURES: the laboratory library alone)
 HEADERS = dict(zip(_build.ABI_HEADERS[:-1], (SIGNATURES, NARROW_SIGNATURES, NARROW_SPARSE_SIGNATURES, ALIGN_SIGNATURES, STAGE1_SIGNATURES, DISCO_SIGNATURES, V2V_SIGNATURES,
                                              V2X_SIGNATURES, V2X_WINDOW_SIGNATURES, W2C_SIGNATURES, V2VR_SIGNATURES, W2COMM_SIGNATURES)))
@@ -231,7 +242,7 @@ def lib() -> ctypes.CDLL:
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(
                 f"{path} is missing and could not be built ({exc}); the CoAlign hot path has no CPU fallback") from exc
-    handle = _bind(ctypes.CDLL(path), HEADERS.values())
+    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), W2COMM_MSG_SIGNATURES])
     if handle.coalign_abi_version() != 2:
         raise CoalignHipError(f"ABI version mismatch: library reports {handle.coalign_abi_version()}, binding expects 2")
     _LIB = handle
@@ -251,7 +262,7 @@ def lab_lib() -> ctypes.CDLL:
             _build.build(lab=True)
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(f"{path} is missing and could not be built ({exc})") from exc
-    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), LAB_SIGNATURES])
+    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), W2COMM_MSG_SIGNATURES, LAB_SIGNATURES])
     _LAB_LIB = handle
     return handle
 

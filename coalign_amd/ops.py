@@ -2065,3 +2065,135 @@ def w2comm_fuse_nhwc(xs: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], 
                                                      i32(*[x.shape[2] for x in xs]), i32(*[x.shape[3] for x in xs]), n, _ptr(th), rw, mode, _stream()),
                   "coalign_w2comm_fuse_nhwc")
     return outs
+
+
+# ---- Where2comm's messages (csrc/coalign_amd_where2comm_msg.h, csrc/w2comm_msg.hip) -------------------------------------------------------------------------------
+W2COMM_SRC_DENSE, W2COMM_SRC_PACKED = 0, 1
+
+
+def w2comm_msg_shape_ok(channels: Sequence[int], n_agents: int = 1, hw: Optional[Sequence[Tuple[int, int]]] = None) -> bool:
+    """What the three message kernels take: 1 .. 3 levels of 64 / 128 / 256 channels, 1 .. 8 agents, maps of fewer than 2^31 values."""
+    ok = 1 <= len(channels) <= W2COMM_MAX_LEVELS and all(int(c) in (64, 128, 256) for c in channels) and 1 <= int(n_agents) <= 8
+    return bool(ok and (hw is None or (len(hw) == len(channels) and all(h >= 1 and w >= 1 and c * h * w < 2 ** 31 for c, (h, w) in zip(channels, hw)))))
+
+
+def w2comm_msg_index_shape_ok(n_agents: int, hw: Sequence[Tuple[int, int]]) -> bool:
+    """What ``coalign_w2comm_msg_index`` takes: 1 .. 8 agents, 1 .. 3 levels of at least one pixel and fewer than 2^31."""
+    return bool(1 <= int(n_agents) <= 8 and 1 <= len(hw) <= W2COMM_MAX_LEVELS and all(h >= 1 and w >= 1 and h * w < 2 ** 31 for h, w in hw))
+
+
+def _words(w: int) -> int:
+    return (int(w) + 31) // 32
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * max(1, len(tensors)))(*[0 if t is None else t.data_ptr() for t in tensors])
+
+
+def _i32_array(values):
+    return (ctypes.c_int32 * max(1, len(values)))(*[int(v) for v in values])
+
+
+@_device_op
+def w2comm_msg_index(masks: Optional[Sequence[torch.Tensor]], bits: Optional[Sequence[torch.Tensor]] = None, hw: Optional[Sequence[Tuple[int, int]]] = None):
+    """Bitmaps, rank tables and counts of n agents at every level in one launch (``coalign_w2comm_msg_index``).  Sender form: ``masks[l]`` [n, H_l, W_l] uint8
+    (nonzero = set).  Receiver form: ``masks`` None, ``bits[l]`` [n, H_l, ceil(W_l / 32)] int32 (the words' bit patterns) and ``hw`` [(H_l, W_l)].
+    -> (bits per level [n, H_l, Wd_l] int32, rank per level [n, H_l, Wd_l] int32, count [n, levels] int32)."""
+    given = masks if masks is not None else bits
+    if given is None or len(given) < 1:
+        raise ValueError("w2comm_msg_index: masks (sender) or bits and hw (receiver)")
+    _need_gpu(*given)
+    n, dev = int(given[0].shape[0]), given[0].device
+    if masks is not None:
+        if any(m.dtype != torch.uint8 or m.dim() != 3 or m.shape[0] != n or m.device != dev for m in masks):
+            raise ValueError("w2comm_msg_index: one uint8 mask [n, H, W] per level, on one device")
+        masks = [m.contiguous() for m in masks]
+        hw = [(int(m.shape[1]), int(m.shape[2])) for m in masks]
+        bits = [torch.empty((n, h, _words(w)), dtype=torch.int32, device=dev) for h, w in hw]
+    else:
+        if hw is None or len(hw) != len(bits) or any(b.dtype != torch.int32 or tuple(b.shape) != (n, h, _words(w)) or b.device != dev or not b.is_contiguous() for b, (h, w) in zip(bits, hw)):
+            raise ValueError("w2comm_msg_index: contiguous int32 bits [n, H, ceil(W / 32)] per level and their (H, W)")
+        bits = list(bits)
+    if not w2comm_msg_index_shape_ok(n, hw):
+        raise ValueError("w2comm_msg_index: 1 .. 8 agents, 1 .. 3 levels")
+    levels = len(hw)
+    rank = [torch.empty_like(b) for b in bits]
+    count = torch.empty((n, levels), dtype=torch.int32, device=dev)
+    with _Timed("w2comm_msg_index"):
+        hip.check(hip.lib().coalign_w2comm_msg_index(n, levels, _i32_array([h for h, _ in hw]), _i32_array([w for _, w in hw]), None if masks is None else _ptr_array(masks),
+                                                     _ptr_array(bits), _ptr_array(rank), _ptr(count), _stream()), "coalign_w2comm_msg_index")
+    return bits, rank, count
+
+
+@_device_op
+def w2comm_msg_pack(xs: Sequence[torch.Tensor], bits: Sequence[torch.Tensor], rank: Sequence[torch.Tensor], rows: Optional[Sequence[torch.Tensor]] = None) -> list:
+    """Every set pixel's channel vector to its row, all agents and levels in one launch (``coalign_w2comm_msg_pack``): ``xs[l]`` [n, C_l, H_l, W_l] channels-last
+    float32, ``bits`` / ``rank`` as ``w2comm_msg_index`` gives them -> rows per level [n, max(1, H_l W_l), C_l] float32 (``rows``: buffers to write into; rows
+    behind an agent's count are not touched)."""
+    _need_gpu(*xs, *bits, *rank)
+    levels, n = len(xs), int(xs[0].shape[0])
+    if not 1 <= levels <= 3 or len(bits) != levels or len(rank) != levels or any(not warp_fuse_nhwc_ok(x) or x.shape[0] != n for x in xs):
+        raise ValueError("w2comm_msg_pack needs 1-3 channels-last float32 maps [n <= 8, C in {64, 128, 256}, H, W]")
+    for x, b, r in zip(xs, bits, rank):
+        want = (n, x.shape[2], _words(x.shape[3]))
+        if any(t.dtype != torch.int32 or tuple(t.shape) != want or not t.is_contiguous() or t.device != x.device for t in (b, r)):
+            raise ValueError("w2comm_msg_pack: contiguous int32 bits and rank [n, H, ceil(W / 32)] per level, on the map's device")
+    shapes = [(n, max(1, x.shape[2] * x.shape[3]), x.shape[1]) for x in xs]
+    if rows is None:
+        rows = [torch.empty(s, dtype=torch.float32, device=xs[0].device) for s in shapes]
+    elif len(rows) != levels or any(r.dtype != torch.float32 or tuple(r.shape) != s or not r.is_contiguous() or r.device != xs[0].device for r, s in zip(rows, shapes)):
+        raise ValueError("w2comm_msg_pack: rows [n, max(1, H W), C] float32 contiguous per level")
+    with _Timed("w2comm_msg_pack"):
+        hip.check(hip.lib().coalign_w2comm_msg_pack(n, levels, _ptr_array(xs), _i32_array([x.shape[1] for x in xs]), _i32_array([x.shape[2] for x in xs]),
+                                                    _i32_array([x.shape[3] for x in xs]), _ptr_array(bits), _ptr_array(rank), _ptr_array(rows), _stream()),
+                  "coalign_w2comm_msg_pack")
+    return list(rows)
+
+
+def _hwc_plane(t: torch.Tensor, C: int, H: int, W: int) -> bool:
+    """One agent's map in (H, W, C) memory: [C, H, W] or [1, C, H, W] of a channels-last tensor."""
+    if t.dim() == 4 and t.shape[0] == 1:
+        t = t[0]
+    return t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (C, H, W) and (t.permute(1, 2, 0).is_contiguous())
+
+
+@_device_op
+def w2comm_fuse_packed(sources: Sequence[Sequence[tuple]], shapes: Sequence[Tuple[int, int, int]], theta: torch.Tensor, mode: int) -> list:
+    """``w2comm_fuse_nhwc`` of ONE frame with a source per agent and scale (``coalign_w2comm_fuse_packed``).  ``shapes[i]`` = (C_i, H_i, W_i); ``sources[i][j]``
+    describes agent j at scale i: ``(x, mask)`` -- a dense plane, [C, H, W] or [1, C, H, W] in (H, W, C) memory, with its uint8 mask [H, W] or None (all ones) --
+    or ``(rows, bits, rank)`` -- a message's level: rows [>= 1, C] float32, bits and rank [H, ceil(W / 32)] int32.  theta [n, 2, 3] f64, mode FUSE_ATT / FUSE_MAX
+    -> per scale [1, C_i, H_i, W_i] channels-last."""
+    k = len(sources)
+    n = len(sources[0]) if k else 0
+    flat = [t for level in sources for s in level for t in s if t is not None]
+    _need_gpu(*flat, theta)
+    if not 1 <= k <= 3 or len(shapes) != k or not 1 <= n <= 8 or any(len(level) != n for level in sources) or any(int(C) not in (64, 128, 256) for C, _, _ in shapes):
+        raise ValueError("w2comm_fuse_packed needs 1-3 scales of C in {64, 128, 256} with one source per agent (1 .. 8) each")
+    if mode not in (FUSE_ATT, FUSE_MAX):
+        raise ValueError("w2comm_fuse_packed fuses (FUSE_ATT | FUSE_MAX)")
+    dev = flat[0].device
+    kind, src, aux, rank = [], [], [], []
+    for (C, H, W), level in zip(shapes, sources):
+        for s in level:
+            if len(s) == 2:
+                x, m = s
+                if not _hwc_plane(x, C, H, W) or (m is not None and (m.dtype != torch.uint8 or tuple(m.shape[-2:]) != (H, W) or m.numel() != H * W or not m.is_contiguous() or m.device != dev)):
+                    raise ValueError("w2comm_fuse_packed: a dense source is (a float32 plane in (H, W, C) memory, its contiguous uint8 mask [H, W] or None)")
+                kind.append(W2COMM_SRC_DENSE); src.append(x); aux.append(m); rank.append(None)
+            else:
+                r, b, rk = s
+                ok = r.dtype == torch.float32 and r.dim() == 2 and r.shape[0] >= max(1, H * W) and r.shape[1] == C and r.is_contiguous()
+                ok = ok and all(t.dtype == torch.int32 and tuple(t.shape) == (H, _words(W)) and t.is_contiguous() for t in (b, rk))
+                if not ok:
+                    raise ValueError("w2comm_fuse_packed: a packed source is (rows [max(1, H W), C] float32, bits [H, ceil(W / 32)] int32, rank likewise), contiguous")
+                kind.append(W2COMM_SRC_PACKED); src.append(r); aux.append(b); rank.append(rk)
+    th = theta.to(device=dev, dtype=torch.float64).contiguous()
+    if tuple(th.shape) != (n, 2, 3):
+        raise ValueError("one theta row per agent")
+    outs = [torch.empty((1, C, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last) for C, H, W in shapes]
+    with _Timed("w2comm_fuse_packed"):
+        hip.check(hip.lib().coalign_w2comm_fuse_packed(k, _i32_array([s[0] for s in shapes]), _i32_array([s[1] for s in shapes]), _i32_array([s[2] for s in shapes]),
+                                                       _i32_array(kind), _ptr_array(src), _ptr_array(aux), _ptr_array(rank), _ptr_array(outs),
+                                                       _i32_array([s[1] for s in shapes]), _i32_array([s[2] for s in shapes]), n, _ptr(th), mode, _stream()),
+                  "coalign_w2comm_fuse_packed")
+    return outs
