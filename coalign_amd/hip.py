@@ -205,6 +205,14 @@ W2COMM_MSG_SIGNATURES = {
 }
 MSG_HEADER = _build.MSG_HEADER
 
+# csrc/coalign_amd_v2x_ffn.h (build.FFN_HEADER): the thirteenth extension header of ABI version 2 (product library): V2X-ViT's feed-forward block -- LayerNorm, the
+# folded first linear, GELU, the second linear and the residual per token in one launch (csrc/v2x_ffn.hip)
+V2X_FFN_SIGNATURES = {
+    "coalign_v2x_ffn_param_bytes": (c_size_t, [c_int, c_int]),
+    "coalign_v2x_feed_forward": (c_int, [P, c_int, c_int, c_int, P, c_size_t, P, P]),
+}
+FFN_HEADER = _build.FFN_HEADER
+
 # header under include/ -> its table, in the order of the ABI's growth: what both loaders bind (coalign_amd_lab.h's LAB_SIGNATURES: the laboratory library alone)
 HEADERS = dict(zip(_build.ABI_HEADERS[:-1], (SIGNATURES, NARROW_SIGNATURES, NARROW_SPARSE_SIGNATURES, ALIGN_SIGNATURES, STAGE1_SIGNATURES, DISCO_SIGNATURES, V2V_SIGNATURES,
                                              V2X_SIGNATURES, V2X_WINDOW_SIGNATURES, W2C_SIGNATURES, V2VR_SIGNATURES, W2COMM_SIGNATURES)))
@@ -242,7 +250,7 @@ def lib() -> ctypes.CDLL:
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(
                 f"{path} is missing and could not be built ({exc}); the CoAlign hot path has no CPU fallback") from exc
-    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), W2COMM_MSG_SIGNATURES])
+    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), W2COMM_MSG_SIGNATURES, V2X_FFN_SIGNATURES])
     if handle.coalign_abi_version() != 2:
         raise CoalignHipError(f"ABI version mismatch: library reports {handle.coalign_abi_version()}, binding expects 2")
     _LIB = handle
@@ -262,7 +270,7 @@ def lab_lib() -> ctypes.CDLL:
             _build.build(lab=True)
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(f"{path} is missing and could not be built ({exc})") from exc
-    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), W2COMM_MSG_SIGNATURES, LAB_SIGNATURES])
+    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), W2COMM_MSG_SIGNATURES, V2X_FFN_SIGNATURES, LAB_SIGNATURES])
     _LAB_LIB = handle
     return handle
 

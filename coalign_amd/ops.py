@@ -1799,6 +1799,54 @@ def v2x_window_attention(x: torch.Tensor, params: torch.Tensor, fuse: str) -> to
     return out
 
 
+# ---- V2X-ViT's feed-forward block in one launch (csrc/coalign_amd_v2x_ffn.h, csrc/v2x_ffn.hip) --------------------------------------------------------------
+V2X_FFN_MAX_HIDDEN = 512      # COALIGN_V2X_FFN_MAX_HIDDEN
+
+
+def v2x_ffn_shape_ok(C: int, M: int) -> bool:
+    """The shapes ``coalign_v2x_feed_forward`` takes: C = 64 or 256 channels, a hidden width M % 32 == 0 with 32 <= M <= 512 (any number of tokens)."""
+    return C in (64, 256) and 32 <= M <= V2X_FFN_MAX_HIDDEN and M % 32 == 0
+
+
+def pack_v2x_ffn_weights(w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor) -> Optional[torch.Tensor]:
+    """The folded feed-forward layer (``v2xvit.folded_feed_forward``: w1 [M, C] = W1 diag(gamma), b1 [M] = W1 beta + b1, w2 [C, M], b2 [C]) -> the parameter image of
+    ``coalign_v2x_feed_forward`` (layout: the header's (16a)), a uint8 tensor on the weights' device.  None when a folded weight reaches the end of the fp16 range
+    (65504), or when a hidden pre-activation could: the hidden vector enters the second product as fp16 pairs, |GELU(z)| <= |z|, and with sum yhat^2 <= C
+    |w1 yhat + b1|_r <= ||w1_r||_2 sqrt(C) + |b1_r| for every token -- a static guarantee in place of a device flag."""
+    w1d, b1d, w2d = w1.detach().double(), b1.detach().double().reshape(-1), w2.detach().double()
+    M, C = w1d.shape
+    if tuple(w2d.shape) != (C, M) or b1d.numel() != M or b2.numel() != C or not v2x_ffn_shape_ok(C, M):
+        raise ValueError("pack_v2x_ffn_weights: w1 [M, C], b1 [M], w2 [C, M], b2 [C], C = 64 or 256, M % 32 == 0 in 32 .. 512")
+    if not bool(torch.isfinite(w1d).all() and torch.isfinite(w2d).all() and torch.isfinite(b1d).all()):
+        return None
+    bound = w1d.norm(dim=1) * float(C) ** 0.5 + b1d.abs()
+    if max(float(w1d.abs().max()), float(w2d.abs().max()), float(bound.max())) >= 65504.0:
+        return None
+    floats = torch.cat([b1.detach().float().reshape(-1), b2.detach().float().reshape(-1)])
+    img = torch.cat([_disco_operand_image(w1.detach().float()), _disco_operand_image(w2.detach().float()), floats.contiguous().view(torch.uint8)])
+    assert img.numel() == 2 * (C // 16) * (M // 32) * 2048 + 4 * (M + C)
+    return img.contiguous()
+
+
+@_device_op
+def v2x_feed_forward(x: torch.Tensor, params: torch.Tensor) -> torch.Tensor:
+    """x + FeedForward(LayerNorm(x)) per token in one launch (``coalign_v2x_feed_forward``): x [..., C] float32 contiguous (any channels-last map), params from
+    ``pack_v2x_ffn_weights`` (its size names the hidden width) -> a new tensor of x's shape."""
+    _need_gpu(x, params)
+    L = hip.lib()
+    if x.dim() < 1 or x.dtype != torch.float32 or not x.is_contiguous() or params.dtype != torch.uint8 or not params.is_contiguous():
+        raise ValueError("v2x_feed_forward needs contiguous float32 token rows [..., C] and the uint8 image of pack_v2x_ffn_weights")
+    C = x.shape[-1]
+    M = (params.numel() - 4 * C) // (8 * C + 4) if C in (64, 256) else 0      # bytes = 2 (C / 16) (M / 32) 2048 + 4 (M + C) = M (8 C + 4) + 4 C
+    if not v2x_ffn_shape_ok(C, M) or int(L.coalign_v2x_ffn_param_bytes(C, M)) != params.numel():
+        raise ValueError("v2x_feed_forward: C = 64 or 256 and an image of pack_v2x_ffn_weights for that C")
+    tokens = x.numel() // C
+    out = torch.empty_like(x)
+    with _Timed("v2x_feed_forward"):
+        hip.check(L.coalign_v2x_feed_forward(_ptr(x), tokens, C, M, _ptr(params), params.numel(), _ptr(out), _stream()), "coalign_v2x_feed_forward")
+    return out
+
+
 # ---- When2com's handshake fusion after its convolutions (include/coalign_amd_w2c.h, csrc/w2c_fuse.hip) ---------------------------------------------------
 W2C_CHANNELS, W2C_FEAT, W2C_HIDDEN1, W2C_HIDDEN2, W2C_ATT = 128, 4480, 256, 128, 128      # COALIGN_W2C_*
 W2C_PARAM_FLOATS = 2 * W2C_HIDDEN1 * W2C_FEAT + 2 * W2C_HIDDEN1 + 2 * (W2C_HIDDEN1 * W2C_HIDDEN2 + W2C_HIDDEN2) + 2 * (W2C_HIDDEN2 * W2C_ATT + W2C_ATT)

@@ -33,6 +33,7 @@ from .detector import BASELINE_REGISTRY, MODEL_REGISTRY, build_model
 # the families' own wording, importable from here
 DISCO, V2V = fusion.DiscoFusion.KERNELS, fusion.V2VNetFusion.KERNELS
 V2X, V2X_WINDOW = fusion.V2XViTFusion.KERNELS, fusion.V2XViTFusion.KERNELS_WINDOW
+V2X_FFN, V2X_WINDOW_FFN = fusion.V2XViTFusion.KERNELS_FFN, fusion.V2XViTFusion.KERNELS_WINDOW_FFN
 W2C, W2C_TORCH, W2C_SCORE, W2C_UNREAD = fusion.When2comFusion.KERNELS, fusion.When2comFusion.TORCH, fusion.When2comFusion.SCORE, fusion.When2comFusion.UNREAD
 V2VR, V2VR_TORCH = v2v_robust.KERNELS, v2v_robust.TORCH
 W2COMM, W2COMM_MASKS = fusion.Where2commFusion.KERNELS, fusion.Where2commFusion.MASKS

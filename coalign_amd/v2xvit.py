@@ -16,7 +16,9 @@ What fusion_in_one.py fixes for every call, and what follows from it:
 
 On the GPU in eval mode (``kernel_route``) the agent attention of every layer runs on ``ops.v2x_agent_attention``; the pyramid window attention, split attention
 and feed-forward stay torch ops on the device (library kernels) -- unless ``window_kernels`` is set (off by default), which puts the pyramid window attention with
-its split attention on ``ops.v2x_window_attention`` where ``window_kernel_reason`` allows it.
+its split attention on ``ops.v2x_window_attention`` where ``window_kernel_reason`` allows it, and unless ``ffn_kernels`` is set (off by default too, independent of
+the first), which puts ``x + FeedForward(LayerNorm(x))`` on ``ops.v2x_feed_forward`` where ``ffn_kernel_reason`` allows it.  With both set an encoder layer of the
+kernel route is hand-written from end to end.
 """
 from __future__ import annotations
 
@@ -35,6 +37,9 @@ from .encoder import host_ints
 # Measurement switch: the pyramid window attention and split attention of the kernel route on ``ops.v2x_window_attention`` (csrc/v2x_window.hip) instead of torch
 # ops.  Off by default; copied into ``V2XViTFusion.window_kernels`` at construction (tests and tools set the attribute).
 V2X_WINDOW_KERNELS = os.environ.get("COALIGN_V2X_WINDOW", "0") != "0"
+# Measurement switch: the feed-forward block of the kernel route on ``ops.v2x_feed_forward`` (csrc/v2x_ffn.hip) instead of torch ops.  Off by default; copied into
+# ``V2XViTFusion.ffn_kernels`` at construction (tests and tools set the attribute).  Independent of the window switch.
+V2X_FFN_KERNELS = os.environ.get("COALIGN_V2X_FFN", "0") != "0"
 
 
 def _warp_torch(src: torch.Tensor, M: torch.Tensor) -> torch.Tensor:
@@ -218,6 +223,24 @@ def window_attention_reduced(x: torch.Tensor, norm: nn.LayerNorm, pw: "PyramidWi
         gap = sum(F.linear(o.mean(dim=(1, 2)), wout[b], bout[b]) for b, o in enumerate(outs))      # [n, C]
         a = sa.fc2(sa.act1(sa.bn1(sa.fc1(gap)))).reshape(n, B, -1).softmax(dim=1)
     return x + sum(a[:, b, None, None, :] * F.linear(o, wout[b], bout[b]) for b, o in enumerate(outs))
+
+
+def folded_feed_forward(norm: nn.LayerNorm, ff: "FeedForward"):
+    """One PreNorm(FeedForward) layer with LayerNorm folded into the first linear: -> (W1' [M, C], b1' [M], W2 [C, M], b2 [C]) in float64 with
+        ff(LayerNorm(x)) = W2 GELU(W1' yhat + b1') + b2,   yhat = (x - mean) / sqrt(var + eps).
+    Exact identities: gamma into the columns (W1' = W1 diag(gamma)), beta into the bias (b1' = W1 beta + b1)."""
+    d = torch.float64
+    w1, b1 = ff.net[0].weight.detach().to(d), ff.net[0].bias.detach().to(d)
+    return ((w1 * norm.weight.detach().to(d)[None, :]).contiguous(), (w1 @ norm.bias.detach().to(d) + b1).contiguous(),
+            ff.net[3].weight.detach().to(d).contiguous(), ff.net[3].bias.detach().to(d).contiguous())
+
+
+def feed_forward_reduced(x: torch.Tensor, norm: nn.LayerNorm, ff: "FeedForward") -> torch.Tensor:
+    """x [..., C] -> x + FeedForward(LayerNorm(x)) on the folded first linear: the arithmetic of ``ops.v2x_feed_forward`` in torch ops (eval mode: no dropout; any
+    dtype, any device)."""
+    w1, b1, w2, b2 = (t.to(x.dtype) for t in _cache_of(ff, "_coalign_v2x_ffn_fold").get(list(norm.parameters()) + list(ff.parameters()), lambda: folded_feed_forward(norm, ff)))
+    yhat = F.layer_norm(x, (x.shape[-1],), None, None, norm.eps)
+    return x + F.linear(F.gelu(F.linear(yhat, w1, b1)), w2, b2)
 
 
 def get_relative_distances(window_size: int) -> torch.Tensor:
@@ -514,6 +537,7 @@ class V2XViTFusion(nn.Module):
         self.fusion_net = V2XTransformer(args["transformer"])
         self.force_torch = False      # measurement / test aid: take the op-by-op route whatever the device
         self.window_kernels = V2X_WINDOW_KERNELS      # the kernel route's window attention on ops.v2x_window_attention (off by default)
+        self.ffn_kernels = V2X_FFN_KERNELS            # the kernel route's feed-forward on ops.v2x_feed_forward (off by default)
 
     # ---- the decision --------------------------------------------------------------------------------------------------------------------------------------
     def _attentions(self):
@@ -551,6 +575,22 @@ class V2XViTFusion(nn.Module):
             return f"a {int(hw[0])} x {int(hw[1])} map: H and W must be multiples of 16"
         return None
 
+    def _feed_forwards(self):
+        return [layer[1] for layer in self.fusion_net.encoder.layers]
+
+    def ffn_kernel_reason(self, channels: int) -> Optional[str]:
+        """None when ``ops.v2x_feed_forward`` takes every feed-forward block of the kernel route at ``channels``; else why not."""
+        if not self.ffn_kernels:
+            return "the feed-forward kernel is switched off (COALIGN_V2X_FFN / ffn_kernels)"
+        for ff in self._feed_forwards():
+            lin1, lin2 = ff.fn.net[0], ff.fn.net[3]
+            if lin1.in_features != channels or lin2.out_features != channels or not ops.v2x_ffn_shape_ok(channels, lin1.out_features):
+                return (f"feed-forward {lin1.in_features} -> {lin1.out_features} -> {lin2.out_features} on {channels} channels outside the kernel's 64 | 256 channels "
+                        f"with mlp_dim a multiple of 32 in 32 .. {ops.V2X_FFN_MAX_HIDDEN}")
+        if self.packed_ffn() is None:
+            return "a folded feed-forward weight, or the static bound of a hidden pre-activation, lies outside the fp16 range"
+        return None
+
     def kernel_route(self, channels: int, n_agents: int = 1, hw=None) -> bool:
         """The static half of the decision (``routes.plan`` asks it): eval mode, hetero attention of 8 or 2 heads of 32 on ``channels``, at most 8 agents, and -- when
         the map's shape ``hw`` is given -- an ROI mask that is all ones there.  ``forward`` adds: a CUDA float32 map, packable weights."""
@@ -564,13 +604,22 @@ class V2XViTFusion(nn.Module):
     KERNELS_WINDOW = ("v2x_agent_attention + v2x_window_attention per encoder layer: the agent attention in two launches, the pyramid window attention with its split attention "
                       "(LayerNorm + folded 9C x C projection, attention inside the 4 / 8 / 16 windows, branch weights, output projections + residual) in three or four; "
                       "the feed-forward is still torch ops on the device (library kernels)")
+    KERNELS_FFN = ("v2x_agent_attention + v2x_feed_forward per encoder layer: the agent attention in two launches, the feed-forward (LayerNorm + folded first linear, GELU, "
+                   "second linear + residual) in one; pyramid window attention and split attention as torch ops on the device (library kernels)")
+    KERNELS_WINDOW_FFN = ("v2x_agent_attention + v2x_window_attention + v2x_feed_forward per encoder layer: the agent attention in two launches, the pyramid window attention with "
+                          "its split attention (LayerNorm + folded 9C x C projection, attention inside the 4 / 8 / 16 windows, branch weights, output projections + residual) in "
+                          "three or four, the feed-forward (LayerNorm + folded first linear, GELU, second linear + residual) in one")
     TORCH = "V2XViTFusion op by op in PyTorch"
+    FFN = "v2x_feed_forward"
     ATT, WIN, UNREAD = "v2x_agent_attention", "v2x_window_attention", "never read (every agent is of type 0; prior_feed has no caller)"
 
     def plan_fusion(self, channels: int, terms: Optional[int] = None):
         """-> (``routes.plan``'s fusion line, whether it is a fallback, {layers noted with it: (line, fallback)})."""
         if self.kernel_route(channels):
-            return (self.KERNELS_WINDOW if self.window_kernel_reason(channels) is None else self.KERNELS), False, {}
+            window = self.window_kernel_reason(channels) is None
+            if self.ffn_kernel_reason(channels) is None:
+                return (self.KERNELS_WINDOW_FFN if window else self.KERNELS_FFN), False, {}
+            return (self.KERNELS_WINDOW if window else self.KERNELS), False, {}
         return f"{self.TORCH} ({self.kernel_shape_reason(channels) or TORCH_MODE})", True, {}
 
     def plan_layer(self, name: str, layer: nn.Module, channels: int, terms: Optional[int] = None):
@@ -588,6 +637,9 @@ class V2XViTFusion(nn.Module):
             part = ("one third of the folded 9C x C projection, fp16 x 2 on the matrix cores" if leaf[-1] == "to_qkv" else "output projection, fp16 x 2 on the matrix cores"
                     if ".to_out." in name else "split attention's branch weights, fp32")
             return f"{self.WIN} ({part})", False
+        if ok and ".net." in name and self.ffn_kernel_reason(channels) is None:
+            part = "first linear with LayerNorm folded in, GELU" if leaf[-1] == "0" else "second linear + residual"
+            return f"{self.FFN} ({part}, fp16 x 2 on the matrix cores)", False
         block = "pyramid window attention" if ".pwmsa." in name else "split attention" if ".split_attn." in name else "feed-forward" if ".net." in name else "agent attention" if ".to_" in name else "time encoding"
         return LINEAR_LIBRARY + f", {block}: torch op on the device)", True
 
@@ -657,6 +709,14 @@ class V2XViTFusion(nn.Module):
             return (None if any(i is None for i in imgs) else imgs,)
         return _cache_of(self, "_coalign_v2x_window_images").get(self, build)[0]
 
+    def packed_ffn(self) -> Optional[List[torch.Tensor]]:
+        """The parameter image of every feed-forward block (``ops.pack_v2x_ffn_weights`` of ``folded_feed_forward``), one per encoder layer, cached until a parameter
+        changes; None when a folded weight or the static bound of a hidden pre-activation lies outside the fp16 range."""
+        def build():
+            imgs = [ops.pack_v2x_ffn_weights(*folded_feed_forward(ff.norm, ff.fn)) for ff in self._feed_forwards()]
+            return (None if any(i is None for i in imgs) else imgs,)
+        return _cache_of(self, "_coalign_v2x_ffn_images").get([p for ff in self._feed_forwards() for p in ff.parameters()], build)[0]
+
     def forward_kernels(self, xx: torch.Tensor, groups: Sequence[int], normalized_affine_matrix: torch.Tensor, images: List[torch.Tensor]) -> torch.Tensor:
         enc = self.fusion_net.encoder
         _, C, H, W = xx.shape
@@ -666,6 +726,7 @@ class V2XViTFusion(nn.Module):
             if not ops.nhwc_memory(xx):
                 xx = xx.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
         wimages = self.packed_windows() if self.window_kernel_reason(C, (H, W)) is None else None      # (one decision per call)
+        fimages = {id(ff): img for ff, img in zip(self._feed_forwards(), self.packed_ffn())} if self.ffn_kernel_reason(C) is None else None
         outs, off = [], 0
         for b, n in enumerate(groups):
             xb = xx[off:off + n]
@@ -686,7 +747,7 @@ class V2XViTFusion(nn.Module):
                 else:
                     xb = xb + pw(xb.unsqueeze(0)).squeeze(0)
                 if ff is not None:
-                    xb = xb + ff(xb)
+                    xb = ops.v2x_feed_forward(xb.contiguous(), fimages[id(ff)]) if fimages is not None else xb + ff(xb)
             outs.append(xb[:1])
         out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
         return out.permute(0, 3, 1, 2)                                        # [B, C, H, W] in channels-last memory
