@@ -5,6 +5,7 @@ Host-side mirror of the reference's yaml loader so that *unchanged* opencood
 
 * ``load_yaml``                 <- opencood/hypes_yaml/yaml_utils.py:14-49
 * ``load_point_pillar_params``  <- opencood/hypes_yaml/yaml_utils.py:97-137
+* ``load_lift_splat_shoot_params`` <- opencood/hypes_yaml/yaml_utils.py:295-334
 
 Differences on purpose: the per-family post-parser named by the yaml's
 ``yaml_parser`` key is looked up in a table instead of being ``eval``-ed, and
@@ -64,8 +65,23 @@ def load_point_pillar_params(param: dict) -> dict:
     return param
 
 
+def load_lift_splat_shoot_params(param: dict) -> dict:
+    """The camera model's parser (yaml_utils.py:295-334): ``anchor_args`` gains ``vw, vh, vd`` and ``W, H, D = ceil(extent / voxel)`` from the range and voxel
+    size of ``preprocess``; the model's own grid is ``model.args.grid_conf`` and needs nothing derived."""
+    rng = param["preprocess"]["cav_lidar_range"]
+    vox = param["preprocess"]["args"]["voxel_size"]
+    anchor = param["postprocess"]["anchor_args"]
+    anchor["vw"], anchor["vh"], anchor["vd"] = vox[0], vox[1], vox[2]
+    anchor["W"] = math.ceil((rng[3] - rng[0]) / vox[0])
+    anchor["H"] = math.ceil((rng[4] - rng[1]) / vox[1])
+    anchor["D"] = math.ceil((rng[5] - rng[2]) / vox[2])
+    param["postprocess"]["anchor_args"] = anchor
+    return param
+
+
 YAML_PARSERS: Dict[str, Callable[[dict], dict]] = {
     "load_point_pillar_params": load_point_pillar_params,
+    "load_lift_splat_shoot_params": load_lift_splat_shoot_params,
 }
 
 

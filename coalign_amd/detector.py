@@ -21,6 +21,7 @@ from . import backbone as _bb
 from . import ops
 from .backbone import BaseBEVBackbone, BasicBlock, DownsampleConv, NaiveCompressor, ResNetBEVBackbone, _cache_of, _fast_ok
 from .encoder import PillarVFE, PointPillarScatter, host_ints
+from .lss import LiftSplatShootIntermediate
 from .fusion import AttFusion, DiscoFusion, MaxFusion, V2VNetFusion, V2XViTFusion, When2comFusion, Where2commFusion, fuse_multiscale
 from . import v2v_robust
 from .pose import generate_noise_torch, get_pairwise_transformation_torch, normalize_pairwise_tfm
@@ -763,12 +764,17 @@ BASELINE_REGISTRY = {
     "point_pillar_where2comm": PointPillarWhere2comm,
 }
 
+# The camera model (coalign_amd.lss): Lift-Splat frustum pooling in front of the multi-scale BEV fusion.  It has no pillar trunk, so ``routes.plan`` does not walk it.
+CAMERA_REGISTRY = {
+    "lift_splat_shoot_intermediate": LiftSplatShootIntermediate,
+}
+
 
 def build_model(hypes: dict) -> nn.Module:
     """``train_utils.create_model`` for the hot-path model families and the comparison baselines (opencood/tools/train_utils.py:113-146):
     ``hypes['model']['core_method']`` names the model, ``hypes['model']['args']`` is its constructor argument."""
     name = hypes["model"]["core_method"]
-    families = {**MODEL_REGISTRY, **BASELINE_REGISTRY}
+    families = {**MODEL_REGISTRY, **BASELINE_REGISTRY, **CAMERA_REGISTRY}
     if name not in families:
         raise KeyError(f"model '{name}' is outside the CoAlign hot path and its baselines (available: {sorted(families)})")
     return families[name](hypes["model"]["args"])

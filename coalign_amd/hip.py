@@ -213,6 +213,16 @@ V2X_FFN_SIGNATURES = {
 }
 FFN_HEADER = _build.FFN_HEADER
 
+# csrc/coalign_amd_lss.h (build.LSS_HEADER): the fourteenth extension header of ABI version 2 (product library): Lift-Splat's frustum pooling -- the voxel of every
+# frustum point once per camera rig, then per frame the depth softmax and the sum of probability x feature row per BEV cell through an inverted index, in two
+# launches (csrc/lss_pool.hip)
+LSS_SIGNATURES = {
+    "coalign_lss_cells": (c_int, [P, P, P, P, P, c_int, c_int, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_int, c_int, c_int, P, P]),
+    "coalign_lss_depth_prob": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "coalign_lss_pool": (c_int, [P, P, c_int, c_int, c_int, P, c_int, P, c_int, P, c_int, P, P]),
+}
+LSS_HEADER = _build.LSS_HEADER
+
 # header under include/ -> its table, in the order of the ABI's growth: what both loaders bind (coalign_amd_lab.h's LAB_SIGNATURES: the laboratory library alone)
 HEADERS = dict(zip(_build.ABI_HEADERS[:-1], (SIGNATURES, NARROW_SIGNATURES, NARROW_SPARSE_SIGNATURES, ALIGN_SIGNATURES, STAGE1_SIGNATURES, DISCO_SIGNATURES, V2V_SIGNATURES,
                                              V2X_SIGNATURES, V2X_WINDOW_SIGNATURES, W2C_SIGNATURES, V2VR_SIGNATURES, W2COMM_SIGNATURES)))
@@ -250,7 +260,7 @@ def lib() -> ctypes.CDLL:
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(
                 f"{path} is missing and could not be built ({exc}); the CoAlign hot path has no CPU fallback") from exc
-    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), W2COMM_MSG_SIGNATURES, V2X_FFN_SIGNATURES])
+    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), W2COMM_MSG_SIGNATURES, V2X_FFN_SIGNATURES, LSS_SIGNATURES])
     if handle.coalign_abi_version() != 2:
         raise CoalignHipError(f"ABI version mismatch: library reports {handle.coalign_abi_version()}, binding expects 2")
     _LIB = handle
@@ -270,7 +280,7 @@ def lab_lib() -> ctypes.CDLL:
             _build.build(lab=True)
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(f"{path} is missing and could not be built ({exc})") from exc
-    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), W2COMM_MSG_SIGNATURES, V2X_FFN_SIGNATURES, LAB_SIGNATURES])
+    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), W2COMM_MSG_SIGNATURES, V2X_FFN_SIGNATURES, LSS_SIGNATURES, LAB_SIGNATURES])
     _LAB_LIB = handle
     return handle
 

@@ -2245,3 +2245,130 @@ def w2comm_fuse_packed(sources: Sequence[Sequence[tuple]], shapes: Sequence[Tupl
                                                        _i32_array([s[1] for s in shapes]), _i32_array([s[2] for s in shapes]), n, _ptr(th), mode, _stream()),
                   "coalign_w2comm_fuse_packed")
     return outs
+
+
+# ---- Lift-Splat's frustum pooling for the camera model (csrc/coalign_amd_lss.h, csrc/lss_pool.hip) --------------------------------------------------------------
+LSS_CHUNK = 512               # COALIGN_LSS_CHUNK
+LSS_MAX_DEPTH = 128           # COALIGN_LSS_MAX_DEPTH
+
+
+def lss_shape_ok(C: int, D: int) -> bool:
+    """The shapes ``coalign_lss_pool`` takes: C = 64 or 128 feature channels, 1 <= D <= 128 depth bins (any number of agents, cameras, pixels and cells)."""
+    return C in (64, 128) and 1 <= D <= LSS_MAX_DEPTH
+
+
+class LiftSplatIndex:
+    """The inverted index of one camera rig (the header's description): per output cell -- key ((a ny + y) nx + x) nz + z -- the list of its frustum points in
+    ascending point order.  ``starts`` [cells + 1], ``points`` [n_points, 2] = (feature row, probability index), ``long_cells`` (lists longer than ``LSS_CHUNK``),
+    all int32; ``order`` [n_points] int64, the flat point numbers in list order (what ``points`` was made of; the tests read it).  ``dims`` = (A, N, D, fH, fW,
+    nx, ny, nz)."""
+
+    def __init__(self, starts, points, long_cells, order, dims):
+        self.starts, self.points, self.long_cells, self.order, self.dims = starts, points, long_cells, order, tuple(int(v) for v in dims)
+
+    @property
+    def cells(self) -> int:
+        A, _, _, _, _, nx, ny, nz = self.dims
+        return A * nx * ny * nz
+
+    @property
+    def n_points(self) -> int:
+        return int(self.points.shape[0])
+
+    def chunks(self):
+        """[(key, begin, end)] of the pieces ``coalign_lss_pool`` sums on their own, in the order it adds them: a list of at most ``LSS_CHUNK`` points is one piece,
+        a longer one is cut every ``LSS_CHUNK`` points (host lists; the tests' view of the split rule)."""
+        s = self.starts.tolist()
+        out = []
+        for k in range(len(s) - 1):
+            for b in range(s[k], s[k + 1], LSS_CHUNK):
+                out.append((k, b, min(s[k + 1], b + LSS_CHUNK)))
+        return out
+
+
+def build_lss_index(cell: torch.Tensor, A: int, N: int, nx: int, ny: int, nz: int) -> LiftSplatIndex:
+    """``cell`` [A N, D, fH, fW] int32 (``lss_cells``: (z ny + y) nx + x, or -1) -> the index, with torch ops on ``cell``'s device (CPU or GPU): a STABLE sort of the
+    kept points' keys keeps every list in ascending point order, ``bincount`` / ``cumsum`` give the list starts.  Once per rig, off the frame path; it synchronises."""
+    M, D, fH, fW = (int(v) for v in cell.shape)
+    if M != A * N:
+        raise ValueError("build_lss_index: cell must be [A N, D, fH, fW]")
+    cells = A * nx * ny * nz
+    if cell.numel() >= 2 ** 31 or cells >= 2 ** 31 or M * fH * fW * D >= 2 ** 31:
+        raise ValueError("build_lss_index: outside int32 indexing")
+    flat = cell.reshape(-1).long()
+    pid = torch.arange(flat.numel(), device=cell.device)
+    kept = flat >= 0
+    flat, pid = flat[kept], pid[kept]
+    agent = pid // (N * D * fH * fW)
+    x, y, z = flat % nx, (flat // nx) % ny, flat // (nx * ny)
+    key = ((agent * ny + y) * nx + x) * nz + z
+    key, perm = torch.sort(key, stable=True)
+    order = pid[perm]
+    counts = torch.bincount(key, minlength=cells)
+    starts = torch.zeros(cells + 1, dtype=torch.int64, device=cell.device)
+    starts[1:] = torch.cumsum(counts, 0)
+    m, rem = order // (D * fH * fW), order % (D * fH * fW)
+    row = m * (fH * fW) + rem % (fH * fW)
+    points = torch.stack([row, row * D + rem // (fH * fW)], dim=1).to(torch.int32).contiguous()
+    long_cells = torch.nonzero(counts > LSS_CHUNK).reshape(-1).to(torch.int32).contiguous()
+    return LiftSplatIndex(starts.to(torch.int32).contiguous(), points, long_cells, order, (A, N, D, fH, fW, nx, ny, nz))
+
+
+@_device_op
+def lss_cells(rots: torch.Tensor, trans: torch.Tensor, intrins: torch.Tensor, post_rots: torch.Tensor, post_trans: torch.Tensor, xs: torch.Tensor,
+              ys: torch.Tensor, ds: torch.Tensor, lower: Sequence[float], dx: Sequence[float], n: Sequence[int], cams_per_agent: int) -> torch.Tensor:
+    """The voxel of every frustum point (``coalign_lss_cells``): camera tensors [A N, 3, 3] / [A N, 3] (or the reference's [A, N, ...]) float32, the frustum's axes
+    xs [fW], ys [fH], ds [D] float32, ``lower`` = bx - dx / 2 and ``dx`` as float32 values per axis, ``n`` = (nx, ny, nz) -> int32 [A N, D, fH, fW]."""
+    _need_gpu(rots, trans, intrins, post_rots, post_trans, xs, ys, ds)
+    r, k, pr = (_f32c(t.reshape(-1, 3, 3)) for t in (rots, intrins, post_rots))
+    t, pt = (_f32c(v.reshape(-1, 3)) for v in (trans, post_trans))
+    M, N = int(r.shape[0]), int(cams_per_agent)
+    if N < 1 or M < 1 or M % N or any(int(v.shape[0]) != M for v in (k, pr, t, pt)):
+        raise ValueError("lss_cells: five camera tensors of A N cameras each")
+    xs, ys, ds = (_f32c(v.reshape(-1)).to(r.device) for v in (xs, ys, ds))
+    D, fH, fW = int(ds.numel()), int(ys.numel()), int(xs.numel())
+    cell = torch.empty((M, D, fH, fW), dtype=torch.int32, device=r.device)
+    hip.check(hip.lib().coalign_lss_cells(_ptr(r), _ptr(t), _ptr(k), _ptr(pr), _ptr(pt), M // N, N, _ptr(xs), _ptr(ys), _ptr(ds), D, fH, fW, float(lower[0]), float(lower[1]),
+                                          float(lower[2]), float(dx[0]), float(dx[1]), float(dx[2]), int(n[0]), int(n[1]), int(n[2]), _ptr(cell), _stream()), "coalign_lss_cells")
+    return cell
+
+
+@_device_op
+def lss_depth_prob(depth_logit: torch.Tensor) -> torch.Tensor:
+    """softmax over the depth bins (``coalign_lss_depth_prob``): [M, D, fH, fW] float32, plain or channels-last memory, read in place -> [M fH fW, D]."""
+    _need_gpu(depth_logit)
+    if depth_logit.dim() != 4 or depth_logit.dtype != torch.float32:
+        raise ValueError("lss_depth_prob needs float32 logits [M, D, fH, fW]")
+    M, D, fH, fW = (int(v) for v in depth_logit.shape)
+    nhwc = depth_logit.permute(0, 2, 3, 1).is_contiguous()
+    x = depth_logit if nhwc or depth_logit.is_contiguous() else depth_logit.contiguous()
+    prob = torch.empty((M * fH * fW, D), dtype=torch.float32, device=x.device)
+    with _Timed("lss_depth_prob"):
+        hip.check(hip.lib().coalign_lss_depth_prob(_ptr(x), M, D, fH, fW, int(nhwc and not x.is_contiguous()), _ptr(prob), _stream()), "coalign_lss_depth_prob")
+    return prob
+
+
+@_device_op
+def lss_pool(depth_logit: torch.Tensor, x_img: torch.Tensor, index: LiftSplatIndex, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The frame path of the frustum pooling, two launches (``coalign_lss_depth_prob``, ``coalign_lss_pool``): depth_logit [A N, D, fH, fW], x_img [A N, C, fH, fW]
+    float32 -> the BEV map [A, nz C, ny, nx] (channel z C + c) in channels-last memory, every element written.  ``x_img`` is read in place when it is channels-last
+    (a point's C values are one row); a plain NCHW map is brought into that layout by torch first.  ``out``: a channels-last buffer to write into."""
+    _need_gpu(depth_logit, x_img, index.points)
+    A, N, D, fH, fW, nx, ny, nz = index.dims
+    if x_img.dim() != 4 or x_img.dtype != torch.float32 or tuple(depth_logit.shape) != (A * N, D, fH, fW) or (x_img.shape[0], x_img.shape[2], x_img.shape[3]) != (A * N, fH, fW):
+        raise ValueError("lss_pool: depth_logit [A N, D, fH, fW] and x_img [A N, C, fH, fW] float32 of the index's camera rig")
+    C = int(x_img.shape[1])
+    if not lss_shape_ok(C, D):
+        raise hip.CoalignHipError("lss_pool: C in {64, 128} and 1 <= D <= 128")
+    rows = x_img.permute(0, 2, 3, 1)
+    if not rows.is_contiguous():
+        rows = rows.contiguous()
+    prob = lss_depth_prob(depth_logit)
+    if out is None:
+        out = torch.empty((A, ny, nx, nz * C), dtype=torch.float32, device=rows.device).permute(0, 3, 1, 2)
+    elif tuple(out.shape) != (A, nz * C, ny, nx) or out.dtype != torch.float32 or not out.permute(0, 2, 3, 1).is_contiguous():
+        raise ValueError("lss_pool: out must be a channels-last float32 map [A, nz C, ny, nx]")
+    with _Timed("lss_pool"):
+        hip.check(hip.lib().coalign_lss_pool(_ptr(rows), _ptr(prob), A * N * fH * fW, C, D, _ptr(index.points), index.n_points, _ptr(index.starts), index.cells,
+                                             _ptr(index.long_cells), int(index.long_cells.numel()), _ptr(out), _stream()), "coalign_lss_pool")
+    return out

@@ -486,3 +486,46 @@ def v2v_robust_parameters_(model: torch.nn.Module, seed: int = 0, input_scale: f
                 else:
                     v = torch.randn(shape, generator=g) * (1.5 / fan_in) ** 0.5
                 t.copy_(v.to(t.dtype))
+
+
+def make_camera_rig(n_agents: int, n_cams: int, final_dim: Sequence[int], seed: int = 5, resize_lim=(0.80, 0.85)) -> Dict:
+    """An OPV2V-like camera rig for the Lift-Splat model: per agent ``n_cams`` cameras turned by 90 degree steps plus a seeded offset of up to +-10 degrees
+    (and +-2 degrees of pitch), mounted within half a metre of the agent's origin at 1.2 .. 1.8 m height; focal length about half the ORIGINAL image width
+    (final width / resize), principal point near the image centre; ``post_rots`` the augmentation's resize (a scale of 0.80 .. 0.85), ``post_trans`` a crop of a few
+    pixels.  Camera axes: z forward, x right, y down; ego axes: x forward, y left, z up.  -> float32 tensors ``rots, intrins, post_rots`` [A, N, 3, 3] and
+    ``trans, post_trans`` [A, N, 3], the keys of the reference's ``image_inputs``."""
+    rng = np.random.RandomState(seed)
+    fH, fW = int(final_dim[0]), int(final_dim[1])
+    base = np.array([[0.0, 0.0, 1.0], [-1.0, 0.0, 0.0], [0.0, -1.0, 0.0]])
+    out = {k: np.zeros((n_agents, n_cams, 3, 3), np.float32) for k in ("rots", "intrins", "post_rots")}
+    out.update({k: np.zeros((n_agents, n_cams, 3), np.float32) for k in ("trans", "post_trans")})
+    for a in range(n_agents):
+        for n in range(n_cams):
+            yaw = np.deg2rad(90.0 * n + rng.uniform(-10.0, 10.0))
+            pitch = np.deg2rad(rng.uniform(-2.0, 2.0))
+            rz = np.array([[np.cos(yaw), -np.sin(yaw), 0.0], [np.sin(yaw), np.cos(yaw), 0.0], [0.0, 0.0, 1.0]])
+            ry = np.array([[np.cos(pitch), 0.0, np.sin(pitch)], [0.0, 1.0, 0.0], [-np.sin(pitch), 0.0, np.cos(pitch)]])
+            s = rng.uniform(*resize_lim)
+            W0, H0 = fW / s, fH / s
+            f = 0.5 * W0 * rng.uniform(0.97, 1.03)
+            out["rots"][a, n] = rz @ ry @ base
+            out["trans"][a, n] = [rng.uniform(-0.5, 0.5), rng.uniform(-0.5, 0.5), rng.uniform(1.2, 1.8)]
+            out["intrins"][a, n] = [[f, 0.0, 0.5 * W0 + rng.uniform(-2.0, 2.0)], [0.0, f, 0.5 * H0 + rng.uniform(-2.0, 2.0)], [0.0, 0.0, 1.0]]
+            out["post_rots"][a, n] = np.diag([s, s, 1.0])
+            out["post_trans"][a, n] = [-rng.uniform(0.0, 3.0), -rng.uniform(0.0, 3.0), 0.0]
+    return {k: torch.from_numpy(v) for k, v in out.items()}
+
+
+def make_camera_frame(hypes: dict, n_agents: int, seed: int = 5, trunk_channels: int = 512) -> Dict:
+    """Batch dict for ``LiftSplatShootIntermediate.forward`` without an image trunk: ``image_inputs`` (``make_camera_rig`` plus seeded ``trunk_features``
+    [A N, 512, fH, fW]), ``record_len`` [1] and ``pairwise_t_matrix`` [1, L, L, 4, 4] float64 of seeded poses a few metres apart."""
+    margs = hypes["model"]["args"]
+    conf = margs["data_aug_conf"]
+    N, down = int(conf["Ncams"]), int(margs["img_downsample"])
+    rig = make_camera_rig(n_agents, N, conf["final_dim"], seed=seed, resize_lim=tuple(conf.get("resize_lim", (0.8, 0.85))))
+    g = torch.Generator().manual_seed(seed)
+    rig["trunk_features"] = torch.randn(n_agents * N, trunk_channels, conf["final_dim"][0] // down, conf["final_dim"][1] // down, generator=g)
+    L = max(int(hypes.get("train_params", {}).get("max_cav", 5)), n_agents)
+    poses = make_poses(np.random.RandomState(seed), n_agents, spread_xy=(2.0, 1.0), spread_yaw=20.0)
+    return {"image_inputs": rig, "record_len": torch.tensor([n_agents], dtype=torch.int64),
+            "pairwise_t_matrix": torch.from_numpy(np.stack([get_pairwise_transformation(poses, L)]))}
