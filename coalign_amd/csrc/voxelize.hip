@@ -540,6 +540,25 @@ int grid_of(const double *voxel_size, const double *range, int g[3]) {
     return COALIGN_OK;
 }
 
+// gather_kernel's grid: enough workgroups for the worst case, capped -- both kinds of workgroup stride over the device-side counts.
+// `need` voxel rows at most, `n` points: a cell on the big-cell list holds > 16 of them.
+struct GatherGrid {
+    unsigned big_blocks, small_blocks;
+    int64_t list_cap;                 // entries of the big-cell list
+};
+
+GatherGrid gather_grid(int64_t need, int64_t n) {
+    GatherGrid g;
+    g.small_blocks = (unsigned)std::min<int64_t>((need + 15) / 16, 8192);
+    g.list_cap = n / 17 + 1;
+    g.big_blocks = (unsigned)std::min<int64_t>((g.list_cap + 3) / 4, 8192);
+    return g;
+}
+
+void launch_gather(const VoxArgs &a, const GatherGrid &g, hipStream_t s) {
+    hipLaunchKernelGGL(gather_kernel, dim3(g.big_blocks + g.small_blocks), dim3(kBlock), 0, s, a, (int)g.big_blocks, (int)g.list_cap);
+}
+
 int max_blocks_of(const int64_t *offsets, int n_clouds) {
     int64_t m = 1;
     for (int c = 0; c < n_clouds; ++c) m = std::max<int64_t>(m, (offsets[c + 1] - offsets[c] + kChunk - 1) / kChunk);
@@ -628,13 +647,38 @@ extern "C" int coalign_voxelize(const float *points, const int64_t *cloud_offset
     a.num_points = num_points;
     a.voxel_counts = voxel_counts;
     const dim3 per_point(a.max_blocks, n_clouds);
-    // gather grid: enough workgroups for the worst case, capped -- both kinds of workgroup stride over the device-side counts
-    const unsigned small_blocks = (unsigned)std::min<int64_t>((need + 15) / 16, 8192);
-    const int64_t list_cap = n / 17 + 1;
-    const unsigned big_blocks = (unsigned)std::min<int64_t>((list_cap + 3) / 4, 8192);
     hipLaunchKernelGGL(split_kernel, per_point, dim3(kBlock), 0, s, a);
     hipLaunchKernelGGL(owner_kernel, dim3(a.ranges, n_clouds), dim3(kOwner), 0, s, a);
     hipLaunchKernelGGL(assign_kernel, per_point, dim3(kBlock), 0, s, a);
-    hipLaunchKernelGGL(gather_kernel, dim3(big_blocks + small_blocks), dim3(kBlock), 0, s, a, (int)big_blocks, (int)list_cap);
+    launch_gather(a, gather_grid(need, n), s);
     return check_launch();
 }
+
+#ifdef COALIGN_LAB
+// Laboratory entry (include/coalign_amd_lab.h): gather_kernel alone, on tables the caller made -- the order inside a bucket segment is then the caller's
+// choice, which the public entry never leaves open (owner_kernel fills the segments nearly sorted).  Same kernel, same grid rule as coalign_voxelize.
+extern "C" int coalign_lab_voxelize_gather(const float *points, int64_t n_points, const int32_t *bucket, const int32_t *seg, const int32_t *cellinfo,
+                                           const int32_t *biglist, const int32_t *big_count, const int32_t *voxel_total, int max_points, float *voxels,
+                                           int64_t capacity, void *stream) {
+    using namespace coalign;
+    if (!points || !bucket || !seg || !cellinfo || !biglist || !big_count || !voxel_total || !voxels) return COALIGN_ERR_NULL_POINTER;
+    if (n_points < 1 || capacity < 1 || max_points < 1) return COALIGN_ERR_BAD_SHAPE;
+    if (max_points > 64 || n_points > (int64_t)1 << 30 || capacity > n_points) return COALIGN_ERR_UNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(voxels) | reinterpret_cast<uintptr_t>(cellinfo)) & 15) return COALIGN_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(seg) & 7) return COALIGN_ERR_UNSUPPORTED;
+    VoxArgs a{};
+    a.pts = reinterpret_cast<const float4 *>(points);
+    a.n_clouds = 0;                   // gather_kernel reads the total at voxel_counts[n_clouds]
+    a.max_points = max_points;
+    a.capacity = (int)capacity;
+    a.bucket = const_cast<int *>(bucket);
+    a.seg = reinterpret_cast<int2 *>(const_cast<int32_t *>(seg));
+    a.cellinfo = reinterpret_cast<int4 *>(const_cast<int32_t *>(cellinfo));
+    a.biglist = const_cast<int *>(biglist);
+    a.big_count = const_cast<int *>(big_count);
+    a.voxel_counts = const_cast<int *>(voxel_total);
+    a.voxels = reinterpret_cast<float4 *>(voxels);
+    launch_gather(a, gather_grid(capacity, n_points), static_cast<hipStream_t>(stream));
+    return check_launch();
+}
+#endif

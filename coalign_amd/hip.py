@@ -98,10 +98,11 @@ SIGNATURES = {
 }
 
 
-# include/coalign_amd_lab.h: entry points of the laboratory library only (measured, not adopted)
+# include/coalign_amd_lab.h: entry points of the laboratory library only (the Winograd kernel: measured, not adopted; the voxeliser's gather_kernel alone: for its limit tests)
 LAB_SIGNATURES = {
     "coalign_conv3x3_wino_weight_bytes": (c_size_t, [c_int, c_int]),
     "coalign_conv3x3_wino": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "coalign_lab_voxelize_gather": (c_int, [P, c_int64, P, P, P, P, P, P, c_int, P, c_int64, P]),
 }
 
 # include/coalign_amd_narrow.h: the extension header of ABI version 2 (product library; coalign_amd.h keeps its 68 names): the narrow-output 3x3 convolution
