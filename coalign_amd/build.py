@@ -30,7 +30,7 @@ LAB_LIB_PATH = os.path.join(LIB_DIR, "libcoalign_hip_lab.so")
 # cause).  `python -m coalign_amd.build --labvec`; COALIGN_LAB=vec loads it.  tools/pk_f32_recheck.sh runs the experiment.
 LABVEC_LIB_PATH = os.path.join(LIB_DIR, "libcoalign_hip_labvec.so")
 INCLUDE = os.path.join(REPO, "include")
-SOURCES = ["status.cpp", "pillar_scatter.hip", "pillar_sparse.hip", "warp_fuse.hip", "warp_fuse_nhwc.hip", "disco_fuse.hip", "v2v_fuse.hip", "v2v_robust.hip", "v2x_attn.hip", "v2x_window.hip", "v2x_ffn.hip", "lss_pool.hip", "w2c_fuse.hip", "w2comm.hip", "w2comm_msg.hip", "decode.hip", "nms.hip", "epilogue.hip", "voxelize.hip", "pose_graph.hip", "pose_graph_build.hip", "conv3x3.hip", "conv3x3_emu.hip", "conv3x3_sp.hip", "conv3x3_sp_s2.hip", "conv3x3_narrow.hip", "pointwise.hip"]
+SOURCES = ["status.cpp", "pillar_scatter.hip", "pillar_sparse.hip", "warp_fuse.hip", "warp_fuse_nhwc.hip", "disco_fuse.hip", "v2v_fuse.hip", "v2v_robust.hip", "v2x_attn.hip", "v2x_window.hip", "v2x_ffn.hip", "lss_pool.hip", "lss_bev.hip", "w2c_fuse.hip", "w2comm.hip", "w2comm_msg.hip", "decode.hip", "nms.hip", "epilogue.hip", "voxelize.hip", "pose_graph.hip", "pose_graph_build.hip", "conv3x3.hip", "conv3x3_emu.hip", "conv3x3_sp.hip", "conv3x3_sp_s2.hip", "conv3x3_narrow.hip", "pointwise.hip"]
 # Kernels that were measured and NOT adopted live in the laboratory library only: the Winograd F(2x2, 3x3) convolution (1.14 x / 0.89 x / 1.05 x
 # against the direct kernel per stage) -- include/coalign_amd_lab.h, coalign_amd.hip.lab_lib(), tests/test_round4_gpu.py keep it testable.
 LAB_ONLY_SOURCES = ["conv3x3_wino.hip"]
@@ -41,6 +41,8 @@ MSG_HEADER = os.path.join(CSRC, "coalign_amd_where2comm_msg.h")
 FFN_HEADER = os.path.join(CSRC, "coalign_amd_v2x_ffn.h")
 # The third: Lift-Splat's frustum pooling for the camera model (csrc/lss_pool.hip).
 LSS_HEADER = os.path.join(CSRC, "coalign_amd_lss.h")
+# The fourth: the camera model's BEV encoder -- the 7 x 7 stem and the up-sampling concatenation as SplitMap producers (csrc/lss_bev.hip).
+LSS_BEV_HEADER = os.path.join(CSRC, "coalign_amd_lss_bev.h")
 ARCH = "gfx950"
 # include/: one header per signature table of coalign_amd.hip (its HEADERS mapping is keyed by these names, in this order; the laboratory header comes last)
 ABI_HEADERS = ("coalign_amd.h", "coalign_amd_narrow.h", "coalign_amd_narrow_sparse.h", "coalign_amd_align.h", "coalign_amd_stage1.h", "coalign_amd_disco.h", "coalign_amd_v2v.h", "coalign_amd_v2x.h", "coalign_amd_v2x_window.h", "coalign_amd_w2c.h", "coalign_amd_v2v_robust.h", "coalign_amd_where2comm.h", "coalign_amd_lab.h")

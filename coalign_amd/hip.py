@@ -224,6 +224,15 @@ LSS_SIGNATURES = {
 }
 LSS_HEADER = _build.LSS_HEADER
 
+# csrc/coalign_amd_lss_bev.h (build.LSS_BEV_HEADER): the fifteenth extension header of ABI version 2 (product library): the camera model's BEV encoder -- the 7 x 7 /
+# stride-2 stem and the bilinear x 2 up-sampling with concatenation, both writing a SplitMap (csrc/lss_bev.hip)
+LSS_BEV_SIGNATURES = {
+    "coalign_conv7x7_s2_weight_bytes": (c_size_t, [c_int]),
+    "coalign_conv7x7_s2_sp": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "coalign_up2x_concat_sp": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
+}
+LSS_BEV_HEADER = _build.LSS_BEV_HEADER
+
 # header under include/ -> its table, in the order of the ABI's growth: what both loaders bind (coalign_amd_lab.h's LAB_SIGNATURES: the laboratory library alone)
 HEADERS = dict(zip(_build.ABI_HEADERS[:-1], (SIGNATURES, NARROW_SIGNATURES, NARROW_SPARSE_SIGNATURES, ALIGN_SIGNATURES, STAGE1_SIGNATURES, DISCO_SIGNATURES, V2V_SIGNATURES,
                                              V2X_SIGNATURES, V2X_WINDOW_SIGNATURES, W2C_SIGNATURES, V2VR_SIGNATURES, W2COMM_SIGNATURES)))
@@ -261,7 +270,7 @@ def lib() -> ctypes.CDLL:
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(
                 f"{path} is missing and could not be built ({exc}); the CoAlign hot path has no CPU fallback") from exc
-    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), W2COMM_MSG_SIGNATURES, V2X_FFN_SIGNATURES, LSS_SIGNATURES])
+    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), W2COMM_MSG_SIGNATURES, V2X_FFN_SIGNATURES, LSS_SIGNATURES, LSS_BEV_SIGNATURES])
     if handle.coalign_abi_version() != 2:
         raise CoalignHipError(f"ABI version mismatch: library reports {handle.coalign_abi_version()}, binding expects 2")
     _LIB = handle
@@ -281,7 +290,7 @@ def lab_lib() -> ctypes.CDLL:
             _build.build(lab=True)
         except Exception as exc:  # noqa: BLE001
             raise CoalignHipError(f"{path} is missing and could not be built ({exc})") from exc
-    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), W2COMM_MSG_SIGNATURES, V2X_FFN_SIGNATURES, LSS_SIGNATURES, LAB_SIGNATURES])
+    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), W2COMM_MSG_SIGNATURES, V2X_FFN_SIGNATURES, LSS_SIGNATURES, LAB_SIGNATURES, LSS_BEV_SIGNATURES])
     _LAB_LIB = handle
     return handle
 

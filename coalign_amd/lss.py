@@ -16,7 +16,7 @@ depends on the camera matrices alone (``LiftSplat.build_index``, once per rig) a
 torch route (``LiftSplat.forward_torch``), which is also what runs on the CPU and for shapes the kernel refuses.
 
 Out of scope here, as in the issue that introduced this module: the EfficientNet / ResNet-101 image trunks (pluggable), depth supervision and ground-truth
-depth, ``BevEncodeSSFusion``, hand-written convolutions for the BEV trunk, training.
+depth, ``BevEncodeSSFusion``, training.  The BEV trunk's convolutions have a kernel route behind ``COALIGN_LSS_BEV`` (off by default, ``BevEncodeMSFusion``).
 """
 from __future__ import annotations
 
@@ -29,13 +29,16 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import backbone, ops
 from .encoder import host_ints
 from .fusion import AttFusion, MaxFusion, regroup
 from .pose import normalize_pairwise_tfm
 
 # The kernel route of the frustum pooling: on by default on the GPU; "0" selects the torch route (module attribute, read at every call).
 LSS_POOL = os.environ.get("COALIGN_LSS_POOL", "1") != "0"
+# The kernel route of the BEV encoder (``BevEncodeMSFusion``: stem, ResNet stages, ``Up`` and ``down_layer`` on the SplitMap kernels): OFF by default, "1" switches it
+# on.  Read once at import; a module copies it into ``bev_kernels`` when it is built, and that attribute can be set per module.
+LSS_BEV = os.environ.get("COALIGN_LSS_BEV", "0") != "0"
 
 
 def gen_dx_bx(xbound, ybound, zbound):
@@ -253,7 +256,9 @@ class Up(nn.Module):
 
 
 class _BasicBlock(nn.Module):
-    """torchvision's ResNet ``BasicBlock`` under its attribute names (conv1, bn1, relu, conv2, bn2, downsample)."""
+    """torchvision's ResNet ``BasicBlock`` under its attribute names (conv1, bn1, relu, conv2, bn2, downsample).  A call is the reference's op sequence on every
+    device.  The names are also those of ``backbone.BasicBlock``, whose SplitMap route (route decision, folded weights, ``_forward_split``) is shared below as plain
+    functions: the kernel route of ``BevEncodeMSFusion`` calls it.  Not a subclass, so that whatever walks a model for ``backbone.BasicBlock`` sees what it saw before."""
 
     def __init__(self, inplanes: int, planes: int, stride: int = 1):
         super().__init__()
@@ -263,8 +268,14 @@ class _BasicBlock(nn.Module):
         self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, stride=1, padding=1, bias=False)
         self.bn2 = nn.BatchNorm2d(planes)
         self.downsample = None
+        self.stride = stride
         if stride != 1 or inplanes != planes:
             self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes, kernel_size=1, stride=stride, bias=False), nn.BatchNorm2d(planes))
+
+    route = backbone.BasicBlock.route
+    skip_pointwise = backbone.BasicBlock.skip_pointwise
+    _folded = backbone.BasicBlock._folded
+    _forward_split = backbone.BasicBlock._forward_split
 
     def forward(self, x):
         out = self.bn2(self.conv2(self.relu(self.bn1(self.conv1(x)))))
@@ -294,7 +305,10 @@ def _fuse_torch(x: torch.Tensor, record_len, affine: torch.Tensor, att: bool) ->
 
 class BevEncodeMSFusion(nn.Module):
     """lss_submodule.py:357-417 (``att_ms`` | ``max_ms``): a 7 x 7 stem, ResNet-18's ``layer1..3``, the three maps fused across the agents, ``Up`` twice and
-    ``down_layer``.  The convolutions are torch ops; the three fusions are the ``AttFusion`` / ``MaxFusion`` kernels on the GPU.  Parameter names are the
+    ``down_layer``.  By default the convolutions are torch ops; the three fusions are the ``AttFusion`` / ``MaxFusion`` kernels on the GPU.  With ``bev_kernels``
+    (``COALIGN_LSS_BEV=1``) an eval-mode float32 CUDA map takes the kernel route (``kernel_route``): stem on ``ops.conv7x7_s2_sp``, the stages on
+    the SplitMap route of ``backbone.BasicBlock``, both ``Up`` steps on ``ops.up2x_concat_sp`` + ``ops.conv3x3_sp``, decoded once on the batch [single maps ; fused
+    maps]; its two outputs are channels-last.  Parameter names are the
     reference's (``conv1``, ``bn1``, ``layer1.0.conv1`` ... ``layer2.0.downsample.0``, ``up_layer1.conv.0``, ...).  torchvision is not a dependency of this package:
     the ``layerN`` names are written from its ``BasicBlock`` attribute names and are NOT pinned by a golden fixture made from the reference."""
 
@@ -304,6 +318,7 @@ class BevEncodeMSFusion(nn.Module):
         inC = args["in_channels"]
         self.discrete_ratio = args["voxel_size"][0]
         self.downsample_rate = 1
+        self.bev_kernels = LSS_BEV                              # the kernel route of the convolutions (off by default); may be set per module
         self.conv1 = nn.Conv2d(inC, 64, kernel_size=7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
@@ -326,9 +341,124 @@ class BevEncodeMSFusion(nn.Module):
             return self.fuse_module[i](x, record_len, affine)
         return _fuse_torch(x, record_len, affine, isinstance(self.fuse_module[i], AttFusion))
 
+    # ---- the kernel route -----------------------------------------------------------------------------------------------------------------------------------
+    STEM_KERNEL = "conv7x7_s2_sp (7 x 7 / stride 2, channels-last float32 in, SplitMap out, fp16 x 2)"
+    UP_KERNEL = "up2x_concat_sp (bilinear x 2 + concatenation written as one SplitMap)"
+    SWITCHED_OFF = "switched off (COALIGN_LSS_BEV=0)"
+
+    def _blocks(self):
+        return [(f"layer{i + 1}.{j}", blk) for i, layer in enumerate((self.layer1, self.layer2, self.layer3)) for j, blk in enumerate(layer)]
+
+    def _static_reason(self) -> Optional[str]:
+        """The part of ``kernel_shape_reason`` that the module's shapes, its mode and the switches decide, without a tensor."""
+        inC = self.conv1.in_channels
+        if not ops.conv7x7_s2_shape_ok(inC, self.conv1.out_channels):
+            return f"in_channels = {inC} outside the stem kernel's Cin % 16 == 0, 16 .. {ops.CONV7X7_MAX_CIN}"
+        if self.training:
+            return "training mode"
+        if not backbone.split_maps_active():
+            return "the SplitMap arithmetic (fp16 x 2) is not in force"
+        if any(blk.route().kind != backbone.BLOCK_SPLIT for _, blk in self._blocks()):
+            return "a BasicBlock is off the SplitMap route (backbone's switches)"
+        return None
+
+    def kernel_shape_reason(self, x: torch.Tensor) -> Optional[str]:
+        """None when the kernels take the map ``x``, else why not, in words."""
+        static = self._static_reason()
+        if static is not None:
+            return static
+        if x.dim() != 4 or x.shape[1] != self.conv1.in_channels:
+            return f"a map of shape {tuple(x.shape)} for in_channels = {self.conv1.in_channels}"
+        H, W = int(x.shape[2]), int(x.shape[3])
+        if H % 8 or W % 8:
+            return f"H x W = {H} x {W}, not multiples of 8 (the Up concatenations do not match)"
+        if not x.is_cuda or x.dtype != torch.float32 or torch.is_grad_enabled() and x.requires_grad:
+            return "not a float32 CUDA tensor in inference"
+        return None
+
+    def kernel_route(self, x: torch.Tensor) -> bool:
+        """Eval mode, ``bev_kernels`` and no reason against (the family convention of DESIGN.md section 8k)."""
+        return bool(not self.training and self.bev_kernels and self.kernel_shape_reason(x) is None)
+
+    def plan(self) -> dict:
+        """{layer name: route text} from the module's shapes, mode and switches alone (no GPU, no tensor; the map-size and device conditions of
+        ``kernel_shape_reason`` are decided per call).  ``routes.plan`` does not walk camera models; this is the camera trunk's own answer."""
+        from .routes import conv3x3_text                      # (routes imports the detector classes, which import this module)
+        why = self.SWITCHED_OFF if not self.bev_kernels else self._static_reason()
+        lines = {}
+        convs = [(n, m) for n, m in self.named_modules() if isinstance(m, nn.Conv2d)]
+        if why is not None:
+            for n, m in convs:
+                lines[n] = f"{backbone.MIOPEN} ({why})"
+            lines["up_layer2.up"] = lines["up_layer1.up"] = f"torch bilinear interpolation + cat ({why})"
+        else:
+            lines["conv1"] = self.STEM_KERNEL
+            for n, blk in self._blocks():
+                r = blk.route()
+                if blk.stride == 1:
+                    lines[f"{n}.conv1"] = backbone.SP
+                else:
+                    lines[f"{n}.conv1"] = backbone.SP_S2 if r.s2_dense else conv3x3_text(blk.conv1, backbone.CONV_EMU_TERMS) + backbone.SPLIT_OUT
+                    lines[f"{n}.downsample.0"] = ("tenth tap of " + backbone.SP_S2.split(" (")[0] if r.s2_dense and r.skip_fused
+                                                  else backbone.pointwise_text(blk.downsample[0].in_channels, backbone.CONV_EMU_TERMS))
+                lines[f"{n}.conv2"] = backbone.SP
+            for up in ("up_layer2", "up_layer1"):
+                lines[f"{up}.up"] = self.UP_KERNEL
+                lines[f"{up}.conv.0"] = lines[f"{up}.conv.3"] = backbone.SP
+            lines["down_layer.0"] = lines["down_layer.2"] = backbone.SP
+        lines["fuse_module"] = MaxFusion.plan_fusion(self.fuse_module[0], self.conv1.out_channels)[0]
+        return lines
+
+    def _folded(self):
+        """(stem image, bias), per ``Up`` and for ``down_layer`` the (tap-major terms-16 image, bias) pairs: BatchNorm folded (``backbone.fold_bn``), cached until a
+        parameter or buffer changes -- a warmed-up forward allocates no weight memory."""
+        def pack(conv, bn):
+            w, b = backbone.fold_bn(conv.weight, conv.bias, bn) if bn is not None else (conv.weight, conv.bias)
+            return backbone.Conv3x3Pack(w.detach().float().contiguous()).emu(16, True), b.detach().float().contiguous(), conv.out_channels
+
+        def build():
+            w, b = backbone.fold_bn(self.conv1.weight, None, self.bn1)
+            ups = [[pack(u.conv[0], u.conv[1]), pack(u.conv[3], u.conv[4])] for u in (self.up_layer2, self.up_layer1)]
+            return (ops.pack_conv7x7_s2_weight(w), b.float().contiguous()), ups, [pack(self.down_layer[0], None), pack(self.down_layer[2], None)]
+        return backbone._cache_of(self).get(self, build)
+
+    def _forward_kernels(self, x, record_len, affine):
+        stem, ups, down = self._folded()
+        A = x.shape[0]
+        cur = ops.conv7x7_s2_sp(x, stem[0], stem[1], relu=True)
+        # layer1..3 as ResNetStages.forward runs them: SplitMaps inside a stage; its last block hands out the channels-last float32 map (fusion, Up) and, when the
+        # next stage opens with conv3x3_sp_s2, the SplitMap of that map as well
+        layers, maps, carry = (self.layer1, self.layer2, self.layer3), [], None
+        for i, layer in enumerate(layers):
+            both = i + 1 < len(layers) and layers[i + 1][0].route().s2_dense
+            for j, blk in enumerate(layer):
+                last = j == len(layer) - 1
+                cur = blk._forward_split(cur, blk.route(), last, out_both=last and both, x_split=carry if j == 0 and not isinstance(cur, ops.SplitMap) else None)
+                carry = None
+                if last and both:
+                    cur, carry = cur
+            maps.append(cur)
+        x1, x2, x3 = maps
+        f1, f2, f3 = (self._fuse(i, v, record_len, affine) for i, v in enumerate(maps))
+
+        def batch(single, fused):                               # [single maps ; fused maps] in channels-last memory
+            return torch.cat([single.permute(0, 2, 3, 1), fused.permute(0, 2, 3, 1)]).permute(0, 3, 1, 2)
+
+        def conv(y, layer, out_split=True, relu=True):
+            return ops.conv3x3_sp(y, layer[0], layer[1], layer[2], None, relu, out_split=out_split)
+
+        y = ops.up2x_concat_sp(batch(x2, f2), batch(x3, f3))
+        y = conv(conv(y, ups[0][0]), ups[0][1], out_split=False)             # (channels-last float32: the next Up's low map)
+        y = ops.up2x_concat_sp(batch(x1, f1), y)
+        y = conv(conv(y, ups[1][0]), ups[1][1])
+        y = conv(conv(y, down[0]), down[1], out_split=False)
+        return y[:A], y[A:]
+
     def forward(self, x, record_len, pairwise_t_matrix):
         _, _, H, W = x.shape
         affine = normalize_pairwise_tfm(pairwise_t_matrix, H, W, self.discrete_ratio, self.downsample_rate)
+        if self.kernel_route(x):
+            return self._forward_kernels(x, record_len, affine)
         x = self.relu(self.bn1(self.conv1(x)))
         x1 = self.layer1(x)
         x2 = self.layer2(x1)
@@ -418,5 +548,5 @@ class LiftSplatShootIntermediate(nn.Module):
         return out
 
 
-__all__ = ["LSS_POOL", "gen_dx_bx", "depth_discretization", "frustum_axes", "create_frustum", "LiftSplat", "Up", "BevEncodeMSFusion", "CamHeads",
+__all__ = ["LSS_POOL", "LSS_BEV", "gen_dx_bx", "depth_discretization", "frustum_axes", "create_frustum", "LiftSplat", "Up", "BevEncodeMSFusion", "CamHeads",
            "LiftSplatShootIntermediate"]

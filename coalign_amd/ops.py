@@ -2372,3 +2372,78 @@ def lss_pool(depth_logit: torch.Tensor, x_img: torch.Tensor, index: LiftSplatInd
         hip.check(hip.lib().coalign_lss_pool(_ptr(rows), _ptr(prob), A * N * fH * fW, C, D, _ptr(index.points), index.n_points, _ptr(index.starts), index.cells,
                                              _ptr(index.long_cells), int(index.long_cells.numel()), _ptr(out), _stream()), "coalign_lss_pool")
     return out
+
+
+# ---- the camera model's BEV encoder (csrc/coalign_amd_lss_bev.h, csrc/lss_bev.hip) ---------------------------------------------------------------------------
+CONV7X7_COUT = 64             # COALIGN_CONV7X7_COUT
+CONV7X7_MAX_CIN = 512         # COALIGN_CONV7X7_MAX_CIN
+
+
+def conv7x7_s2_shape_ok(cin: int, cout: int = CONV7X7_COUT) -> bool:
+    """A 7 x 7 / stride-2 layer of (cin, cout) fits ``coalign_conv7x7_s2_sp``."""
+    return cout == CONV7X7_COUT and cin % 16 == 0 and 16 <= cin <= CONV7X7_MAX_CIN
+
+
+def pack_conv7x7_s2_weight(weight: torch.Tensor) -> torch.Tensor:
+    """[64, Cin, 7, 7] fp32 (Cin % 16 == 0, 16 <= Cin <= 512) -> the weight image of ``coalign_conv7x7_s2_sp`` as uint8 (csrc/coalign_amd_lss_bev.h (18a)):
+    [Cin / 16][7 ky][7 kx][2 terms][2 channel halves][64 cout][8 cin] fp16 sp16 pairs of the per-output-channel scaled weights (the scaling and rounding of
+    ``pack_conv3x3_emu_weight``'s terms-16 image), 16 zero bytes, [64] float32 2^-k_c, [64] float32 2^k_c."""
+    co, ci, kh, kw = weight.shape
+    if (kh, kw) != (7, 7) or not conv7x7_s2_shape_ok(ci, co):
+        raise ValueError(f"conv7x7_s2_sp needs 7x7 weights with Cout == {CONV7X7_COUT}, Cin % 16 == 0 and 16 <= Cin <= {CONV7X7_MAX_CIN}, got {tuple(weight.shape)}")
+    wf = weight.detach().float()
+    w = wf.reshape(co, ci // 16, 2, 8, 7, 7).permute(1, 4, 5, 2, 0, 3)    # [interval, ky, kx, channel half, cout, cin]
+    amax = wf.abs().reshape(co, -1).amax(dim=1)
+    k = torch.where(amax > 0, 14 - torch.frexp(amax)[1], torch.zeros_like(amax, dtype=torch.int32)).clamp(-60, 60).to(torch.int32)
+    scale = torch.ldexp(torch.ones_like(amax), k)
+    ws = (w * scale.reshape(1, 1, 1, 1, co, 1)).contiguous()
+    ws = ((ws.view(torch.int32) + 2) & -4).view(torch.float32)             # 22 significant bits, ties away from zero (sp16_round)
+    hi = ws.half()
+    lo = ((ws - hi.float()) * 1024.0).half()
+    flat = torch.stack([hi, lo], dim=3).contiguous().view(torch.uint8).reshape(-1)      # [interval, ky, kx, term, channel half, cout, cin]
+    tail = [torch.ldexp(torch.ones_like(amax), -k).contiguous().view(torch.uint8).reshape(-1), scale.contiguous().view(torch.uint8).reshape(-1)]
+    out = torch.cat([flat, torch.zeros(16, dtype=torch.uint8, device=flat.device)] + tail)
+    assert out.numel() == hip.lib().coalign_conv7x7_s2_weight_bytes(ci)
+    return out
+
+
+@_device_op
+def conv7x7_s2_sp(x: torch.Tensor, image: torch.Tensor, bias: torch.Tensor, relu: bool = True) -> "SplitMap":
+    """y = act(conv7x7(x, w, stride 2, padding 3) + bias) with 64 output channels, written as a ``SplitMap`` (csrc/coalign_amd_lss_bev.h (18b)): the stem of
+    ``lss.BevEncodeMSFusion``.  ``x``: float32 of logical shape [N, C, H, W], read in place when its memory is channels-last (what ``lss_pool`` writes), converted
+    by torch first when it is NCHW; ``image``: ``pack_conv7x7_s2_weight``; ``bias`` [64]."""
+    _need_gpu(x, image, bias)
+    if x.dim() != 4:
+        raise ValueError("conv7x7_s2_sp reads a [N, C, H, W] tensor")
+    N, Cin, H, W = (int(v) for v in x.shape)
+    L = hip.lib()
+    if not conv7x7_s2_shape_ok(Cin) or image.numel() != L.coalign_conv7x7_s2_weight_bytes(Cin) or bias.numel() != CONV7X7_COUT:
+        raise ValueError(f"conv7x7_s2_sp needs Cin % 16 == 0, 16 <= Cin <= {CONV7X7_MAX_CIN}, the weight image of Cin and {CONV7X7_COUT} biases")
+    if H < 1 or W < 1:
+        raise ValueError("conv7x7_s2_sp needs H, W >= 1")
+    xt = to_nhwc(x)
+    out = SplitMap.empty(N, CONV7X7_COUT, (H - 1) // 2 + 1, (W - 1) // 2 + 1, xt.device)
+    with _Timed("conv7x7_s2_sp"):
+        hip.check(L.coalign_conv7x7_s2_sp(_ptr(xt), _ptr(image), _ptr(_f32c(bias)), _ptr(out.data), N, Cin, H, W, int(bool(relu)), _ptr(sp_range_flag(xt.device)), _stream()),
+                  "coalign_conv7x7_s2_sp")
+    return out
+
+
+@_device_op
+def up2x_concat_sp(skip: torch.Tensor, low: torch.Tensor) -> "SplitMap":
+    """SplitMap of ``cat([skip, up(low)], dim=1)``, ``up`` = bilinear x 2 with ``align_corners=True``, in one pass (csrc/coalign_amd_lss_bev.h (18c)): ``lss.Up``
+    up to its convolutions.  ``skip`` [N, Cs, 2h, 2w], ``low`` [N, Cl, h, w], float32, read in place when channels-last, converted by torch first when NCHW."""
+    _need_gpu(skip, low)
+    if skip.dim() != 4 or low.dim() != 4:
+        raise ValueError("up2x_concat_sp reads two [N, C, H, W] tensors")
+    N, Cs, H2, W2 = (int(v) for v in skip.shape)
+    Nl, Cl, h, w = (int(v) for v in low.shape)
+    if Nl != N or (H2, W2) != (2 * h, 2 * w) or h < 1 or w < 1:
+        raise ValueError(f"up2x_concat_sp: skip {tuple(skip.shape)} must be [N, Cs, 2h, 2w] for low {tuple(low.shape)} = [N, Cl, h, w]")
+    if Cs % 16 or Cl % 16 or Cs < 16 or Cl < 16:
+        raise ValueError("up2x_concat_sp needs Cs % 16 == 0 and Cl % 16 == 0")
+    st, lt = to_nhwc(skip), to_nhwc(low)
+    out = SplitMap.empty(N, Cs + Cl, H2, W2, st.device)
+    with _Timed("up2x_concat_sp"):
+        hip.check(hip.lib().coalign_up2x_concat_sp(_ptr(st), _ptr(lt), _ptr(out.data), N, Cs, Cl, h, w, _ptr(sp_range_flag(st.device)), _stream()), "coalign_up2x_concat_sp")
+    return out
