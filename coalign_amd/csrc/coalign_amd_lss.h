@@ -66,7 +66,8 @@ int coalign_lss_depth_prob(const float *depth_logit, int M, int D, int fH, int f
  *   C in {64, 128} and 1 <= D <= COALIGN_LSS_MAX_DEPTH: anything else COALIGN_ERR_UNSUPPORTED.  rows, n_points, cells, n_long < 0, n_long > cells,
  *   rows D >= 2^31 or n_points > 0 with rows = 0: COALIGN_ERR_BAD_SHAPE.  NULL out / starts with cells > 0, NULL x_rows / prob / points with n_points > 0, NULL
  *   long_cells with n_long > 0, x_rows / out not aligned to 16 bytes, points to 8, the others to 4: COALIGN_ERR_NULL_POINTER.  cells = 0 returns COALIGN_OK
- *   without a launch.  The kernel reads nothing outside [0, rows) and [0, n_points) whatever the index holds (entries outside are skipped), and writes only out. */
+ *   without a launch.  The kernel reads nothing outside [0, rows) and [0, n_points) whatever the index holds (entries outside are skipped), and writes only out.
+ *   "Every element is written" presumes that `long_cells` is complete: the row of a list longer than COALIGN_LSS_CHUNK that `long_cells` does not name is left as it was. */
 int coalign_lss_pool(const float *x_rows, const float *prob, int rows, int C, int D, const int *points, int n_points, const int *starts, int cells,
                      const int *long_cells, int n_long, float *out, void *stream);
 

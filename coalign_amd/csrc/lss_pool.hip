@@ -143,11 +143,25 @@ __device__ __forceinline__ void sum_points(const PoolArgs &a, int b, int e, int 
         const int cnt = min(64, e - i);
         int row = 0;
         float pv = 0.f;
+        bool ok = false, outside = false;
         if (lane < cnt) {
             const int2 pt = a.points[i + lane];
-            const bool ok = (unsigned)pt.x < (unsigned)a.rows && (unsigned)pt.y < (unsigned)a.prob_len;      // (an entry outside the buffers adds 0 x row 0)
+            ok = (unsigned)pt.x < (unsigned)a.rows && (unsigned)pt.y < (unsigned)a.prob_len;
+            outside = !ok;
             row = ok ? pt.x : 0;
             pv = ok ? a.prob[pt.y] : 0.f;
+        }
+        if (__builtin_amdgcn_ballot_w64(outside)) {            // an entry outside the buffers (an inconsistent index): it is SKIPPED -- not 0 x row 0, which is NaN when
+            unsigned long long take = __builtin_amdgcn_ballot_w64(ok);
+            while (take) {                                     // that row holds inf or NaN; the entries that are left are added one by one, in the same order
+                const int j = __builtin_ctzll(take);
+                take &= take - 1;
+                const Row<C> v = load_row<C>(a.x, __builtin_amdgcn_readlane(row, j), lane);
+                const float pw = lane_value(pv, j);
+                s0 = fmaf(pw, v.v0, s0);
+                if constexpr (C == 128) s1 = fmaf(pw, v.v1, s1);
+            }
+            continue;
         }
         int j = 0;
         for (; j + 8 <= cnt; j += 8) {

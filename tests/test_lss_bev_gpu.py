@@ -66,8 +66,10 @@ def conv7_f64(x, w, b):
 
 
 # (N, Cin, H, W): centre tap only | smallest even map | odd sizes | smallest map the route accepts | the mini config | outputs no tile edge divides |
-# straddles tile edges | one full-size map (K = 6272)
-STEM_CASES = [(3, 16, 1, 1), (2, 64, 2, 2), (2, 64, 7, 9), (1, 128, 8, 8), (5, 64, 16, 32), (2, 128, 40, 24), (1, 64, 66, 130), (1, 128, 240, 240)]
+# straddles tile edges | one full-size map (K = 6272) | two and three channel intervals (the one patch buffer restaged once and twice) | above the model's channel
+# counts, up to the entry's limit (K = 12 544 and 25 088)
+STEM_CASES = [(3, 16, 1, 1), (2, 64, 2, 2), (2, 64, 7, 9), (1, 128, 8, 8), (5, 64, 16, 32), (2, 128, 40, 24), (1, 64, 66, 130), (1, 128, 240, 240),
+              (1, 32, 9, 9), (1, 48, 16, 16), (1, 256, 8, 8), (1, 512, 8, 8)]
 _STEM = {}
 
 
@@ -88,7 +90,8 @@ def _stem_case(case):
 def test_stem_mixed_channel_scales_against_float64(case, relu):
     """Every output channel of ``conv7x7_s2_sp`` within 3e-6 of its own scale + 2^-33 of the float64 convolution of the 22-bit inputs with the unrounded
     weights, output channels on scales 2^-20 ... 2^6; the all-zero channel is exactly act(bias) as a SplitMap holds it; float32 ``F.conv2d``'s error on the same
-    inputs is printed beside the kernel's."""
+    inputs is printed beside the kernel's.  Above Cin = 128 (K beyond 6 272, where the 3e-6 had been measured) the bound is the larger of 3e-6 and TWICE the
+    library's own worst-channel error on the same inputs: both accumulate in fp32, the sp16 pair holds 22 operand bits where float32 holds 24."""
     N, Ci, H, W = case
     x, w, b, image, pre, x22 = _stem_case(case)
     ref = torch.relu(pre) if relu else pre
@@ -98,9 +101,10 @@ def test_stem_mixed_channel_scales_against_float64(case, relu):
     got = y.dense()
     lib = F.conv2d(x22, w, b, stride=2, padding=3)
     e_lib = channel_error(torch.relu(lib) if relu else lib, ref, pre)
+    bound = BOUND if Ci <= 128 else max(BOUND, 2.0 * e_lib)
     print(f"\nconv7x7_s2_sp {case} {'relu' if relu else 'linear'}: K = {49 * Ci}, worst channel error beyond 2^-33 {channel_error(got, ref, pre, SP_ABS):.2e} of the channel scale "
-          f"(bound {BOUND:g}); float32 F.conv2d {e_lib:.2e}")
-    assert_channels_close(got, ref, case, pre)
+          f"(bound {bound:g}); float32 F.conv2d {e_lib:.2e}")
+    assert_channels_close(got, ref, case, pre, bound)
     zero = b[ZERO_CH].view(1, 1, 1, 1).expand(N, 16, y.shape[2], y.shape[3])
     assert torch.equal(got[:, ZERO_CH], ops.SplitMap.pack(torch.relu(zero) if relu else zero).dense()[:, 0]), case
     if not relu and H * W > 1:
