@@ -34,18 +34,12 @@ SOURCES = ["status.cpp", "pillar_scatter.hip", "pillar_sparse.hip", "warp_fuse.h
 # Kernels that were measured and NOT adopted live in the laboratory library only: the Winograd F(2x2, 3x3) convolution (1.14 x / 0.89 x / 1.05 x
 # against the direct kernel per stage) -- include/coalign_amd_lab.h, coalign_amd.hip.lab_lib(), tests/test_round4_gpu.py keep it testable.
 LAB_ONLY_SOURCES = ["conv3x3_wino.hip"]
-# The extension header that lies beside the sources (csrc/), bound like ABI_HEADERS' by coalign_amd.hip: Where2comm's messages (csrc/w2comm_msg.hip).  It says itself
-# why it is not under include/.
-MSG_HEADER = os.path.join(CSRC, "coalign_amd_where2comm_msg.h")
-# The second of that kind: V2X-ViT's feed-forward block in one launch (csrc/v2x_ffn.hip).
-FFN_HEADER = os.path.join(CSRC, "coalign_amd_v2x_ffn.h")
-# The third: Lift-Splat's frustum pooling for the camera model (csrc/lss_pool.hip).
-LSS_HEADER = os.path.join(CSRC, "coalign_amd_lss.h")
-# The fourth: the camera model's BEV encoder -- the 7 x 7 stem and the up-sampling concatenation as SplitMap producers (csrc/lss_bev.hip).
-LSS_BEV_HEADER = os.path.join(CSRC, "coalign_amd_lss_bev.h")
 ARCH = "gfx950"
-# include/: one header per signature table of coalign_amd.hip (its HEADERS mapping is keyed by these names, in this order; the laboratory header comes last)
-ABI_HEADERS = ("coalign_amd.h", "coalign_amd_narrow.h", "coalign_amd_narrow_sparse.h", "coalign_amd_align.h", "coalign_amd_stage1.h", "coalign_amd_disco.h", "coalign_amd_v2v.h", "coalign_amd_v2x.h", "coalign_amd_v2x_window.h", "coalign_amd_w2c.h", "coalign_amd_v2v_robust.h", "coalign_amd_where2comm.h", "coalign_amd_lab.h")
+# include/: every header of the C ABI, one per signature table of coalign_amd.hip, in the order of the ABI's growth (hip.HEADERS has the same keys in the same order;
+# the laboratory header, bound by hip.lab_lib() alone, comes last)
+ABI_HEADERS = ("coalign_amd.h", "coalign_amd_narrow.h", "coalign_amd_narrow_sparse.h", "coalign_amd_align.h", "coalign_amd_stage1.h", "coalign_amd_disco.h", "coalign_amd_v2v.h",
+               "coalign_amd_v2x.h", "coalign_amd_v2x_window.h", "coalign_amd_w2c.h", "coalign_amd_v2v_robust.h", "coalign_amd_where2comm.h", "coalign_amd_where2comm_msg.h",
+               "coalign_amd_v2x_ffn.h", "coalign_amd_lss.h", "coalign_amd_lss_bev.h", "coalign_amd_lab.h")
 # per-source extras.  pillar_scatter.hip: its matrix-core encoder reduces the accumulators with VALU right after each instruction
 # pair -- results in VGPRs (not AGPRs) save 64 v_accvgpr_read per pass; -fno-honor-nans drops the canonicalising v_max the compiler
 # puts in front of every two-operand fmaxf of a raw matrix result (20 per pass; the file tests for NaN nowhere, its selects are explicit).

@@ -1,4 +1,4 @@
-// The two operations of the camera model's BEV encoder that the SplitMap convolutions do not cover, gfx950 (csrc/coalign_amd_lss_bev.h):
+// The two operations of the camera model's BEV encoder that the SplitMap convolutions do not cover, gfx950 (include/coalign_amd_lss_bev.h):
 //   conv7x7_s2_sp    the 7 x 7 / stride 2 / pad 3 stem, channels-last float32 in, 64 channels out as a SplitMap
 //                    (opencood/models/sub_modules/lss_submodule.py:369-372, 402-404);
 //   up2x_concat_sp   bilinear x 2 up-sampling (align_corners = True) of the low map, concatenated behind the skip map, as a SplitMap in one pass

@@ -13,7 +13,7 @@
 //   3. barrier; the C / 32 row tiles of W2 over that tile, b2 seeding; the residual x (read again: an L2 hit) added, streaming stores.
 // The last tile loads zeros for the rows behind `tokens` (yhat = 0, finite throughout) and stores nothing for them.  LDS: 32 (4 C + 16) + 32 (4 M + 16) bytes,
 // 33 KB + 66 KB at (256, 512): above 64 KB the limit of dynamic LDS is raised once per device.  No workspace, no atomics: the same input gives the same bits.
-// The hidden activations are inside the fp16 range by the packer's static bound (csrc/coalign_amd_v2x_ffn.h): no range flag.
+// The hidden activations are inside the fp16 range by the packer's static bound (include/coalign_amd_v2x_ffn.h): no range flag.
 #include "common.h"
 
 #include "coalign_amd_v2x_ffn.h"

@@ -105,18 +105,18 @@ LAB_SIGNATURES = {
     "coalign_lab_voxelize_gather": (c_int, [P, c_int64, P, P, P, P, P, P, c_int, P, c_int64, P]),
 }
 
-# include/coalign_amd_narrow.h: the extension header of ABI version 2 (product library; coalign_amd.h keeps its 68 names): the narrow-output 3x3 convolution
+# include/coalign_amd_narrow.h: extension header of ABI version 2 (product library; coalign_amd.h keeps its 68 names): the narrow-output 3x3 convolution
 NARROW_SIGNATURES = {
     "coalign_conv3x3_narrow_weight_bytes": (c_size_t, [c_int, c_int]),
     "coalign_conv3x3_sp_narrow": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
 }
 
-# include/coalign_amd_narrow_sparse.h: the third extension header of ABI version 2 (product library): the narrow-output convolution reading the sparse canvas
+# include/coalign_amd_narrow_sparse.h: extension header of ABI version 2 (product library): the narrow-output convolution reading the sparse canvas
 NARROW_SPARSE_SIGNATURES = {
     "coalign_conv3x3_sp_narrow_sparse": (c_int, [P, c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
 }
 
-# include/coalign_amd_align.h: the second extension header of ABI version 2 (product library): online pose correction -- stage-1 gather, pose-graph
+# include/coalign_amd_align.h: extension header of ABI version 2 (product library): online pose correction -- stage-1 gather, pose-graph
 # construction, corrected pairwise / affine matrices (csrc/pose_graph_build.hip)
 ALIGN_SIGNATURES = {
     "coalign_align_store_boxes": (c_int, []),
@@ -125,7 +125,7 @@ ALIGN_SIGNATURES = {
     "coalign_pose_correct_matrices": (c_int, [c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, P, P, P]),
 }
 
-# include/coalign_amd_stage1.h: the fourth extension header of ABI version 2 (product library): stage 1 of all agents in one pass -- decode, rotated NMS and
+# include/coalign_amd_stage1.h: extension header of ABI version 2 (product library): stage 1 of all agents in one pass -- decode, rotated NMS and
 # the store gather of every agent in five launches (csrc/decode.hip, csrc/nms.hip)
 STAGE1_SIGNATURES = {
     "coalign_stage1_boxes_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
@@ -134,14 +134,14 @@ STAGE1_SIGNATURES = {
                                              c_int, P, P, P, P, P, c_size_t, P]),
 }
 
-# include/coalign_amd_disco.h: the fifth extension header of ABI version 2 (product library): DiscoNet's pixel-weight fusion -- warp, per-pixel MLP, softmax
+# include/coalign_amd_disco.h: extension header of ABI version 2 (product library): DiscoNet's pixel-weight fusion -- warp, per-pixel MLP, softmax
 # over agents and weighted sum in one launch (csrc/disco_fuse.hip)
 DISCO_SIGNATURES = {
     "coalign_disco_param_bytes": (c_size_t, [c_int]),
     "coalign_disco_fuse": (c_int, [P, c_int, c_int, c_int, c_int, P, P, c_size_t, P, P]),
 }
 
-# include/coalign_amd_v2v.h: the sixth extension header of ABI version 2 (product library): the glue of V2VNet's message passing between its convolutions --
+# include/coalign_amd_v2v.h: extension header of ABI version 2 (product library): the glue of V2VNet's message passing between its convolutions --
 # warp + operand split, message mask + aggregation + GRU input, GRU gate (csrc/v2v_fuse.hip)
 V2V_SIGNATURES = {
     "coalign_v2v_warp_split": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
@@ -149,7 +149,7 @@ V2V_SIGNATURES = {
     "coalign_v2v_gate": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
 }
 
-# include/coalign_amd_v2x.h: the seventh extension header of ABI version 2 (product library): V2X-ViT's heterogeneous agent attention -- warp, LayerNorm, the folded
+# include/coalign_amd_v2x.h: extension header of ABI version 2 (product library): V2X-ViT's heterogeneous agent attention -- warp, LayerNorm, the folded
 # q / k / v projection, softmax over the agents per head, output projection and residual in two launches (csrc/v2x_attn.hip)
 V2X_SIGNATURES = {
     "coalign_v2x_param_bytes": (c_size_t, [c_int]),
@@ -157,7 +157,7 @@ V2X_SIGNATURES = {
     "coalign_v2x_agent_attention": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P, P, c_size_t, P]),
 }
 
-# include/coalign_amd_v2x_window.h: the eighth extension header of ABI version 2 (product library): V2X-ViT's pyramid window attention with split attention --
+# include/coalign_amd_v2x_window.h: extension header of ABI version 2 (product library): V2X-ViT's pyramid window attention with split attention --
 # LayerNorm + the folded 9C x C projection, attention inside the 4 / 8 / 16 windows, the branch weights, output projections and residual in three or four
 # launches (csrc/v2x_window.hip)
 V2X_WINDOW_SIGNATURES = {
@@ -166,7 +166,7 @@ V2X_WINDOW_SIGNATURES = {
     "coalign_v2x_window_attention": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P, P, c_size_t, P]),
 }
 
-# include/coalign_amd_w2c.h: the ninth extension header of ABI version 2 (product library): When2com's handshake fusion after its convolutions -- the pooled key /
+# include/coalign_amd_w2c.h: extension header of ABI version 2 (product library): When2com's handshake fusion after its convolutions -- the pooled key /
 # query heads with the softmax over the agents in two launches, the warp-and-weighted-sum of the agents' maps in one (csrc/w2c_fuse.hip)
 W2C_SIGNATURES = {
     "coalign_w2c_workspace_bytes": (c_size_t, []),
@@ -174,7 +174,7 @@ W2C_SIGNATURES = {
     "coalign_w2c_fuse": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P]),
 }
 
-# include/coalign_amd_v2v_robust.h: the tenth extension header of ABI version 2 (product library): the glue of the pose-robust V2VNet between its convolutions --
+# include/coalign_amd_v2v_robust.h: extension header of ABI version 2 (product library): the glue of the pose-robust V2VNet between its convolutions --
 # pooling tails, the attention's score head, the pose regression's head, pairwise matrices, the whole WeightedEM in one workgroup, the weighted aggregation
 # (csrc/v2v_robust.hip)
 V2VR_SIGNATURES = {
@@ -187,7 +187,7 @@ V2VR_SIGNATURES = {
     "coalign_v2vr_aggregate": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P, P, P]),
 }
 
-# include/coalign_amd_where2comm.h: the eleventh extension header of ABI version 2 (product library): Where2comm's confidence-masked fusion -- the communication
+# include/coalign_amd_where2comm.h: extension header of ABI version 2 (product library): Where2comm's confidence-masked fusion -- the communication
 # masks and rates of every agent at every backbone level in one launch, the warp and fusion of the masked maps in one launch per frame (csrc/w2comm.hip)
 W2COMM_SIGNATURES = {
     "coalign_w2comm_masks": (c_int, [P, c_int, c_int, c_int, c_int, POINTER(c_int32), c_int, P, P, c_int, c_float, c_int, POINTER(P), P, P]),
@@ -195,7 +195,7 @@ W2COMM_SIGNATURES = {
                                          POINTER(c_int32), c_int, P, POINTER(c_int32), c_int, P]),
 }
 
-# csrc/coalign_amd_where2comm_msg.h (build.MSG_HEADER): the twelfth extension header of ABI version 2 (product library): Where2comm's messages -- bitmaps, rank
+# include/coalign_amd_where2comm_msg.h: extension header of ABI version 2 (product library): Where2comm's messages -- bitmaps, rank
 # tables and counts of every agent and level in one launch, the masked pixels' rows packed in one launch, and the fusion that reads dense and packed sources
 # (csrc/w2comm_msg.hip).  The reference has no counterpart.
 W2COMM_MSG_SIGNATURES = {
@@ -204,17 +204,15 @@ W2COMM_MSG_SIGNATURES = {
     "coalign_w2comm_fuse_packed": (c_int, [c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(P), POINTER(P), POINTER(P), POINTER(P),
                                            POINTER(c_int32), POINTER(c_int32), c_int, P, c_int, P]),
 }
-MSG_HEADER = _build.MSG_HEADER
 
-# csrc/coalign_amd_v2x_ffn.h (build.FFN_HEADER): the thirteenth extension header of ABI version 2 (product library): V2X-ViT's feed-forward block -- LayerNorm, the
+# include/coalign_amd_v2x_ffn.h: extension header of ABI version 2 (product library): V2X-ViT's feed-forward block -- LayerNorm, the
 # folded first linear, GELU, the second linear and the residual per token in one launch (csrc/v2x_ffn.hip)
 V2X_FFN_SIGNATURES = {
     "coalign_v2x_ffn_param_bytes": (c_size_t, [c_int, c_int]),
     "coalign_v2x_feed_forward": (c_int, [P, c_int, c_int, c_int, P, c_size_t, P, P]),
 }
-FFN_HEADER = _build.FFN_HEADER
 
-# csrc/coalign_amd_lss.h (build.LSS_HEADER): the fourteenth extension header of ABI version 2 (product library): Lift-Splat's frustum pooling -- the voxel of every
+# include/coalign_amd_lss.h: extension header of ABI version 2 (product library): Lift-Splat's frustum pooling -- the voxel of every
 # frustum point once per camera rig, then per frame the depth softmax and the sum of probability x feature row per BEV cell through an inverted index, in two
 # launches (csrc/lss_pool.hip)
 LSS_SIGNATURES = {
@@ -222,30 +220,36 @@ LSS_SIGNATURES = {
     "coalign_lss_depth_prob": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "coalign_lss_pool": (c_int, [P, P, c_int, c_int, c_int, P, c_int, P, c_int, P, c_int, P, P]),
 }
-LSS_HEADER = _build.LSS_HEADER
 
-# csrc/coalign_amd_lss_bev.h (build.LSS_BEV_HEADER): the fifteenth extension header of ABI version 2 (product library): the camera model's BEV encoder -- the 7 x 7 /
+# include/coalign_amd_lss_bev.h: extension header of ABI version 2 (product library): the camera model's BEV encoder -- the 7 x 7 /
 # stride-2 stem and the bilinear x 2 up-sampling with concatenation, both writing a SplitMap (csrc/lss_bev.hip)
 LSS_BEV_SIGNATURES = {
     "coalign_conv7x7_s2_weight_bytes": (c_size_t, [c_int]),
     "coalign_conv7x7_s2_sp": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "coalign_up2x_concat_sp": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
 }
-LSS_BEV_HEADER = _build.LSS_BEV_HEADER
 
-# header under include/ -> its table, in the order of the ABI's growth: what both loaders bind (coalign_amd_lab.h's LAB_SIGNATURES: the laboratory library alone)
-HEADERS = dict(zip(_build.ABI_HEADERS[:-1], (SIGNATURES, NARROW_SIGNATURES, NARROW_SPARSE_SIGNATURES, ALIGN_SIGNATURES, STAGE1_SIGNATURES, DISCO_SIGNATURES, V2V_SIGNATURES,
-                                             V2X_SIGNATURES, V2X_WINDOW_SIGNATURES, W2C_SIGNATURES, V2VR_SIGNATURES, W2COMM_SIGNATURES)))
+# header under include/ -> its table, in the order of the ABI's growth (build.ABI_HEADERS without its last): what both loaders bind.  coalign_amd_lab.h's
+# LAB_SIGNATURES: the laboratory library alone.
+HEADERS = {
+    "coalign_amd.h": SIGNATURES,
+    "coalign_amd_narrow.h": NARROW_SIGNATURES,
+    "coalign_amd_narrow_sparse.h": NARROW_SPARSE_SIGNATURES,
+    "coalign_amd_align.h": ALIGN_SIGNATURES,
+    "coalign_amd_stage1.h": STAGE1_SIGNATURES,
+    "coalign_amd_disco.h": DISCO_SIGNATURES,
+    "coalign_amd_v2v.h": V2V_SIGNATURES,
+    "coalign_amd_v2x.h": V2X_SIGNATURES,
+    "coalign_amd_v2x_window.h": V2X_WINDOW_SIGNATURES,
+    "coalign_amd_w2c.h": W2C_SIGNATURES,
+    "coalign_amd_v2v_robust.h": V2VR_SIGNATURES,
+    "coalign_amd_where2comm.h": W2COMM_SIGNATURES,
+    "coalign_amd_where2comm_msg.h": W2COMM_MSG_SIGNATURES,
+    "coalign_amd_v2x_ffn.h": V2X_FFN_SIGNATURES,
+    "coalign_amd_lss.h": LSS_SIGNATURES,
+    "coalign_amd_lss_bev.h": LSS_BEV_SIGNATURES,
+}
 _LAB_LIB = None
-
-
-def _bind(handle: ctypes.CDLL, tables) -> ctypes.CDLL:
-    for table in tables:
-        for name, (res, args) in table.items():
-            fn = getattr(handle, name)  # AttributeError here == header / library mismatch
-            fn.restype = res
-            fn.argtypes = args
-    return handle
 
 
 class CoalignHipError(RuntimeError):
@@ -256,21 +260,31 @@ def lib_path() -> str:
     return _build.LIB_PATH
 
 
+def _load(path: str, tables, no_fallback: str = "") -> ctypes.CDLL:
+    """dlopen ``path``, building it first if it is missing, and give every name of ``tables`` its types."""
+    import torch  # noqa: F401  -- load PyTorch-ROCm's HIP runtime first so both share one libamdhip64.so.7
+    if not os.path.exists(path):
+        try:
+            _build.build(lab=path != _build.LIB_PATH, vectorize=path == _build.LABVEC_LIB_PATH)
+        except Exception as exc:  # noqa: BLE001
+            raise CoalignHipError(f"{path} is missing and could not be built ({exc}){no_fallback}") from exc
+    handle = ctypes.CDLL(path)
+    for table in tables:
+        for name, (res, args) in table.items():
+            fn = getattr(handle, name)  # AttributeError here == header / library mismatch
+            fn.restype = res
+            fn.argtypes = args
+    return handle
+
+
 def lib() -> ctypes.CDLL:
     """Load (building first if needed) the gfx950 library.  Raises if that is impossible."""
     global _LIB
     if _LIB is not None:
         return _LIB
-    import torch  # noqa: F401  -- load PyTorch-ROCm's HIP runtime first so both share one libamdhip64.so.7
     lab = os.environ.get("COALIGN_LAB", "0")             # tools/ only: "1" = the laboratory build with its ablation switches, "vec" = + packed fp32 allowed (build.py)
     path = _build.LABVEC_LIB_PATH if lab == "vec" else _build.LAB_LIB_PATH if lab == "1" else _build.LIB_PATH
-    if not os.path.exists(path):
-        try:
-            _build.build(lab=lab == "1", vectorize=lab == "vec")
-        except Exception as exc:  # noqa: BLE001
-            raise CoalignHipError(
-                f"{path} is missing and could not be built ({exc}); the CoAlign hot path has no CPU fallback") from exc
-    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), W2COMM_MSG_SIGNATURES, V2X_FFN_SIGNATURES, LSS_SIGNATURES, LSS_BEV_SIGNATURES])
+    handle = _load(path, HEADERS.values(), "; the CoAlign hot path has no CPU fallback")
     if handle.coalign_abi_version() != 2:
         raise CoalignHipError(f"ABI version mismatch: library reports {handle.coalign_abi_version()}, binding expects 2")
     _LIB = handle
@@ -281,18 +295,9 @@ def lab_lib() -> ctypes.CDLL:
     """The laboratory library (product sources + -DCOALIGN_LAB + include/coalign_amd_lab.h's kernels), loaded beside the product library: the Winograd tests
     and tools call through it; nothing in the detector's default routes does."""
     global _LAB_LIB
-    if _LAB_LIB is not None:
-        return _LAB_LIB
-    import torch  # noqa: F401
-    path = _build.LAB_LIB_PATH
-    if not os.path.exists(path):
-        try:
-            _build.build(lab=True)
-        except Exception as exc:  # noqa: BLE001
-            raise CoalignHipError(f"{path} is missing and could not be built ({exc})") from exc
-    handle = _bind(ctypes.CDLL(path), [*HEADERS.values(), W2COMM_MSG_SIGNATURES, V2X_FFN_SIGNATURES, LSS_SIGNATURES, LAB_SIGNATURES, LSS_BEV_SIGNATURES])
-    _LAB_LIB = handle
-    return handle
+    if _LAB_LIB is None:
+        _LAB_LIB = _load(_build.LAB_LIB_PATH, [*HEADERS.values(), LAB_SIGNATURES])
+    return _LAB_LIB
 
 
 def check(status: int, what: str) -> None:

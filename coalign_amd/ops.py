@@ -1799,7 +1799,7 @@ def v2x_window_attention(x: torch.Tensor, params: torch.Tensor, fuse: str) -> to
     return out
 
 
-# ---- V2X-ViT's feed-forward block in one launch (csrc/coalign_amd_v2x_ffn.h, csrc/v2x_ffn.hip) --------------------------------------------------------------
+# ---- V2X-ViT's feed-forward block in one launch (include/coalign_amd_v2x_ffn.h, csrc/v2x_ffn.hip) --------------------------------------------------------------
 V2X_FFN_MAX_HIDDEN = 512      # COALIGN_V2X_FFN_MAX_HIDDEN
 
 
@@ -2115,7 +2115,7 @@ def w2comm_fuse_nhwc(xs: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], 
     return outs
 
 
-# ---- Where2comm's messages (csrc/coalign_amd_where2comm_msg.h, csrc/w2comm_msg.hip) -------------------------------------------------------------------------------
+# ---- Where2comm's messages (include/coalign_amd_where2comm_msg.h, csrc/w2comm_msg.hip) -------------------------------------------------------------------------------
 W2COMM_SRC_DENSE, W2COMM_SRC_PACKED = 0, 1
 
 
@@ -2247,7 +2247,7 @@ def w2comm_fuse_packed(sources: Sequence[Sequence[tuple]], shapes: Sequence[Tupl
     return outs
 
 
-# ---- Lift-Splat's frustum pooling for the camera model (csrc/coalign_amd_lss.h, csrc/lss_pool.hip) --------------------------------------------------------------
+# ---- Lift-Splat's frustum pooling for the camera model (include/coalign_amd_lss.h, csrc/lss_pool.hip) --------------------------------------------------------------
 LSS_CHUNK = 512               # COALIGN_LSS_CHUNK
 LSS_MAX_DEPTH = 128           # COALIGN_LSS_MAX_DEPTH
 
@@ -2374,7 +2374,7 @@ def lss_pool(depth_logit: torch.Tensor, x_img: torch.Tensor, index: LiftSplatInd
     return out
 
 
-# ---- the camera model's BEV encoder (csrc/coalign_amd_lss_bev.h, csrc/lss_bev.hip) ---------------------------------------------------------------------------
+# ---- the camera model's BEV encoder (include/coalign_amd_lss_bev.h, csrc/lss_bev.hip) ---------------------------------------------------------------------------
 CONV7X7_COUT = 64             # COALIGN_CONV7X7_COUT
 CONV7X7_MAX_CIN = 512         # COALIGN_CONV7X7_MAX_CIN
 
@@ -2385,7 +2385,7 @@ def conv7x7_s2_shape_ok(cin: int, cout: int = CONV7X7_COUT) -> bool:
 
 
 def pack_conv7x7_s2_weight(weight: torch.Tensor) -> torch.Tensor:
-    """[64, Cin, 7, 7] fp32 (Cin % 16 == 0, 16 <= Cin <= 512) -> the weight image of ``coalign_conv7x7_s2_sp`` as uint8 (csrc/coalign_amd_lss_bev.h (18a)):
+    """[64, Cin, 7, 7] fp32 (Cin % 16 == 0, 16 <= Cin <= 512) -> the weight image of ``coalign_conv7x7_s2_sp`` as uint8 (include/coalign_amd_lss_bev.h (18a)):
     [Cin / 16][7 ky][7 kx][2 terms][2 channel halves][64 cout][8 cin] fp16 sp16 pairs of the per-output-channel scaled weights (the scaling and rounding of
     ``pack_conv3x3_emu_weight``'s terms-16 image), 16 zero bytes, [64] float32 2^-k_c, [64] float32 2^k_c."""
     co, ci, kh, kw = weight.shape
@@ -2409,7 +2409,7 @@ def pack_conv7x7_s2_weight(weight: torch.Tensor) -> torch.Tensor:
 
 @_device_op
 def conv7x7_s2_sp(x: torch.Tensor, image: torch.Tensor, bias: torch.Tensor, relu: bool = True) -> "SplitMap":
-    """y = act(conv7x7(x, w, stride 2, padding 3) + bias) with 64 output channels, written as a ``SplitMap`` (csrc/coalign_amd_lss_bev.h (18b)): the stem of
+    """y = act(conv7x7(x, w, stride 2, padding 3) + bias) with 64 output channels, written as a ``SplitMap`` (include/coalign_amd_lss_bev.h (18b)): the stem of
     ``lss.BevEncodeMSFusion``.  ``x``: float32 of logical shape [N, C, H, W], read in place when its memory is channels-last (what ``lss_pool`` writes), converted
     by torch first when it is NCHW; ``image``: ``pack_conv7x7_s2_weight``; ``bias`` [64]."""
     _need_gpu(x, image, bias)
@@ -2431,7 +2431,7 @@ def conv7x7_s2_sp(x: torch.Tensor, image: torch.Tensor, bias: torch.Tensor, relu
 
 @_device_op
 def up2x_concat_sp(skip: torch.Tensor, low: torch.Tensor) -> "SplitMap":
-    """SplitMap of ``cat([skip, up(low)], dim=1)``, ``up`` = bilinear x 2 with ``align_corners=True``, in one pass (csrc/coalign_amd_lss_bev.h (18c)): ``lss.Up``
+    """SplitMap of ``cat([skip, up(low)], dim=1)``, ``up`` = bilinear x 2 with ``align_corners=True``, in one pass (include/coalign_amd_lss_bev.h (18c)): ``lss.Up``
     up to its convolutions.  ``skip`` [N, Cs, 2h, 2w], ``low`` [N, Cl, h, w], float32, read in place when channels-last, converted by torch first when NCHW."""
     _need_gpu(skip, low)
     if skip.dim() != 4 or low.dim() != 4:

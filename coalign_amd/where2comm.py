@@ -11,7 +11,7 @@ masks of all levels and the rates) and ``ops.w2comm_fuse_nhwc`` (warp and fusion
 ``wire="packed"`` (off by default; ``PointPillarWhere2comm.packed_wire``) fuses from MESSAGES instead of the agents' dense maps: every non-ego agent's masked pixels
 are packed (``W2Message``: a bitmap and the masked pixels' rows per level, ``ops.w2comm_msg_index`` + ``ops.w2comm_msg_pack``) and ``ops.w2comm_fuse_packed`` reads the
 ego's dense maps and the others' messages -- to the same values as the dense route.  The reference has no counterpart; the format is stated in
-csrc/coalign_amd_where2comm_msg.h and, op by op, by ``pack_messages_torch``.
+include/coalign_amd_where2comm_msg.h and, op by op, by ``pack_messages_torch``.
 
 Quirks of the reference that are kept: the masks of the agents with an even index inside their frame are all ones
 (``communication_mask_nodiag[::2] = 1``, where2comm.py:71), the rate counts the ego's mask before that; single-scale mode masks every agent of frame b with the
@@ -151,7 +151,7 @@ def rank_torch(bits: torch.Tensor, W: int):
 
 
 class W2Message:
-    """What ONE agent transmits (csrc/coalign_amd_where2comm_msg.h states the format and the wire layout).  Per level l: ``shapes[l]`` = (C, H, W), ``bits[l]`` int32
+    """What ONE agent transmits (include/coalign_amd_where2comm_msg.h states the format and the wire layout).  Per level l: ``shapes[l]`` = (C, H, W), ``bits[l]`` int32
     [H, ceil(W / 32)] (the uint32 words' bit patterns), ``rows[l]`` float32 [max(1, H W), C] whose first K_l rows are the masked pixels in raster order, ``count``
     int32 [levels] ON THE DEVICE, and ``rank[l]`` int32 [H, Wd], which sender and receiver each compute and which does not travel.  Everything has a static shape;
     nothing here reads a count back except ``counts`` / ``nbytes`` / ``to_wire``, on demand."""

@@ -1,11 +1,8 @@
 /* Extension header of ABI version 2 (include/coalign_amd.h keeps its 68 entry points, the thirteen earlier extension headers their 2 / 1 / 4 / 3 / 2 / 3 / 3 / 3 /
  * 3 / 7 / 2 / 3 / 2): Lift-Splat's frustum pooling -- the step of the camera model that turns per-camera image features and depth logits into the BEV map the
- * fusion families read.  Part of the product library libcoalign_hip.so; same conventions as csrc/coalign_amd_v2x_ffn.h (status codes, every shape / pointer /
+ * fusion families read.  Part of the product library libcoalign_hip.so; same conventions as include/coalign_amd_v2x_ffn.h (status codes, every shape / pointer /
  * alignment check before any HIP call, everything on the caller's stream, no allocation, no workspace: safe inside a captured graph; no float atomics: the same
  * input gives the same bits).
- *
- * This header lies beside the sources, not under include/, for the reason csrc/coalign_amd_where2comm_msg.h gives: the tests of the earlier headers count the
- * files of include/.  It is bound like the others (coalign_amd.hip.LSS_SIGNATURES, hip.LSS_HEADER).
  *
  * The reference materialises depth x features ([A N, C, D, fH, fW], lss_submodule.py:134-136), sorts every frustum point by its voxel and takes differences of a
  * running sum (lift_splat_shoot.py:116-169).  Here the voxel of a point is computed once per camera rig (17a); the host turns those cells into an inverted index

@@ -2,11 +2,8 @@
  * 3 / 7 / 2 / 3 / 2 / 3): the two operations of the camera model's BEV encoder (BevEncodeMSFusion, opencood/models/sub_modules/lss_submodule.py:357-417) that
  * had no kernel -- the 7 x 7 / stride-2 stem and the bilinear x 2 up-sampling with concatenation of `Up` -- both writing a SplitMap (include/coalign_amd.h (9e)),
  * so that every 3 x 3 convolution behind them runs on coalign_conv3x3_sp / coalign_conv3x3_sp_s2.  Part of the product library libcoalign_hip.so; same
- * conventions as csrc/coalign_amd_lss.h (status codes, every shape / pointer / alignment check before any HIP call, everything on the caller's stream, no
+ * conventions as include/coalign_amd_lss.h (status codes, every shape / pointer / alignment check before any HIP call, everything on the caller's stream, no
  * allocation, no workspace: safe inside a captured graph; a fixed summation order: the same input gives the same bits).
- *
- * This header lies beside the sources, not under include/, for the reason csrc/coalign_amd_where2comm_msg.h gives: the tests of the earlier headers count the
- * files of include/.  It is bound like the others (coalign_amd.hip.LSS_BEV_SIGNATURES, hip.LSS_BEV_HEADER).
  *
  * SplitMap [N, C, H, W]: fp16 [N][C / 16][4 planes][H][W][8], plane = 2 * (8-channel half) + term, term 0 = h, term 1 = l' of the sp16 pair (csrc/common.h).
  * Both kernels OR bit 0 into *range_flag (may be NULL) when a value they store exceeds the pair's range (|y| > 65504). */

@@ -1,10 +1,7 @@
 /* Extension header of ABI version 2 (include/coalign_amd.h keeps its 68 entry points, the twelve earlier extension headers their 2 / 1 / 4 / 3 / 2 / 3 / 3 / 3 / 3 /
  * 7 / 2 / 3): the feed-forward block of V2X-ViT's encoder layers, x + FeedForward(LayerNorm(x)), in ONE launch.  Part of the product library libcoalign_hip.so; same
  * conventions as include/coalign_amd_v2x_window.h (status codes, every shape / pointer check before any HIP call, everything on the caller's stream, no allocation,
- * no workspace: safe inside a captured graph; no atomics: the same input gives the same bits).
- *
- * This header lies beside the sources, not under include/, for the reason csrc/coalign_amd_where2comm_msg.h gives: the tests of the earlier headers count the
- * files of include/.  It is bound like the others (coalign_amd.hip.V2X_FFN_SIGNATURES, hip.FFN_HEADER). */
+ * no workspace: safe inside a captured graph; no atomics: the same input gives the same bits). */
 #ifndef COALIGN_AMD_V2X_FFN_H
 #define COALIGN_AMD_V2X_FFN_H
 

@@ -3,9 +3,6 @@
  * libcoalign_hip.so; same conventions as include/coalign_amd_where2comm.h (status codes, every shape / pointer check before any HIP call, everything on the
  * caller's stream, no allocation, no host read-back: safe inside a captured graph; the same input gives the same bits).
  *
- * This header lies beside the sources, not under include/: the test of the eleventh header (tests/test_where2comm_cpu.py) counts the files of include/ and allows
- * twelve beside its own.  It is bound like the others (coalign_amd.hip.W2COMM_MSG_SIGNATURES, hip.MSG_HEADER).
- *
  * THE REFERENCE HAS NO COUNTERPART of any of this: its Communication (opencood/models/comm_modules/where2comm.py:9-78) and Where2comm
  * (opencood/models/fuse_modules/where2comm_attn.py:224-341) multiply dense maps by masks and stop there.  The format is this project's.
  *

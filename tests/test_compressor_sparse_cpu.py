@@ -12,6 +12,7 @@ import re
 
 import pytest
 
+import abi_headers
 from coalign_amd import backbone as bb
 from coalign_amd import detector, hip
 from coalign_amd.config import builtin_config
@@ -21,22 +22,9 @@ from coalign_amd.routes import COMPRESSOR_LIBRARY, NARROW, SP, plan
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, ONE = ctypes.c_void_p(0), ctypes.c_void_p(16)      # (a non-NULL, 16-byte aligned token: none of the calls below gets as far as touching memory)
 HW = 8
+HEADER = "coalign_amd_narrow_sparse.h"
 NAME = "coalign_conv3x3_sp_narrow_sparse"
 ENCODER, PILLAR_SPARSE, PILLAR_DENSE = "naive_compressor.encoder.0", "sparse canvas read by the compressor's encoder", "persistent dense canvas"
-
-
-def _declarations(header):
-    """name -> (return type, [argument types]) of every prototype of the header, comments removed."""
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"\b(int|size_t)\s+(coalign_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        out[name] = (ret, [re.sub(r"\s*\w+$", "", a.strip()).replace(" ", "") for a in args.split(",")] if args.strip() != "void" else [])
-    return out
-
-
-def _names(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-    return set(re.findall(r"\b(coalign_[a-z0-9_]+)\s*\(", text))
 
 
 def _call(cin=64, cout=16, n=0, rows=ONE, m=4, stamps=ONE, state=ONE, w=ONE, bias=ONE, y=ONE, h=HW, wd=HW):
@@ -45,20 +33,18 @@ def _call(cin=64, cout=16, n=0, rows=ONE, m=4, stamps=ONE, state=ONE, w=ONE, bia
 
 def test_third_extension_header_table_and_library_agree():
     """include/coalign_amd_narrow_sparse.h declares exactly one name; the product library exports it; it equals ``hip.NARROW_SPARSE_SIGNATURES``, argument types
-    included; the declaration's comment cites naive_compress.py:5-31; the two older headers keep their 68 and 2 names and share none with it."""
-    decl = _declarations("coalign_amd_narrow_sparse.h")
-    assert set(decl) == _names("coalign_amd_narrow_sparse.h") == set(hip.NARROW_SPARSE_SIGNATURES) == {NAME}
+    included (``const int32_t *`` is a device buffer here: its own mapping, not the rule of tests/abi_headers.py); the declaration's comment cites
+    naive_compress.py:5-31."""
+    decl = abi_headers.declarations(HEADER)
+    assert set(decl) == abi_headers.names(HEADER) == set(hip.NARROW_SPARSE_SIGNATURES) == {NAME}
     ctype = {"int": ctypes.c_int, "constvoid*": ctypes.c_void_p, "void*": ctypes.c_void_p, "constint32_t*": ctypes.c_void_p, "int32_t*": ctypes.c_void_p,
              "constfloat*": ctypes.c_void_p}
     ret, args = decl[NAME]
-    assert ret == "int" and hip.NARROW_SPARSE_SIGNATURES[NAME] == (ctypes.c_int, [ctype[a] for a in args]) and len(args) == 15
+    args = [re.sub(r"\s*\w+$", "", a).replace(" ", "") for a in args]                              # "const int32_t *stamps" -> "constint32_t*"
+    assert ret is ctypes.c_int and hip.NARROW_SPARSE_SIGNATURES[NAME] == (ctypes.c_int, [ctype[a] for a in args]) and len(args) == 15
     fn = getattr(hip.lib(), NAME)
     assert fn.restype is ctypes.c_int and list(fn.argtypes) == hip.NARROW_SPARSE_SIGNATURES[NAME][1]
-    old, narrow = _names("coalign_amd.h"), _names("coalign_amd_narrow.h")
-    assert len(old) == 68 and len(narrow) == 2 and narrow == set(hip.NARROW_SIGNATURES)
-    assert NAME not in old and NAME not in narrow and NAME not in hip.SIGNATURES and NAME not in hip.ALIGN_SIGNATURES
-    assert hip.lib().coalign_abi_version() == 2
-    text = open(os.path.join(REPO, "include", "coalign_amd_narrow_sparse.h")).read()
+    text = open(abi_headers.path(HEADER)).read()
     assert '#include "coalign_amd.h"' in text
     comments = re.findall(r"/\*.*?\*/", text, flags=re.S)
     last = [c for c in comments if c in text[:text.index(NAME + "(")]][-1]

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_headers
 from conftest import assert_elementwise
 from coalign_amd import hip, ops
 from coalign_amd.config import builtin_config
@@ -19,49 +20,17 @@ from disco_reference import assert_not_degenerate, disco_fuse_f64
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, ONE = ctypes.c_void_p(0), ctypes.c_void_p(16)      # (a non-NULL, 16-byte aligned token: none of these calls gets as far as touching memory)
-C_TYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
 HEADER = "coalign_amd_disco.h"
 CONFIGS = ("opv2v_pointpillar_disconet", "mini_pointpillar_disconet")
 
 
-def _names(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-    return set(re.findall(r"\b(coalign_[a-z0-9_]+)\s*\(", text))
-
-
-def _declarations(header):
-    """name -> (restype, [argtypes]) parsed from the header's prototypes (every pointer crosses the ABI as ``hip.P``)."""
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"\b(int|size_t)\s+(coalign_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        argtypes = []
-        for a in [a.strip() for a in args.split(",")]:
-            if a == "void":
-                continue
-            argtypes.append(hip.P if "*" in a else C_TYPES[a.split()[-2] if len(a.split()) > 1 else a])
-        out[name] = (C_TYPES[ret], argtypes)
-    return out
-
-
 def test_disco_header_table_and_library_agree():
-    """Every name of include/coalign_amd_disco.h is exported by the product library and equals ``hip.DISCO_SIGNATURES``, return and argument types included; the
-    header includes coalign_amd.h and cites the reference lines each entry point replaces; the frozen headers still declare 68 / 2 / 1 / 4 / 3 names; ABI version 2."""
-    text = open(os.path.join(REPO, "include", HEADER)).read()
+    """include/coalign_amd_disco.h declares exactly the keys of ``hip.DISCO_SIGNATURES`` (types, counts and exports: tests/test_abi_cpu.py); the header includes
+    coalign_amd.h and cites the reference lines each entry point replaces."""
+    text = open(abi_headers.path(HEADER)).read()
     assert '#include "coalign_amd.h"' in text
-    declared = _declarations(HEADER)
-    assert set(declared) == set(hip.DISCO_SIGNATURES) == _names(HEADER) and len(declared) == 2
-    lib = hip.lib()
-    for name, (res, args) in declared.items():
-        fn = getattr(lib, name)
-        assert hip.DISCO_SIGNATURES[name][0] is res and hip.DISCO_SIGNATURES[name][1] == args, name
-        assert fn.restype is res and list(fn.argtypes) == args, name
-    frozen = {"coalign_amd.h": (68, hip.SIGNATURES), "coalign_amd_narrow.h": (2, hip.NARROW_SIGNATURES), "coalign_amd_narrow_sparse.h": (1, hip.NARROW_SPARSE_SIGNATURES),
-              "coalign_amd_align.h": (4, hip.ALIGN_SIGNATURES), "coalign_amd_stage1.h": (3, hip.STAGE1_SIGNATURES)}
-    for header, (count, table) in frozen.items():
-        names = _names(header)
-        assert len(names) == count and names == set(table), header
-        assert not (set(declared) & names), header
-    assert lib.coalign_abi_version() == 2
+    declared = abi_headers.declarations(HEADER)
+    assert set(declared) == set(hip.DISCO_SIGNATURES) == abi_headers.names(HEADER) and len(declared) == 2
     comments = re.findall(r"/\*.*?\*/", text, flags=re.S)
     for name in declared:
         last = [c for c in comments if c in text[:text.index(name + "(")]][-1]

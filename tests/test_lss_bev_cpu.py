@@ -1,4 +1,4 @@
-"""The camera model's BEV encoder on kernels, the part that needs no GPU: csrc/coalign_amd_lss_bev.h against the product library and ``hip.LSS_BEV_SIGNATURES``,
+"""The camera model's BEV encoder on kernels, the part that needs no GPU: include/coalign_amd_lss_bev.h against the product library and ``hip.LSS_BEV_SIGNATURES``,
 argument refusals before any HIP call, ``ops.pack_conv7x7_s2_weight`` against a restatement of the image from its documented layout, the route predicate of
 ``lss.BevEncodeMSFusion`` on both sides, the switch (off: today's forward, bit for bit) and ``plan()`` for the two shipped camera configs."""
 import ctypes
@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import abi_headers
 from coalign_amd import backbone, build, hip, lss, ops
 from coalign_amd.config import builtin_config
 from coalign_amd.detector import build_model
@@ -18,56 +19,25 @@ from coalign_amd.synthetic import fill_parameters_, make_camera_frame
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, ONE = ctypes.c_void_p(0), ctypes.c_void_p(16)      # (a non-NULL, aligned token: none of these calls gets as far as touching memory)
-C_TYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+HEADER = "coalign_amd_lss_bev.h"
 NAMES = {"coalign_conv7x7_s2_weight_bytes", "coalign_conv7x7_s2_sp", "coalign_up2x_concat_sp"}
 STEM_CITES = ("lss_submodule.py:19-38, 369-372, 402-404",)
 
 
-def _text(path):      # (copied from tests/test_lss_cpu.py, as are the two below)
-    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-
-
-def _names(path):
-    return set(re.findall(r"\b(coalign_[a-z0-9_]+)\s*\(", _text(path)))
-
-
-def _declarations(path):
-    out = {}
-    for ret, name, a in re.findall(r"\b(int|size_t)\s+(coalign_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _text(path)):
-        out[name] = (C_TYPES[ret], [hip.P if "*" in p else C_TYPES[p.split()[-2]] for p in [p.strip() for p in a.split(",")] if p != "void"])
-    return out
-
-
 # ---- the ABI --------------------------------------------------------------------------------------------------------------------------------------------------
 def test_lss_bev_header_table_and_library_agree():
-    """Every name of the header is exported by the product library and equals ``hip.LSS_BEV_SIGNATURES``, types included; every declaration's comment cites the
-    reference lines it replaces; include/ still has 13 files, none of which declares these names; ABI version 2; both loaders bind the table behind the earlier
-    ones; build.py lists the source; the source reads no environment variable."""
-    assert hip.LSS_BEV_HEADER == build.LSS_BEV_HEADER == os.path.join(REPO, "coalign_amd", "csrc", "coalign_amd_lss_bev.h")
-    text = open(hip.LSS_BEV_HEADER).read()
+    """The header declares exactly ``NAMES``, the keys of ``hip.LSS_BEV_SIGNATURES`` (types, counts and exports: tests/test_abi_cpu.py); every declaration's comment
+    cites the reference lines it replaces; build.py lists the source; the source reads no environment variable."""
+    text = open(abi_headers.path(HEADER)).read()
     assert '#include "coalign_amd.h"' in text
-    declared = _declarations(hip.LSS_BEV_HEADER)
-    assert set(declared) == set(hip.LSS_BEV_SIGNATURES) == _names(hip.LSS_BEV_HEADER) == NAMES
-    lib = hip.lib()
-    for name, (res, a) in declared.items():
-        fn = getattr(lib, name)
-        assert hip.LSS_BEV_SIGNATURES[name][0] is res and hip.LSS_BEV_SIGNATURES[name][1] == a, name
-        assert fn.restype is res and list(fn.argtypes) == a, name
+    declared = abi_headers.declarations(HEADER)
+    assert set(declared) == set(hip.LSS_BEV_SIGNATURES) == abi_headers.names(HEADER) == NAMES
     comments = re.findall(r"/\*.*?\*/", text, flags=re.S)
     cites = {"coalign_conv7x7_s2_weight_bytes": STEM_CITES, "coalign_conv7x7_s2_sp": STEM_CITES,
              "coalign_up2x_concat_sp": STEM_CITES + ("lss_submodule.py:23-24", "nn.Upsample(scale_factor=2, mode='bilinear', align_corners=True)")}
     for name in declared:
         last = [c for c in comments if c in text[:text.index(name + "(")]][-1]
         assert all(c in last for c in cites[name]), name
-    headers = sorted(os.listdir(os.path.join(REPO, "include")))
-    assert len(headers) == 13 and sorted(build.ABI_HEADERS) == headers
-    for header in headers + [os.path.basename(build.LSS_HEADER), os.path.basename(build.FFN_HEADER), os.path.basename(build.MSG_HEADER)]:
-        path = os.path.join(REPO, "include", header) if header in headers else os.path.join(REPO, "coalign_amd", "csrc", header)
-        assert not (NAMES & _names(path)), header
-    assert lib.coalign_abi_version() == 2
-    src = open(os.path.join(REPO, "coalign_amd", "hip.py")).read()
-    assert src.count("W2COMM_MSG_SIGNATURES, V2X_FFN_SIGNATURES, LSS_SIGNATURES") == 2          # the earlier tables, untouched ...
-    assert src.count("LSS_BEV_SIGNATURES])") == 2                                                # ... and this one at the END of both lists (lib() and lab_lib())
     assert '"lss_bev.hip"' in open(os.path.join(REPO, "coalign_amd", "build.py")).read() and "lss_bev.hip" in build.SOURCES
     assert int(re.search(r"#define COALIGN_CONV7X7_MAX_CIN (\d+)", text).group(1)) == ops.CONV7X7_MAX_CIN >= 256
     assert int(re.search(r"#define COALIGN_CONV7X7_COUT (\d+)", text).group(1)) == ops.CONV7X7_COUT == 64

@@ -1,6 +1,6 @@
 """Lift-Splat's frustum pooling and the camera model, host side (no GPU): the float64 restatement of tests/lss_reference.py against the fixture made from the
 reference (tests/golden/make_lss_golden.py), ``LiftSplat``'s torch routes against the restatement, the properties of the inverted index, the extension header
-csrc/coalign_amd_lss.h against the product library and ``hip.LSS_SIGNATURES``, argument refusals before any HIP call, the switch, the yaml parser and
+include/coalign_amd_lss.h against the product library and ``hip.LSS_SIGNATURES``, argument refusals before any HIP call, the switch, the yaml parser and
 ``build_model`` of the camera configs with a forward through the torch route."""
 import ctypes
 import os
@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_headers
 from conftest import assert_elementwise
 from coalign_amd import build, hip, lss, ops
 from coalign_amd.config import YAML_PARSERS, builtin_config
@@ -19,24 +20,9 @@ import lss_reference as R
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, ONE, TWO = ctypes.c_void_p(0), ctypes.c_void_p(16), ctypes.c_void_p(1 << 20)      # (non-NULL, aligned tokens: none of these calls gets as far as touching memory)
-C_TYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+HEADER = "coalign_amd_lss.h"
 NAMES = {"coalign_lss_cells", "coalign_lss_depth_prob", "coalign_lss_pool"}
 NZ1 = ((-4.0, 4.8, 0.4), (-3.2, 3.2, 0.4), (-10, 10, 20.0), (2, 12, 6))
-
-
-def _text(path):
-    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-
-
-def _names(path):
-    return set(re.findall(r"\b(coalign_[a-z0-9_]+)\s*\(", _text(path)))
-
-
-def _declarations(path):
-    out = {}
-    for ret, name, a in re.findall(r"\b(int|size_t)\s+(coalign_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _text(path)):
-        out[name] = (C_TYPES[ret], [hip.P if "*" in p else C_TYPES[p.split()[-2]] for p in [p.strip() for p in a.split(",")] if p != "void"])
-    return out
 
 
 # ---- the restatement against the reference ------------------------------------------------------------------------------------------------------------------
@@ -183,19 +169,12 @@ def test_index_cache_follows_the_rig():
 
 # ---- header, table, library ------------------------------------------------------------------------------------------------------------------------------
 def test_lss_header_table_and_library_agree():
-    """Every name of the header is exported by the product library and equals ``hip.LSS_SIGNATURES``, types included; every declaration's comment cites the
-    reference lines it replaces; include/ still has 13 files, none of which declares these names; ABI version 2; both loaders bind the table; build.py lists
-    the source; the source reads no environment variable."""
-    assert hip.LSS_HEADER == build.LSS_HEADER == os.path.join(REPO, "coalign_amd", "csrc", "coalign_amd_lss.h")
-    text = open(hip.LSS_HEADER).read()
+    """The header declares exactly ``NAMES``, the keys of ``hip.LSS_SIGNATURES`` (types, counts and exports: tests/test_abi_cpu.py); every declaration's comment
+    cites the reference lines it replaces; build.py lists the source; the source reads no environment variable."""
+    text = open(abi_headers.path(HEADER)).read()
     assert '#include "coalign_amd.h"' in text
-    declared = _declarations(hip.LSS_HEADER)
-    assert set(declared) == set(hip.LSS_SIGNATURES) == _names(hip.LSS_HEADER) == NAMES
-    lib = hip.lib()
-    for name, (res, a) in declared.items():
-        fn = getattr(lib, name)
-        assert hip.LSS_SIGNATURES[name][0] is res and hip.LSS_SIGNATURES[name][1] == a, name
-        assert fn.restype is res and list(fn.argtypes) == a, name
+    declared = abi_headers.declarations(HEADER)
+    assert set(declared) == set(hip.LSS_SIGNATURES) == abi_headers.names(HEADER) == NAMES
     comments = re.findall(r"/\*.*?\*/", text, flags=re.S)
     cites = {"coalign_lss_cells": ("lift_splat_shoot.py:80-102", "lift_splat_shoot.py:65-78", "lift_splat_shoot.py:126", "lift_splat_shoot.py:133-135", "camera_utils.py:129-134",
                                    "camera_utils.py:187-196", "undefined"),
@@ -204,18 +183,11 @@ def test_lss_header_table_and_library_agree():
     for name in declared:
         last = [c for c in comments if c in text[:text.index(name + "(")]][-1]
         assert all(c in last for c in cites[name]), name
-    headers = sorted(os.listdir(os.path.join(REPO, "include")))
-    assert len(headers) == 13 and sorted(build.ABI_HEADERS) == headers
-    for header in headers:
-        assert not (NAMES & _names(os.path.join(REPO, "include", header))), header
-    assert lib.coalign_abi_version() == 2
-    src = open(os.path.join(REPO, "coalign_amd", "hip.py")).read()
-    assert src.count("W2COMM_MSG_SIGNATURES, V2X_FFN_SIGNATURES, LSS_SIGNATURES") == 2          # lib() and lab_lib()
     assert '"lss_pool.hip"' in open(os.path.join(REPO, "coalign_amd", "build.py")).read() and "lss_pool.hip" in build.SOURCES
     assert int(re.search(r"#define COALIGN_LSS_CHUNK (\d+)", text).group(1)) == ops.LSS_CHUNK == 512
     assert int(re.search(r"#define COALIGN_LSS_MAX_DEPTH (\d+)", text).group(1)) == ops.LSS_MAX_DEPTH
     kernel = open(os.path.join(REPO, "coalign_amd", "csrc", "lss_pool.hip")).read()
-    assert "getenv" not in kernel and "lab_env" not in kernel and "atomic" not in _text(os.path.join(REPO, "coalign_amd", "csrc", "lss_pool.hip")).replace("no atomics", "")
+    assert "getenv" not in kernel and "lab_env" not in kernel and "atomic" not in re.sub(r"/\*.*?\*/", "", kernel, flags=re.S).replace("no atomics", "")
     for k in ("lss_cells", "lss_depth_prob", "lss_pool"):
         assert re.search(r"__global__[^\n]*\bvoid " + k + r"\(", kernel), k
 

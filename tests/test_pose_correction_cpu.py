@@ -8,44 +8,30 @@ import types
 import pytest
 import torch
 
+import abi_headers
 from coalign_amd import box_align, hip, inference, ops
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, ONE = ctypes.c_void_p(0), ctypes.c_void_p(16)      # (a non-NULL token: none of these calls gets as far as touching memory)
 
+HEADER = "coalign_amd_align.h"
 C_TYPES = {"int": ctypes.c_int, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
 
 
-def _declarations(header):
-    """name -> (restype, [argtypes]) parsed from the header's prototypes (every pointer crosses the ABI as ``hip.P``)."""
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"\b(int|size_t)\s+(coalign_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        argtypes = []
-        for a in [a.strip() for a in args.split(",")]:
-            if a == "void":
-                continue
-            argtypes.append(hip.P if "*" in a else C_TYPES[a.split()[-2] if len(a.split()) > 1 else a])
-        out[name] = (C_TYPES[ret], argtypes)
-    return out
-
-
 def test_align_header_table_and_library_agree():
-    """Every name of include/coalign_amd_align.h is exported by the product library and equals ``hip.ALIGN_SIGNATURES``, argument types included; the header
-    includes coalign_amd.h and cites the reference lines each entry point replaces; the frozen header still declares 68 names at ABI version 2."""
-    text = open(os.path.join(REPO, "include", "coalign_amd_align.h")).read()
+    """Every name of include/coalign_amd_align.h is exported by the product library and equals ``hip.ALIGN_SIGNATURES``, argument types included (every pointer of
+    this header, host or device, crosses as ``hip.P``: its own mapping, not the rule of tests/abi_headers.py); the header includes coalign_amd.h and cites the
+    reference lines each entry point replaces."""
+    text = open(abi_headers.path(HEADER)).read()
     assert '#include "coalign_amd.h"' in text
-    declared = _declarations("coalign_amd_align.h")
+    declared = abi_headers.declarations(HEADER)
     assert set(declared) == set(hip.ALIGN_SIGNATURES) and len(declared) == 4
     lib = hip.lib()
     for name, (res, args) in declared.items():
+        args = [hip.P if "*" in a else C_TYPES[a.split()[-2]] for a in args]
         fn = getattr(lib, name)
         assert hip.ALIGN_SIGNATURES[name][0] is res and hip.ALIGN_SIGNATURES[name][1] == args, name
         assert fn.restype is res and list(fn.argtypes) == args, name
-    frozen = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "coalign_amd.h")).read(), flags=re.S)
-    frozen = set(re.findall(r"\b(coalign_[a-z0-9_]+)\s*\(", frozen))
-    assert len(frozen) == 68 and not (set(declared) & frozen) and frozen == set(hip.SIGNATURES)
-    assert lib.coalign_abi_version() == 2
     comments = re.findall(r"/\*.*?\*/", text, flags=re.S)
     cites = {"coalign_stage1_gather": "uncertainty_voxel_postprocessor.py:26-112", "coalign_pose_graph_build": "box_align_v2.py:150-372",
              "coalign_pose_correct_matrices": "transformation_utils.py:22-67"}

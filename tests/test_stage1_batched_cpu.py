@@ -7,49 +7,21 @@ import re
 import pytest
 import torch
 
+import abi_headers
 from coalign_amd import hip, ops
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, ONE = ctypes.c_void_p(0), ctypes.c_void_p(16)      # (a non-NULL token: none of these calls gets as far as touching memory)
-C_TYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
 HEADER = "coalign_amd_stage1.h"
 
 
-def _names(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-    return set(re.findall(r"\b(coalign_[a-z0-9_]+)\s*\(", text))
-
-
-def _declarations(header):
-    """name -> (restype, [argtypes]) parsed from the header's prototypes (every pointer crosses the ABI as ``hip.P``)."""
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"\b(int|size_t)\s+(coalign_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        argtypes = []
-        for a in [a.strip() for a in args.split(",")]:
-            if a == "void":
-                continue
-            argtypes.append(hip.P if "*" in a else C_TYPES[a.split()[-2] if len(a.split()) > 1 else a])
-        out[name] = (C_TYPES[ret], argtypes)
-    return out
-
-
 def test_stage1_header_table_and_library_agree():
-    """Every name of include/coalign_amd_stage1.h is exported by the product library and equals ``hip.STAGE1_SIGNATURES``, return and argument types included;
-    the header includes coalign_amd.h and cites the reference lines each entry point replaces; the frozen headers still declare 68 and 4 names."""
-    text = open(os.path.join(REPO, "include", HEADER)).read()
+    """include/coalign_amd_stage1.h declares exactly the keys of ``hip.STAGE1_SIGNATURES`` (types, counts and exports: tests/test_abi_cpu.py); the header includes
+    coalign_amd.h and cites the reference lines each entry point replaces."""
+    text = open(abi_headers.path(HEADER)).read()
     assert '#include "coalign_amd.h"' in text
-    declared = _declarations(HEADER)
-    assert set(declared) == set(hip.STAGE1_SIGNATURES) == _names(HEADER) and len(declared) == 3
-    lib = hip.lib()
-    for name, (res, args) in declared.items():
-        fn = getattr(lib, name)
-        assert hip.STAGE1_SIGNATURES[name][0] is res and hip.STAGE1_SIGNATURES[name][1] == args, name
-        assert fn.restype is res and list(fn.argtypes) == args, name
-    frozen, align = _names("coalign_amd.h"), _names("coalign_amd_align.h")
-    assert len(frozen) == 68 and frozen == set(hip.SIGNATURES) and len(align) == 4 and align == set(hip.ALIGN_SIGNATURES)
-    assert not (set(declared) & (frozen | align))
-    assert lib.coalign_abi_version() == 2
+    declared = abi_headers.declarations(HEADER)
+    assert set(declared) == set(hip.STAGE1_SIGNATURES) == abi_headers.names(HEADER) and len(declared) == 3
     comments = re.findall(r"/\*.*?\*/", text, flags=re.S)
     for name in declared:
         last = [c for c in comments if c in text[:text.index(name + "(")]][-1]

@@ -10,6 +10,7 @@ import re
 import pytest
 import torch
 
+import abi_headers
 from conftest import assert_elementwise
 from coalign_amd import hip, ops
 from coalign_amd.config import builtin_config
@@ -20,46 +21,18 @@ from v2v_reference import assert_not_degenerate, make_thetas, v2v_fuse_f64
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, ONE = ctypes.c_void_p(0), ctypes.c_void_p(16)      # (a non-NULL, 16-byte aligned token: none of these calls gets as far as touching memory)
-C_TYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
 HEADER = "coalign_amd_v2v.h"
 CONFIGS = ("opv2v_pointpillar_v2vnet", "mini_pointpillar_v2vnet")
 GOLDEN_ARGS = {"num_iteration": 2, "in_channels": 16, "gru_flag": True, "agg_operator": "max", "conv_gru": {"H": 9, "W": 14, "num_layers": 1, "kernel_size": [[3, 3]]}}
 
 
-def _text(header):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-
-
-def _names(header):
-    return set(re.findall(r"\b(coalign_[a-z0-9_]+)\s*\(", _text(header)))
-
-
-def _declarations(header):
-    """name -> (restype, [argtypes]) parsed from the header's prototypes (every pointer crosses the ABI as ``hip.P``)."""
-    out = {}
-    for ret, name, args in re.findall(r"\b(int|size_t)\s+(coalign_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _text(header)):
-        out[name] = (C_TYPES[ret], [hip.P if "*" in a else C_TYPES[a.split()[-2]] for a in [a.strip() for a in args.split(",")] if a != "void"])
-    return out
-
-
 def test_v2v_header_table_and_library_agree():
-    """Every name of include/coalign_amd_v2v.h is exported by the product library and equals ``hip.V2V_SIGNATURES``, return and argument types included; the header
-    includes coalign_amd.h and cites the reference lines; the earlier headers still declare 68 / 2 / 1 / 4 / 3 / 2 names; ABI version 2."""
-    text = open(os.path.join(REPO, "include", HEADER)).read()
+    """include/coalign_amd_v2v.h declares exactly the keys of ``hip.V2V_SIGNATURES`` (types, counts and exports: tests/test_abi_cpu.py); the header includes
+    coalign_amd.h and cites the reference lines."""
+    text = open(abi_headers.path(HEADER)).read()
     assert '#include "coalign_amd.h"' in text
-    declared = _declarations(HEADER)
-    assert set(declared) == set(hip.V2V_SIGNATURES) == _names(HEADER) == {"coalign_v2v_warp_split", "coalign_v2v_aggregate", "coalign_v2v_gate"}
-    lib = hip.lib()
-    for name, (res, args) in declared.items():
-        fn = getattr(lib, name)
-        assert hip.V2V_SIGNATURES[name][0] is res and hip.V2V_SIGNATURES[name][1] == args, name
-        assert fn.restype is res and list(fn.argtypes) == args, name
-    frozen = {"coalign_amd.h": (68, hip.SIGNATURES), "coalign_amd_narrow.h": (2, hip.NARROW_SIGNATURES), "coalign_amd_narrow_sparse.h": (1, hip.NARROW_SPARSE_SIGNATURES),
-              "coalign_amd_align.h": (4, hip.ALIGN_SIGNATURES), "coalign_amd_stage1.h": (3, hip.STAGE1_SIGNATURES), "coalign_amd_disco.h": (2, hip.DISCO_SIGNATURES)}
-    for header, (count, table) in frozen.items():
-        names = _names(header)
-        assert len(names) == count and names == set(table) and not (set(declared) & names), header
-    assert lib.coalign_abi_version() == 2
+    declared = abi_headers.declarations(HEADER)
+    assert set(declared) == set(hip.V2V_SIGNATURES) == abi_headers.names(HEADER) == {"coalign_v2v_warp_split", "coalign_v2v_aggregate", "coalign_v2v_gate"}
     comments = re.findall(r"/\*.*?\*/", text, flags=re.S)
     for name in declared:
         last = [c for c in comments if c in text[:text.index(name + "(")]][-1]

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_headers
 from conftest import assert_elementwise
 from coalign_amd import hip, ops, pose, routes, v2v_robust
 from coalign_amd.config import builtin_config
@@ -22,7 +23,6 @@ from v2v_robust_reference import attention_f64, fuse_weight_f64, normalize_f64, 
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, ONE = ctypes.c_void_p(0), ctypes.c_void_p(16)      # (a non-NULL, 16-byte aligned token: none of these calls gets as far as touching memory)
-C_TYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
 HEADER = "coalign_amd_v2v_robust.h"
 NAMES = {"coalign_v2vr_pool_act", "coalign_v2vr_score_head", "coalign_v2vr_pose_head_workspace_bytes", "coalign_v2vr_pose_head", "coalign_v2vr_pairwise",
          "coalign_v2vr_consistency", "coalign_v2vr_aggregate"}
@@ -33,40 +33,12 @@ AFFINE = {"H": 24, "W": 40, "downsample_rate": 2, "discrete_ratio": 0.4}
 GOLDEN_RTOL, GOLDEN_FLOOR = 1e-5, 1e-6
 
 
-def _text(header):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-
-
-def _names(header):
-    return set(re.findall(r"\b(coalign_[a-z0-9_]+)\s*\(", _text(header)))
-
-
-def _declarations(header):
-    out = {}
-    for ret, name, args in re.findall(r"\b(int|size_t)\s+(coalign_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _text(header)):
-        out[name] = (C_TYPES[ret], [hip.P if "*" in a else C_TYPES[a.split()[-2]] for a in [a.strip() for a in args.split(",")] if a != "void"])
-    return out
-
-
 def test_header_table_and_library_agree():
-    """Every name of the tenth extension header is exported by the product library and equals ``hip.V2VR_SIGNATURES``, types included; every declaration's comment
-    cites the reference lines it replaces; the earlier headers keep their names and share none with it; ABI version 2; build.py lists the header and the source."""
-    text = open(os.path.join(REPO, "include", HEADER)).read()
-    declared = _declarations(HEADER)
-    assert set(declared) == set(hip.V2VR_SIGNATURES) == _names(HEADER) == NAMES
-    lib = hip.lib()
-    for name, (res, args) in declared.items():
-        fn = getattr(lib, name)
-        assert hip.V2VR_SIGNATURES[name][0] is res and hip.V2VR_SIGNATURES[name][1] == args, name
-        assert fn.restype is res and list(fn.argtypes) == args, name
-    frozen = {"coalign_amd.h": (68, hip.SIGNATURES), "coalign_amd_narrow.h": (2, hip.NARROW_SIGNATURES), "coalign_amd_narrow_sparse.h": (1, hip.NARROW_SPARSE_SIGNATURES),
-              "coalign_amd_align.h": (4, hip.ALIGN_SIGNATURES), "coalign_amd_stage1.h": (3, hip.STAGE1_SIGNATURES), "coalign_amd_disco.h": (2, hip.DISCO_SIGNATURES),
-              "coalign_amd_v2v.h": (3, hip.V2V_SIGNATURES), "coalign_amd_v2x.h": (3, hip.V2X_SIGNATURES), "coalign_amd_v2x_window.h": (3, hip.V2X_WINDOW_SIGNATURES),
-              "coalign_amd_w2c.h": (3, hip.W2C_SIGNATURES)}
-    for header, (count, table) in frozen.items():
-        names = _names(header)
-        assert len(names) == count and names == set(table) and not (NAMES & names), header
-    assert lib.coalign_abi_version() == 2
+    """The header declares exactly ``NAMES``, the keys of ``hip.V2VR_SIGNATURES`` (types, counts and exports: tests/test_abi_cpu.py); every declaration's comment
+    cites the reference lines it replaces; build.py lists the header and the source."""
+    text = open(abi_headers.path(HEADER)).read()
+    declared = abi_headers.declarations(HEADER)
+    assert set(declared) == set(hip.V2VR_SIGNATURES) == abi_headers.names(HEADER) == NAMES
     comments = re.findall(r"/\*.*?\*/", text, flags=re.S)
     for name in declared:
         last = [c for c in comments if c in text[:text.index(name + "(")]][-1]

@@ -1,4 +1,4 @@
-"""V2X-ViT's feed-forward block, host side (no GPU): the extension header csrc/coalign_amd_v2x_ffn.h against the product library and ``hip.V2X_FFN_SIGNATURES``,
+"""V2X-ViT's feed-forward block, host side (no GPU): the extension header include/coalign_amd_v2x_ffn.h against the product library and ``hip.V2X_FFN_SIGNATURES``,
 argument refusals before any HIP call, the identity of ``v2xvit.feed_forward_reduced`` in float64 against the module and against the float64 restatement of
 tests/v2x_ffn_reference.py, the parameter image decoded lane by lane against a numpy statement of the layout, the packer's static range guarantee, the examination
 that the yardstick SEES the activation, the switch, and the route plan with the switch on and off."""
@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_headers
 from conftest import assert_elementwise
 from coalign_amd import build, hip, ops, routes, v2xvit
 from coalign_amd.config import builtin_config
@@ -22,26 +23,11 @@ from v2xvit_reference import args
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, ONE, TWO = ctypes.c_void_p(0), ctypes.c_void_p(16), ctypes.c_void_p(1 << 20)      # (non-NULL, 16-byte aligned tokens: none of these calls gets as far as touching memory)
-C_TYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+HEADER = "coalign_amd_v2x_ffn.h"
 NAMES = {"coalign_v2x_ffn_param_bytes", "coalign_v2x_feed_forward"}
 SHAPES = ((64, 64), (64, 256), (256, 256), (256, 512))
 WINDOWS, DIM_HEADS = [4, 8, 16], [16, 32, 64]
 CONFIGS = ("opv2v_pointpillar_v2xvit", "mini_pointpillar_v2xvit")
-
-
-def _text(path):
-    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-
-
-def _names(path):
-    return set(re.findall(r"\b(coalign_[a-z0-9_]+)\s*\(", _text(path)))
-
-
-def _declarations(path):
-    out = {}
-    for ret, name, a in re.findall(r"\b(int|size_t)\s+(coalign_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _text(path)):
-        out[name] = (C_TYPES[ret], [hip.P if "*" in p else C_TYPES[p.split()[-2]] for p in [p.strip() for p in a.split(",")] if p != "void"])
-    return out
 
 
 def _param_bytes(C, M):
@@ -49,30 +35,17 @@ def _param_bytes(C, M):
 
 
 def test_ffn_header_table_and_library_agree():
-    """Every name of the header is exported by the product library and equals ``hip.V2X_FFN_SIGNATURES``, types included; every declaration cites the reference
-    lines it replaces; include/ still has 13 files, none of which declares these names; ABI version 2; both loaders bind the table; build.py lists the source."""
-    assert hip.FFN_HEADER == build.FFN_HEADER == os.path.join(REPO, "coalign_amd", "csrc", "coalign_amd_v2x_ffn.h")
-    text = open(hip.FFN_HEADER).read()
+    """The header declares exactly ``NAMES``, the keys of ``hip.V2X_FFN_SIGNATURES`` (types, counts and exports: tests/test_abi_cpu.py); every declaration cites the
+    reference lines it replaces; build.py lists the source."""
+    text = open(abi_headers.path(HEADER)).read()
     assert '#include "coalign_amd.h"' in text
-    declared = _declarations(hip.FFN_HEADER)
-    assert set(declared) == set(hip.V2X_FFN_SIGNATURES) == _names(hip.FFN_HEADER) == NAMES
-    lib = hip.lib()
-    for name, (res, a) in declared.items():
-        fn = getattr(lib, name)
-        assert hip.V2X_FFN_SIGNATURES[name][0] is res and hip.V2X_FFN_SIGNATURES[name][1] == a, name
-        assert fn.restype is res and list(fn.argtypes) == a, name
+    declared = abi_headers.declarations(HEADER)
+    assert set(declared) == set(hip.V2X_FFN_SIGNATURES) == abi_headers.names(HEADER) == NAMES
     comments = re.findall(r"/\*.*?\*/", text, flags=re.S)
     for name in declared:
         last = [c for c in comments if c in text[:text.index(name + "(")]][-1]
         assert "base_transformer.py:7-14" in last and "base_transformer.py:17-29" in last, name
     assert "v2xvit_basic.py:179" in [c for c in comments if c in text[:text.index("coalign_v2x_feed_forward(")]][-1]
-    headers = sorted(os.listdir(os.path.join(REPO, "include")))
-    assert len(headers) == 13 and sorted(build.ABI_HEADERS) == headers
-    for header in headers:
-        assert not (NAMES & _names(os.path.join(REPO, "include", header))), header
-    assert lib.coalign_abi_version() == 2
-    src = open(os.path.join(REPO, "coalign_amd", "hip.py")).read()
-    assert src.count("W2COMM_MSG_SIGNATURES, V2X_FFN_SIGNATURES") == 2                          # lib() and lab_lib()
     assert '"v2x_ffn.hip"' in open(os.path.join(REPO, "coalign_amd", "build.py")).read() and "v2x_ffn.hip" in build.SOURCES
     assert int(re.search(r"#define COALIGN_V2X_FFN_MAX_HIDDEN (\d+)", text).group(1)) == ops.V2X_FFN_MAX_HIDDEN
 

@@ -5,11 +5,11 @@ with the switch on and off."""
 import copy
 import ctypes
 import os
-import re
 
 import pytest
 import torch
 
+import abi_headers
 from coalign_amd import hip, ops, routes, v2xvit
 from coalign_amd.config import builtin_config
 from coalign_amd.fusion import V2XViTFusion
@@ -20,26 +20,10 @@ from v2xvit_reference import args
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, ONE = ctypes.c_void_p(0), ctypes.c_void_p(16)      # (a non-NULL, 16-byte aligned token: none of these calls gets as far as touching memory)
-C_TYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
 HEADER = "coalign_amd_v2x_window.h"
 NAMES = {"coalign_v2x_window_param_bytes", "coalign_v2x_window_workspace_bytes", "coalign_v2x_window_attention"}
 WINDOWS, DIM_HEADS = [4, 8, 16], [16, 32, 64]
 CONFIGS = ("opv2v_pointpillar_v2xvit", "mini_pointpillar_v2xvit")
-
-
-def _text(header):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-
-
-def _names(header):
-    return set(re.findall(r"\b(coalign_[a-z0-9_]+)\s*\(", _text(header)))
-
-
-def _declarations(header):
-    out = {}
-    for ret, name, a in re.findall(r"\b(int|size_t)\s+(coalign_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _text(header)):
-        out[name] = (C_TYPES[ret], [hip.P if "*" in p else C_TYPES[p.split()[-2]] for p in [p.strip() for p in a.split(",")] if p != "void"])
-    return out
 
 
 def _param_bytes(C, fuse):
@@ -47,25 +31,13 @@ def _param_bytes(C, fuse):
 
 
 def test_window_header_table_and_library_agree():
-    """Every name of include/coalign_amd_v2x_window.h is exported by the product library and equals ``hip.V2X_WINDOW_SIGNATURES``, return and argument types included;
-    the eight earlier headers still declare 68 / 2 / 1 / 4 / 3 / 2 / 3 / 3 names and share none with it; ABI version 2; build.py lists the header and the source."""
-    text = open(os.path.join(REPO, "include", HEADER)).read()
+    """include/coalign_amd_v2x_window.h declares exactly ``NAMES``, the keys of ``hip.V2X_WINDOW_SIGNATURES`` (types, counts and exports: tests/test_abi_cpu.py) and
+    cites the reference; build.py lists the header and the source."""
+    text = open(abi_headers.path(HEADER)).read()
     assert '#include "coalign_amd.h"' in text and "mswin.py:19-121" in text and "split_attn.py:6-63" in text and "base_transformer.py:7-14" in text
     assert "v2xvit_basic.py:118-122" in text
-    declared = _declarations(HEADER)
-    assert set(declared) == set(hip.V2X_WINDOW_SIGNATURES) == _names(HEADER) == NAMES
-    lib = hip.lib()
-    for name, (res, a) in declared.items():
-        fn = getattr(lib, name)
-        assert hip.V2X_WINDOW_SIGNATURES[name][0] is res and hip.V2X_WINDOW_SIGNATURES[name][1] == a, name
-        assert fn.restype is res and list(fn.argtypes) == a, name
-    frozen = {"coalign_amd.h": (68, hip.SIGNATURES), "coalign_amd_narrow.h": (2, hip.NARROW_SIGNATURES), "coalign_amd_narrow_sparse.h": (1, hip.NARROW_SPARSE_SIGNATURES),
-              "coalign_amd_align.h": (4, hip.ALIGN_SIGNATURES), "coalign_amd_stage1.h": (3, hip.STAGE1_SIGNATURES), "coalign_amd_disco.h": (2, hip.DISCO_SIGNATURES),
-              "coalign_amd_v2v.h": (3, hip.V2V_SIGNATURES), "coalign_amd_v2x.h": (3, hip.V2X_SIGNATURES)}
-    for header, (count, table) in frozen.items():
-        names = _names(header)
-        assert len(names) == count and names == set(table) and not (NAMES & names), header
-    assert lib.coalign_abi_version() == 2
+    declared = abi_headers.declarations(HEADER)
+    assert set(declared) == set(hip.V2X_WINDOW_SIGNATURES) == abi_headers.names(HEADER) == NAMES
     src = open(os.path.join(REPO, "coalign_amd", "build.py")).read()
     assert '"coalign_amd_v2x_window.h"' in src and '"v2x_window.hip"' in src
 

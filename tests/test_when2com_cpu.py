@@ -12,6 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import abi_headers
 from conftest import assert_elementwise
 from coalign_amd import fusion, hip, ops, routes
 from coalign_amd.config import builtin_config
@@ -22,7 +23,6 @@ from when2com_reference import (adaptive_pool_f64, assert_sees_the_heads, parame
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, ONE = ctypes.c_void_p(0), ctypes.c_void_p(16)      # (a non-NULL, 16-byte aligned token: none of these calls gets as far as touching memory)
-C_TYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
 HEADER = "coalign_amd_w2c.h"
 NAMES = {"coalign_w2c_workspace_bytes", "coalign_w2c_score", "coalign_w2c_fuse"}
 CONFIGS = ("opv2v_pointpillar_when2com", "mini_pointpillar_when2com")
@@ -30,42 +30,13 @@ GOLDEN_ARGS = {"in_channels": 16, "H": 9, "W": 14, "query_size": 32, "key_size":
 PARAM_BYTES = 4 * ops.W2C_PARAM_FLOATS
 
 
-def _text(header):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-
-
-def _names(header):
-    return set(re.findall(r"\b(coalign_[a-z0-9_]+)\s*\(", _text(header)))
-
-
-def _declarations(header):
-    """name -> (restype, [argtypes]) parsed from the header's prototypes (every pointer crosses the ABI as ``hip.P``)."""
-    out = {}
-    for ret, name, args in re.findall(r"\b(int|size_t)\s+(coalign_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _text(header)):
-        out[name] = (C_TYPES[ret], [hip.P if "*" in a else C_TYPES[a.split()[-2]] for a in [a.strip() for a in args.split(",")] if a != "void"])
-    return out
-
-
 def test_w2c_header_table_and_library_agree():
-    """Every name of include/coalign_amd_w2c.h is exported by the product library and equals ``hip.W2C_SIGNATURES``, return and argument types included; every
-    declaration's comment cites the reference lines it replaces; the nine earlier headers keep their 68 / 2 / 1 / 4 / 3 / 2 / 3 / 3 / 3 names and share none with it;
-    ABI version 2; the header's image size is the one ``ops`` packs; build.py lists the header and the source."""
-    text = open(os.path.join(REPO, "include", HEADER)).read()
+    """include/coalign_amd_w2c.h declares exactly ``NAMES``, the keys of ``hip.W2C_SIGNATURES`` (types, counts and exports: tests/test_abi_cpu.py); every
+    declaration's comment cites the reference lines it replaces; the header's image size is the one ``ops`` packs; build.py lists the header and the source."""
+    text = open(abi_headers.path(HEADER)).read()
     assert '#include "coalign_amd.h"' in text
-    declared = _declarations(HEADER)
-    assert set(declared) == set(hip.W2C_SIGNATURES) == _names(HEADER) == NAMES
-    lib = hip.lib()
-    for name, (res, args) in declared.items():
-        fn = getattr(lib, name)
-        assert hip.W2C_SIGNATURES[name][0] is res and hip.W2C_SIGNATURES[name][1] == args, name
-        assert fn.restype is res and list(fn.argtypes) == args, name
-    frozen = {"coalign_amd.h": (68, hip.SIGNATURES), "coalign_amd_narrow.h": (2, hip.NARROW_SIGNATURES), "coalign_amd_narrow_sparse.h": (1, hip.NARROW_SPARSE_SIGNATURES),
-              "coalign_amd_align.h": (4, hip.ALIGN_SIGNATURES), "coalign_amd_stage1.h": (3, hip.STAGE1_SIGNATURES), "coalign_amd_disco.h": (2, hip.DISCO_SIGNATURES),
-              "coalign_amd_v2v.h": (3, hip.V2V_SIGNATURES), "coalign_amd_v2x.h": (3, hip.V2X_SIGNATURES), "coalign_amd_v2x_window.h": (3, hip.V2X_WINDOW_SIGNATURES)}
-    for header, (count, table) in frozen.items():
-        names = _names(header)
-        assert len(names) == count and names == set(table) and not (NAMES & names), header
-    assert lib.coalign_abi_version() == 2
+    declared = abi_headers.declarations(HEADER)
+    assert set(declared) == set(hip.W2C_SIGNATURES) == abi_headers.names(HEADER) == NAMES
     comments = re.findall(r"/\*.*?\*/", text, flags=re.S)
     for name in declared:
         last = [c for c in comments if c in text[:text.index(name + "(")]][-1]
@@ -73,7 +44,7 @@ def test_w2c_header_table_and_library_agree():
     assert "when2com_fuse.py:253-270" in text and "when2com_fuse.py:342-363" in text
     floats = int(eval(re.search(r"#define COALIGN_W2C_PARAM_FLOATS (\(.*\))", text).group(1), {"__builtins__": {}}))
     assert floats == ops.W2C_PARAM_FLOATS == 2 * 256 * 4480 + 2 * 256 + 2 * (256 * 128 + 128) + 2 * (128 * 128 + 128)
-    assert lib.coalign_w2c_workspace_bytes() == 2 * 16 * 8 * 256 * 4
+    assert hip.lib().coalign_w2c_workspace_bytes() == 2 * 16 * 8 * 256 * 4
     src = open(os.path.join(REPO, "coalign_amd", "build.py")).read()
     assert '"coalign_amd_w2c.h"' in src and '"w2c_fuse.hip"' in src
 

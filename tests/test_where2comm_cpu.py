@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_headers
 from conftest import assert_elementwise
 from coalign_amd import fusion, hip, opencood_compat, ops, routes, where2comm
 from coalign_amd.backbone import BaseBEVBackbone, ResNetBEVBackbone
@@ -39,49 +40,13 @@ def module_args(mode, multi_scale, smooth, C=16, thre=None):
     return args
 
 
-def _text(header):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-
-
-def _names(header):
-    return set(re.findall(r"\b(coalign_[a-z0-9_]+)\s*\(", _text(header)))
-
-
-def _ctype(arg):
-    """A prototype's argument -> the binding's type: device buffers cross as ``hip.P``, host int32 arrays and host arrays of pointers as typed pointers."""
-    if re.search(r"\*\s*const\s*\*", arg):
-        return ctypes.POINTER(hip.P)
-    if "int32_t" in arg and "*" in arg:
-        return ctypes.POINTER(ctypes.c_int32)
-    if "*" in arg:
-        return hip.P
-    return {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}[arg.split()[-2]]
-
-
-def _declarations(header):
-    out = {}
-    for ret, name, args in re.findall(r"\b(int|size_t)\s+(coalign_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _text(header)):
-        out[name] = ({"int": ctypes.c_int, "size_t": ctypes.c_size_t}[ret], [_ctype(a.strip()) for a in args.split(",")])
-    return out
-
-
 def test_w2comm_header_table_and_library_agree():
-    """Every name of the eleventh extension header is exported by the product library and equals ``hip.W2COMM_SIGNATURES``, types included; every declaration's
-    comment cites the reference lines it replaces; no earlier header shares a name with it; ABI version 2; build.py lists the header and the source."""
-    text = open(os.path.join(REPO, "include", HEADER)).read()
+    """The header declares exactly ``NAMES``, the keys of ``hip.W2COMM_SIGNATURES`` (types, counts and exports: tests/test_abi_cpu.py); every declaration's comment
+    cites the reference lines it replaces; build.py lists the header and the source."""
+    text = open(abi_headers.path(HEADER)).read()
     assert '#include "coalign_amd.h"' in text
-    declared = _declarations(HEADER)
-    assert set(declared) == set(hip.W2COMM_SIGNATURES) == _names(HEADER) == NAMES
-    lib = hip.lib()
-    for name, (res, args) in declared.items():
-        fn = getattr(lib, name)
-        assert hip.W2COMM_SIGNATURES[name][0] is res and hip.W2COMM_SIGNATURES[name][1] == args, name
-        assert fn.restype is res and list(fn.argtypes) == args, name
-    earlier = [h for h in os.listdir(os.path.join(REPO, "include")) if h != HEADER]
-    assert len(earlier) == 12                                   # coalign_amd.h, the laboratory header and the ten earlier extension headers
-    for h in earlier:
-        assert not (NAMES & _names(h)), h
-    assert lib.coalign_abi_version() == 2
+    declared = abi_headers.declarations(HEADER)
+    assert set(declared) == set(hip.W2COMM_SIGNATURES) == abi_headers.names(HEADER) == NAMES
     comments = re.findall(r"/\*.*?\*/", text, flags=re.S)
     cites = {"coalign_w2comm_masks": ("where2comm.py:34-78", "where2comm_attn.py:273-275"), "coalign_w2comm_fuse_nhwc": ("where2comm_attn.py:224-341", "AttenFusion :44-54")}
     for name in declared:

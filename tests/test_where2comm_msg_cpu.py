@@ -1,5 +1,5 @@
-"""Where2comm's messages, host side (no GPU): the extension header csrc/coalign_amd_where2comm_msg.h against the product library and
-``hip.W2COMM_MSG_SIGNATURES`` with the earlier headers frozen at their counts, argument refusals before any HIP call, ``where2comm.pack_messages_torch`` against a
+"""Where2comm's messages, host side (no GPU): the extension header include/coalign_amd_where2comm_msg.h against
+``hip.W2COMM_MSG_SIGNATURES``, argument refusals before any HIP call, ``where2comm.pack_messages_torch`` against a
 numpy statement of the format (bit order, raster order, size), the wire round trip, the refusal of routes the message kernels do not serve, and the route plan's
 wording with and without ``packed_wire``."""
 import ctypes
@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 import torch
 
-from coalign_amd import build, hip, ops, routes, where2comm
+import abi_headers
+from coalign_amd import hip, ops, routes, where2comm
 from coalign_amd.backbone import BaseBEVBackbone
 from coalign_amd.config import builtin_config
 from coalign_amd.detector import PointPillarWhere2comm, build_model
@@ -19,61 +20,18 @@ from coalign_amd.where2comm import W2Message, pack_bits_torch, pack_messages_tor
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, ONE = ctypes.c_void_p(0), ctypes.c_void_p(16)      # (a non-NULL, 16-byte aligned token: none of these calls gets as far as touching memory)
+HEADER = "coalign_amd_where2comm_msg.h"
 NAMES = {"coalign_w2comm_msg_index", "coalign_w2comm_msg_pack", "coalign_w2comm_fuse_packed"}
 LEVELS = ((64, 5, 37), (128, 2, 18), (256, 1, 9))
 
 
-def _text(path):
-    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-
-
-def _names(path):
-    return set(re.findall(r"\b(coalign_[a-z0-9_]+)\s*\(", _text(path)))
-
-
-def _ctype(arg):
-    """A prototype's argument -> the binding's type: host arrays of pointers and host int32 arrays (``const int32_t *``) as typed pointers, every device buffer and
-    the stream as ``hip.P``."""
-    if re.search(r"\*\s*const\s*\*", arg):
-        return ctypes.POINTER(hip.P)
-    if re.match(r"const int32_t \*\w+$", arg):
-        return ctypes.POINTER(ctypes.c_int32)
-    if "*" in arg:
-        return hip.P
-    return {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}[arg.split()[-2]]
-
-
-def _declarations(path):
-    out = {}
-    for ret, name, args in re.findall(r"\b(int|size_t)\s+(coalign_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _text(path)):
-        out[name] = ({"int": ctypes.c_int, "size_t": ctypes.c_size_t}[ret], [_ctype(" ".join(a.split())) for a in args.split(",")])
-    return out
-
-
 def test_msg_header_table_and_library_agree():
-    """Every name of the header is exported by the product library and equals ``hip.W2COMM_MSG_SIGNATURES``, types included; the thirteen headers under include/
-    keep their counts and share no name with it; every declaration says what it replaces or that the reference has no counterpart; ABI version 2; build.py lists
-    the source; the header documents the wire layout."""
-    assert hip.MSG_HEADER == build.MSG_HEADER == os.path.join(REPO, "coalign_amd", "csrc", "coalign_amd_where2comm_msg.h")
-    text = open(hip.MSG_HEADER).read()
+    """The header declares exactly ``NAMES``, the keys of ``hip.W2COMM_MSG_SIGNATURES`` (types, counts and exports: tests/test_abi_cpu.py); every declaration says
+    what it replaces or that the reference has no counterpart; build.py lists the source; the header documents the wire layout."""
+    text = open(abi_headers.path(HEADER)).read()
     assert '#include "coalign_amd.h"' in text
-    declared = _declarations(hip.MSG_HEADER)
-    assert set(declared) == set(hip.W2COMM_MSG_SIGNATURES) == _names(hip.MSG_HEADER) == NAMES
-    lib = hip.lib()
-    for name, (res, args) in declared.items():
-        fn = getattr(lib, name)
-        assert hip.W2COMM_MSG_SIGNATURES[name][0] is res and hip.W2COMM_MSG_SIGNATURES[name][1] == args, name
-        assert fn.restype is res and list(fn.argtypes) == args, name
-    frozen = {"coalign_amd.h": (68, hip.SIGNATURES), "coalign_amd_narrow.h": (2, hip.NARROW_SIGNATURES), "coalign_amd_narrow_sparse.h": (1, hip.NARROW_SPARSE_SIGNATURES),
-              "coalign_amd_align.h": (4, hip.ALIGN_SIGNATURES), "coalign_amd_stage1.h": (3, hip.STAGE1_SIGNATURES), "coalign_amd_disco.h": (2, hip.DISCO_SIGNATURES),
-              "coalign_amd_v2v.h": (3, hip.V2V_SIGNATURES), "coalign_amd_v2x.h": (3, hip.V2X_SIGNATURES), "coalign_amd_v2x_window.h": (3, hip.V2X_WINDOW_SIGNATURES),
-              "coalign_amd_w2c.h": (3, hip.W2C_SIGNATURES), "coalign_amd_v2v_robust.h": (7, hip.V2VR_SIGNATURES), "coalign_amd_where2comm.h": (2, hip.W2COMM_SIGNATURES),
-              "coalign_amd_lab.h": (3, hip.LAB_SIGNATURES)}
-    assert sorted(frozen) == sorted(os.listdir(os.path.join(REPO, "include"))) and list(frozen)[:-1] == list(hip.HEADERS)
-    for header, (count, table) in frozen.items():
-        names = _names(os.path.join(REPO, "include", header))
-        assert len(names) == count and names == set(table) and not (NAMES & names), header
-    assert lib.coalign_abi_version() == 2
+    declared = abi_headers.declarations(HEADER)
+    assert set(declared) == set(hip.W2COMM_MSG_SIGNATURES) == abi_headers.names(HEADER) == NAMES
     comments = re.findall(r"/\*.*?\*/", text, flags=re.S)
     for name in declared:
         last = [c for c in comments if c in text[:text.index(name + "(")]][-1]
