@@ -29,7 +29,7 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
+using namespace coalign;
 
 constexpr int kKC = 8;               // input channels per LDS chunk
 constexpr int kCoutTile = 64;        // output channels per workgroup
@@ -268,22 +268,13 @@ void conv3x3_kernel(const ConvArgs a) {
 template <int BH, int BW, int NPB>
 int plan(const ConvArgs &a0, ConvArgs *out, size_t *ws_bytes) {          // grid size; fills the tiling fields and the workspace size
     using G = Geo<BH, BW, NPB>;
-    static int resident = 0;                    // workgroups one CU holds at once (occupancy query, once per shape family)
-    static int cus = 0;
-    if (!resident) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) prop.multiProcessorCount = 256;
-        cus = prop.multiProcessorCount;
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv3x3_kernel<BH, BW, NPB, true>, G::THREADS, 0) != hipSuccess || n < 1) n = 1;
-        resident = n;
-    }
+    static PerDevice resident;                  // workgroups one CU holds at once (occupancy query, once per shape family and device)
+    const int slots = cu_count() * resident_blocks(resident, conv3x3_kernel<BH, BW, NPB, true>, G::THREADS, 0);
     ConvArgs a = a0;
     a.tiles_x = (a.W + G::TW - 1) / G::TW;
     a.tiles_per_img = a.tiles_x * ((a.H + G::TH - 1) / G::TH);
     a.total_tiles = a.tiles_per_img * (a.Cout / kCoutTile) * a.N;
-    const int grid = a.total_tiles < cus * resident ? a.total_tiles : cus * resident;     // every range >= one tile; all resident
+    const int grid = a.total_tiles < slots ? a.total_tiles : slots;     // every range >= one tile; all resident
     if (out) *out = a;
     if (ws_bytes) *ws_bytes = coalign::align_up((size_t)(grid + 1) * sizeof(int), 256) + (size_t)(grid + 1) * 16 * G::NCO * G::THREADS * sizeof(float);
     return grid;

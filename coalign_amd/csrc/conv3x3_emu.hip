@@ -30,9 +30,7 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
+using namespace coalign;
 
 // F16 (round 4, terms = 16 at the C ABI): the 2-way split with FP16 terms -- x = x_h + x_l, x_h = fp16(x) (11 significant bits), x_l = fp16(x - x_h):
 // 22 bits of every operand instead of bf16's 16, at the 2-way split's three products.  The 16-byte operands travel through the kernel typed bf16x8;
@@ -353,7 +351,7 @@ void conv3x3_emu_kernel(const EmuArgs a) {
             if (ins < G::WUNITS * G::WINSTR) {
                 if constexpr (VAR & VAR_ASM_DMA) {
                     const unsigned dst = (unsigned)(size_t)(lptr_t)(wdst + ins * 256);      // wave-uniform LDS byte address -> M0
-                    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(__builtin_amdgcn_readfirstlane(dst)), "v"(wsrc + ins * 64) : "memory", "m0");
+                    COALIGN_LDS_DMA16(wsrc + ins * 64, dst);
                 } else {
                     __builtin_amdgcn_global_load_lds((gptr_t)(wsrc + ins * 64), (lptr_t)(wdst + ins * 256), 16, 0, 0);
                 }
@@ -690,22 +688,9 @@ template <int BH, int BW, int NPB, int TERMS, int KCH, int STRIDE, int LAYOUT, i
 int launch_variant(const EmuArgs &a0, hipStream_t s) {
     using G = Geo<BH, BW, NPB, TERMS, KCH, STRIDE, PBUF, (VAR & VAR_TAPK) != 0, (VAR >> 2) & 7>;
     static_assert(G::LDS_BYTES <= 160 * 1024, "geometry does not fit the 160 KB LDS");
-    static int resident = 0, cus = 0;
     auto kern = conv3x3_emu_kernel<BH, BW, NPB, TERMS, KCH, false, STRIDE, LAYOUT, PBUF, VAR>;
-    if (!resident) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) prop.multiProcessorCount = 256;
-        cus = prop.multiProcessorCount;
-        const int rc = coalign::hip_call(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES));
-        if (rc != COALIGN_OK) {
-            (void)hipGetLastError();
-            return rc;
-        }
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, G::THREADS, G::LDS_BYTES) != hipSuccess || n < 1) n = 1;
-        resident = n;
-    }
+    static PerDevice lds_set, resident;
+    if (const int rc = allow_dynamic_lds(lds_set, G::LDS_BYTES, kern)) return rc;
     EmuArgs a = a0;
     a.tiles_x = (a.W + G::TW - 1) / G::TW;
     if constexpr (G::STACK) {                                  // the batch as one image of N * H rows: decode() then yields n = 0, y0 = stacked row
@@ -716,7 +701,7 @@ int launch_variant(const EmuArgs &a0, hipStream_t s) {
         a.tiles_per_img = a.tiles_x * ((a.H + G::TH - 1) / G::TH);
         a.total_tiles = a.tiles_per_img * (a.Cout / kCoutTile) * a.N;
     }
-    const int slots = cus * resident;
+    const int slots = cu_count() * resident_blocks(resident, kern, G::THREADS, G::LDS_BYTES);
     const int grid = a.total_tiles < slots ? a.total_tiles : slots;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, a);
     return COALIGN_OK;
@@ -770,30 +755,15 @@ int launch(const EmuArgs &a0, void *workspace, size_t workspace_bytes, hipStream
     static_assert(!(VAR & (VAR_STACK | VAR_NCO1)), "stacked / 32-channel variants go through launch_variant (whole tiles)");
     using G = Geo<BH, BW, NPB, TERMS, KCH, 1, PBUF, TAPK>;
     static_assert(!TAPK || G::LDS_BYTES <= 160 * 1024, "geometry does not fit the 160 KB LDS");
-    static int resident = 0, cus = 0;
-    if (!resident) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) prop.multiProcessorCount = 256;
-        cus = prop.multiProcessorCount;
-        for (int sp = 0; sp < 2; ++sp) {
-            const void *fn = sp ? reinterpret_cast<const void *>(conv3x3_emu_kernel<BH, BW, NPB, TERMS, KCH, true, 1, LAYOUT, PBUF, VAR>)
-                                : reinterpret_cast<const void *>(conv3x3_emu_kernel<BH, BW, NPB, TERMS, KCH, false, 1, LAYOUT, PBUF, VAR>);
-            const int rc = coalign::hip_call(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES));
-            if (rc != COALIGN_OK) {                // geometry does not fit this device's LDS: report, leave no sticky error behind
-                (void)hipGetLastError();
-                return rc;
-            }
-        }
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv3x3_emu_kernel<BH, BW, NPB, TERMS, KCH, true, 1, LAYOUT, PBUF, VAR>, G::THREADS, G::LDS_BYTES) != hipSuccess || n < 1) n = 1;
-        resident = n;
-    }
+    auto k_split = conv3x3_emu_kernel<BH, BW, NPB, TERMS, KCH, true, 1, LAYOUT, PBUF, VAR>;
+    auto k_whole = conv3x3_emu_kernel<BH, BW, NPB, TERMS, KCH, false, 1, LAYOUT, PBUF, VAR>;
+    static PerDevice lds_set, resident;
+    if (const int rc = allow_dynamic_lds(lds_set, G::LDS_BYTES, k_whole, k_split)) return rc;      // (a geometry that does not fit this device's LDS is reported here)
     EmuArgs a = a0;
     a.tiles_x = (a.W + G::TW - 1) / G::TW;
     a.tiles_per_img = a.tiles_x * ((a.H + G::TH - 1) / G::TH);
     a.total_tiles = a.tiles_per_img * (a.Cout / kCoutTile) * a.N;
-    const int slots = cus * resident, chunks = a.Cin / (kKC * KCH);
+    const int slots = cu_count() * resident_blocks(resident, k_split, G::THREADS, G::LDS_BYTES), chunks = a.Cin / (kKC * KCH);
     Launch l;
     l.split = want_split(a.total_tiles, slots, chunks, TAPK ? 16 : 32);
     l.grid = a.total_tiles < slots ? a.total_tiles : slots;
@@ -821,9 +791,9 @@ int launch(const EmuArgs &a0, void *workspace, size_t workspace_bytes, hipStream
         a.partial = reinterpret_cast<float *>(static_cast<char *>(workspace) + l.flag_bytes);
         const int rc = coalign::fill_words(workspace, l.flag_bytes / 4, 0u, s);
         if (rc != COALIGN_OK) return rc;
-        hipLaunchKernelGGL((conv3x3_emu_kernel<BH, BW, NPB, TERMS, KCH, true, 1, LAYOUT, PBUF, VAR>), dim3(l.grid), dim3(G::THREADS), G::LDS_BYTES, s, a);
+        hipLaunchKernelGGL(k_split, dim3(l.grid), dim3(G::THREADS), G::LDS_BYTES, s, a);
     } else {
-        hipLaunchKernelGGL((conv3x3_emu_kernel<BH, BW, NPB, TERMS, KCH, false, 1, LAYOUT, PBUF, VAR>), dim3(l.grid), dim3(G::THREADS), G::LDS_BYTES, s, a);
+        hipLaunchKernelGGL(k_whole, dim3(l.grid), dim3(G::THREADS), G::LDS_BYTES, s, a);
     }
     return COALIGN_OK;
 }

@@ -33,8 +33,7 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
+using namespace coalign;
 typedef __attribute__((address_space(3))) void *lptr_t;
 
 constexpr int kWaves = 16, kThreads = 64 * kWaves;
@@ -61,17 +60,6 @@ struct NarrowArgs {
     int *range_flag;                    // may be NULL
     int N, Cin, H, W, relu, tiles_x, tiles_y, total_tiles, stationary;
 };
-
-__device__ __forceinline__ void swap32(unsigned &a, unsigned &b) {       // lanes 32-63 of a <-> lanes 0-31 of b
-    const auto q = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-    const unsigned x = q[0], y = q[1];
-    a = x;
-    b = y;
-}
-
-__device__ __forceinline__ void dma16(const uint4 *src, unsigned lds_byte) {      // 64 lanes x 16 bytes -> LDS [lds_byte, + 1024): lane l lands at + 16 l
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(__builtin_amdgcn_readfirstlane(lds_byte)), "v"(src) : "memory", "m0");
-}
 
 struct Tile {
     int n, y0, x0;
@@ -139,7 +127,7 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv3x3_narrow_kernel(co
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const uint4 *src = off < 0 ? a.zero : KIND == 2 ? xs + (size_t)off + (c * 4 + q) : xs + (size_t)off + ((size_t)c * 4 + q) * HW;
-                dma16(src, lds0 + kPatch0 + slot * kBBytes + (q * kPixP + wave * 64) * 16);
+                lds_dma16(src, lds0 + kPatch0 + slot * kBBytes + (q * kPixP + wave * 64) * 16);
             }
         }
     };
@@ -147,7 +135,7 @@ __global__ __launch_bounds__(kThreads, kWaves / 4) void conv3x3_narrow_kernel(co
 #pragma unroll
         for (int k = 0; k < WJ; ++k) {
             const int ins = (kWaves - 1 - wave) + kWaves * k;          // (the wavefronts without a patch piece first)
-            if (ins < WINS) dma16(a.wt + (size_t)c * WQ + ins * 64 + lane, lds0 + slot * W_BYTES + ins * 1024);
+            if (ins < WINS) lds_dma16(a.wt + (size_t)c * WQ + ins * 64 + lane, lds0 + slot * W_BYTES + ins * 1024);
         }
     };
     // ---- input kind 1: (pixel, channel half) items of this thread: 8 floats each, fetched one interval ahead, split into the other patch buffer
@@ -336,26 +324,15 @@ int narrow_check(int N, int Cin, int Cout, int H, int W) {
 
 template <int CT, int KIND>
 int launch_narrow(NarrowArgs a, hipStream_t s) {
-    constexpr int kMaxDev = 16;
-    static int cus[kMaxDev] = {0};                                     // per device: the function attribute belongs to the device's code object
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = 0;
     auto k = conv3x3_narrow_kernel<CT, KIND>;
-    if (!cus[dev]) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount < 1) prop.multiProcessorCount = 256;
-        const int rc = coalign::hip_call(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-        if (rc != COALIGN_OK) {
-            (void)hipGetLastError();
-            return rc;
-        }
-        cus[dev] = prop.multiProcessorCount;
-    }
+    static PerDevice lds_set;
+    if (const int rc = allow_dynamic_lds(lds_set, kLdsBytes, k)) return rc;
+    const int cus = cu_count();
     a.tiles_x = (a.W + kTW - 1) / kTW;
     a.tiles_y = (a.H + kTH - 1) / kTH;
     a.total_tiles = a.N * a.tiles_y * a.tiles_x;
     a.stationary = (size_t)(a.Cin / 16) * (9 * 2 * 2 * CT * 16) <= (size_t)kWAreaBytes ? 1 : 0;
-    const int grid = a.total_tiles < cus[dev] ? a.total_tiles : cus[dev];      // 152 KB of LDS: one workgroup per CU
+    const int grid = a.total_tiles < cus ? a.total_tiles : cus;      // 152 KB of LDS: one workgroup per CU
     hipLaunchKernelGGL(k, dim3(grid), dim3(kThreads), kLdsBytes, s, a);
     return coalign::check_launch();
 }

@@ -23,11 +23,8 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
+using namespace coalign;
 typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
-typedef _Float16 halfx4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void *lptr_t;
 
 constexpr int kCoutTile = 64;
@@ -95,17 +92,6 @@ struct Geo {
 struct Tile {
     int cg, n0, yl0, yb, x0;      // output-channel group; image of the tile's first row, that row inside the image, rows left in the image (H - yl0; huge if not stacked); first column
 };
-
-__device__ __forceinline__ void swap32(unsigned &a, unsigned &b) {       // lanes 32-63 of a <-> lanes 0-31 of b
-    const auto q = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-    const unsigned x = q[0], y = q[1];
-    a = x;
-    b = y;
-}
-
-__device__ __forceinline__ void dma16(const uint4 *src, unsigned lds_byte) {      // 64 lanes x 16 bytes -> LDS [lds_byte, + 1024): lane l lands at + 16 l
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(__builtin_amdgcn_readfirstlane(lds_byte)), "v"(src) : "memory", "m0");
-}
 
 enum { SP_OUT_SP = 1, SP_OUT_NHWC = 2, SP_OUT_BOTH = 3 };
 enum { SP_RES_NONE = 0, SP_RES_SP = 1, SP_RES_NHWC = 2 };
@@ -229,11 +215,11 @@ __global__ __launch_bounds__(64 * NPB + (MODE == 3 ? 64 : MODE == 7 ? 256 : 0), 
     auto issue_op = [&](const Plan &pl, int c, int slot, int k) {
         if (k < K::WJ) {
             const int ins = lw + K::LOADERS * k;
-            if (ins < G::WINS && !SP_ABLATE(1)) dma16(pl.wsrc + (size_t)c * G::WQ_SRC + ins * (64 * kCoutTile / CT), lds0 + slot * G::W_BYTES + ins * 1024);
+            if (ins < G::WINS && !SP_ABLATE(1)) lds_dma16(pl.wsrc + (size_t)c * G::WQ_SRC + ins * (64 * kCoutTile / CT), lds0 + slot * G::W_BYTES + ins * 1024);
         } else {
             const int j = (k - K::WJ) / 4, q = (k - K::WJ) % 4, ins = lw + K::LOADERS * j;
             if (ins < G::PINS && !SP_ABLATE(2))
-                dma16(pl.off[j] < 0 ? a.zero : a.x + (size_t)pl.off[j] + ((size_t)c * 4 + q) * HW, lds0 + K::NBUF * G::W_BYTES + slot * G::B_BYTES + (q * G::PIXP + ins * 64) * 16);
+                lds_dma16(pl.off[j] < 0 ? a.zero : a.x + (size_t)pl.off[j] + ((size_t)c * 4 + q) * HW, lds0 + K::NBUF * G::W_BYTES + slot * G::B_BYTES + (q * G::PIXP + ins * 64) * 16);
         }
     };
     auto issue_all = [&](const Plan &pl, int c, int slot) {
@@ -704,10 +690,6 @@ struct SpLaunch {          // what the host needs to know about one (shape, geom
 template <int BH, int BW, int NPB, int NBX, int MODE, int CT = 64>
 int launch_geo(SpArgs a, int out_kind, int split_policy, void *workspace, size_t workspace_bytes, hipStream_t s, SpLaunch *query) {
     using G = Geo<BH, BW, NPB, NBX, CT>;
-    constexpr int kMaxDev = 16;
-    static int cus[kMaxDev] = {0};                                    // per device: the function attribute belongs to the device's code object
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = 0;
     using KW = Work<BH, BW, NPB, NBX, MODE, CT>;
     constexpr bool CAN_SPLIT = NPB == 8 && CT == 64 && MODE != 3 && MODE != 6 && MODE != 7;    // (the hand-over code needs the 8-wavefront geometries' register budget; the loader wavefront of MODE 3 mirrors whole tiles only; the paired mode runs whole tiles)
     auto k_sp = conv3x3_sp_kernel<BH, BW, NPB, NBX, SP_OUT_SP, MODE, false, CT>;
@@ -716,27 +698,11 @@ int launch_geo(SpArgs a, int out_kind, int split_policy, void *workspace, size_t
     auto k_cl_s = conv3x3_sp_kernel<BH, BW, NPB, NBX, SP_OUT_NHWC, MODE, CAN_SPLIT, CT>;
     auto k_both = conv3x3_sp_kernel<BH, BW, NPB, NBX, SP_OUT_BOTH, MODE, false, CT>;
     auto k_both_s = conv3x3_sp_kernel<BH, BW, NPB, NBX, SP_OUT_BOTH, MODE, CAN_SPLIT, CT>;
-    if (!cus[dev]) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) prop.multiProcessorCount = 256;
-        if (!query) {
-            for (const void *fn : {reinterpret_cast<const void *>(k_sp), reinterpret_cast<const void *>(k_cl), reinterpret_cast<const void *>(k_sp_s), reinterpret_cast<const void *>(k_cl_s),
-                                   reinterpret_cast<const void *>(k_both), reinterpret_cast<const void *>(k_both_s)}) {
-                const int rc = coalign::hip_call(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KW::LDS_BYTES));
-                if (rc != COALIGN_OK) {
-                    (void)hipGetLastError();
-                    return rc;
-                }
-            }
-            cus[dev] = prop.multiProcessorCount;
-        }
-        if (query && !cus[dev]) {                                     // (a size query before the first launch: same CU count, attributes set at the launch)
-            SpArgs b = a;
-            (void)b;
-        }
+    static PerDevice lds_set;
+    if (!query) {                                                      // (a size query before the first launch sets no attributes: the launch does)
+        if (const int rc = allow_dynamic_lds(lds_set, KW::LDS_BYTES, k_sp, k_cl, k_sp_s, k_cl_s, k_both, k_both_s)) return rc;
     }
-    hipDeviceProp_t prop2;
-    const int n_cu = cus[dev] ? cus[dev] : (hipGetDeviceProperties(&prop2, dev) == hipSuccess && prop2.multiProcessorCount > 0 ? prop2.multiProcessorCount : 256);
+    const int n_cu = cu_count();
     a.stack = (a.N > 1 && G::TH <= a.H) ? 1 : 0;
     a.tiles_x = (a.W + G::TW - 1) / G::TW;
     a.tiles_y = (a.H + G::TH - 1) / G::TH;                            // per image (not stacked)
@@ -840,12 +806,7 @@ int dispatch_sp(const SpArgs &a, int out_kind, int geometry, void *ws, size_t ws
         // Round 6: a 12-wavefront geometry that leaves more than a quarter of the CUs without a tile loses to the 8-wavefront one whose (smaller) tiles still fit one
         // round: 2 x 64 -> 64 @ 100 x 252 (DAIR stage 1: 136 tiles of 12 x 32 against 200 of 8 x 32 on 256 CUs) 21.5 -> 17.0 us.  Same sums in the same order:
         // the geometries are bit-equal (tests/test_round5_gpu.py).
-        static int n_cu = 0;
-        if (!n_cu) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        }
+        const int n_cu = cu_count();
         const int rows = a.N * a.H, groups = a.Cout / kCoutTile;
         if (geo == 121 || geo == 124) {
             const int th12 = geo == 121 ? 12 : 24, tw12 = geo == 121 ? 32 : 16, alt = (a.W % 32 == 0 || a.W % 32 > 24) ? 81 : 148;

@@ -29,8 +29,7 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
+using namespace coalign;
 typedef __attribute__((address_space(3))) void *lptr_t;
 
 constexpr int kCoutTile = 64;
@@ -71,17 +70,6 @@ struct S2Args {
 #else
 #define S2_STAMP(k)
 #endif
-
-__device__ __forceinline__ void swap32(unsigned &a, unsigned &b) {       // lanes 32-63 of a <-> lanes 0-31 of b
-    const auto q = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-    const unsigned x = q[0], y = q[1];
-    a = x;
-    b = y;
-}
-
-__device__ __forceinline__ void dma16(const uint4 *src, unsigned lds_byte) {      // 64 lanes x 16 bytes -> LDS [lds_byte, + 1024): lane l lands at + 16 l
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(__builtin_amdgcn_readfirstlane(lds_byte)), "v"(src) : "memory", "m0");
-}
 
 struct Task {
     int cg, n, oy0, ox0;
@@ -181,12 +169,12 @@ __global__ __launch_bounds__(THREADS, 2) void conv3x3_sp_s2_kernel(const S2Args 
         if (k < WJ) {
             const bool ok = wave < 2 ? k < 3 : true;
             const int piece = wave < 2 ? 3 * wave + k : 6 + 5 * (wave - 2) + k;
-            if (ok && !(a.ablate & 1)) dma16(pl.wsrc + (size_t)c * WQ + piece * 64, lds0 + slot * W_BYTES + piece * 1024);
+            if (ok && !(a.ablate & 1)) lds_dma16(pl.wsrc + (size_t)c * WQ + piece * 64, lds0 + slot * W_BYTES + piece * 1024);
         } else {
             const int j = (k - WJ) / 4, q = (k - WJ) % 4, ins = j == 0 ? wave : 8 + wave;
             if ((j == 0 || wave < 2) && !(a.ablate & 2)) {
                 const uint4 *src = pl.off[j] < 0 ? a.zero : SPARSE ? a.x + (size_t)pl.off[j] + (c * 4 + q) : a.x + (size_t)pl.off[j] + ((size_t)c * 4 + q) * HW;
-                dma16(src, lds0 + 2 * W_BYTES + slot * B_BYTES + (q * PIXP + ins * 64) * 16);
+                lds_dma16(src, lds0 + 2 * W_BYTES + slot * B_BYTES + (q * PIXP + ins * 64) * 16);
             }
         }
     };
@@ -407,21 +395,10 @@ int s2_check(int N, int Cin, int Cout, int H, int W) {
 
 template <bool SPARSE, bool SKIP>
 int launch_s2(S2Args a, hipStream_t s) {
-    constexpr int kMaxDev = 16;
-    static int cus[kMaxDev] = {0};                                    // per device: the function attribute belongs to the device's code object
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = 0;
     auto kern = conv3x3_sp_s2_kernel<SPARSE, SKIP>;
-    if (!cus[dev]) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount <= 0) prop.multiProcessorCount = 256;
-        const int rc = coalign::hip_call(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
-        if (rc != COALIGN_OK) {
-            (void)hipGetLastError();
-            return rc;
-        }
-        cus[dev] = prop.multiProcessorCount;
-    }
+    static PerDevice lds_set;
+    if (const int rc = allow_dynamic_lds(lds_set, LDS_BYTES, kern)) return rc;
+    const int cus = cu_count();
     a.Ho = (a.H + 1) / 2;
     a.Wo = (a.W + 1) / 2;
     a.tiles_x = (a.Wo + TW - 1) / TW;
@@ -429,7 +406,7 @@ int launch_s2(S2Args a, hipStream_t s) {
     a.total_tasks = a.tiles_x * a.tiles_y * a.N * (a.Cout / kCoutTile);
     // as many workgroups as give every one the same number of tasks (+-1): 780 tasks on 256 CUs are four rounds either way, 195 workgroups leave 61 CUs to the
     // other frame's kernels
-    const int rounds = (a.total_tasks + cus[dev] - 1) / cus[dev], grid = (a.total_tasks + rounds - 1) / rounds;
+    const int rounds = (a.total_tasks + cus - 1) / cus, grid = (a.total_tasks + rounds - 1) / rounds;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), LDS_BYTES, s, a);
     return coalign::check_launch();
 }

@@ -37,8 +37,7 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using namespace coalign;
 typedef __attribute__((address_space(3))) void *lptr_w_t;
 
 constexpr int kCoutUnit = 64;        // output channels per workgroup
@@ -155,7 +154,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino_kernel(const WinoArgs a) {
                 if (64 * (wave + 8 * d) < G::RAWSZ) {      // (wave-uniform)
                     const float *src = goff[d] < 0 ? a.zero16 : a.x + goff[d] + 16 * k;
                     const unsigned dst = (unsigned)(size_t)(lptr_w_t)(lds + G::R_OFF + buf * G::RAWSZ + 64 * (wave + 8 * d));
-                    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(__builtin_amdgcn_readfirstlane(dst)), "v"(src) : "memory", "m0");
+                    COALIGN_LDS_DMA16(src, dst);
                 }
             }
         };
@@ -356,19 +355,10 @@ template <int TBW, int ABL = 0, int MODE = 0>
 int launch_wino(const WinoArgs &a0, hipStream_t s) {
     using G = WGeo<TBW>;
     static_assert(G::LDS_BYTES <= 160 * 1024, "geometry does not fit the 160 KB LDS");
-    static int cus = 0;
     auto kern = conv3x3_wino_kernel<TBW, ABL, MODE>;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) prop.multiProcessorCount = 256;
-        const int rc = coalign::hip_call(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES));
-        if (rc != COALIGN_OK) {
-            (void)hipGetLastError();
-            return rc;
-        }
-        cus = prop.multiProcessorCount;
-    }
+    static PerDevice lds_set;
+    if (const int rc = allow_dynamic_lds(lds_set, G::LDS_BYTES, kern)) return rc;
+    const int cus = cu_count();
     WinoArgs a = a0;
     a.pitch = a.H + ((a.H & 1) ? 1 : 2);
     const int tile_rows = a.N * a.pitch / 2, tile_cols = (a.W + 1) / 2;

@@ -24,15 +24,13 @@
 // No workspace, no allocation, the caller's stream: capturable.  Accuracy: the matrix layers see operands rounded to 22 bits (sp16), everything else is fp32.
 #include "common.h"
 #include "warp_taps.h"
+#include "sp16_tiles.h"
 
 #include "coalign_amd_disco.h"
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
-
-constexpr int TP = 32;                         // pixels per workgroup = columns of one matrix instruction
+using namespace coalign;
 constexpr int H1 = 128, H2 = 32, H3 = 8;       // PixelWeightLayer's widths (disco_fuse.py:80-89)
 constexpr int H1_ROW = H1 * 4 + 16;            // bytes of a pixel's row in the hidden tile: 16 groups x (8 h + 8 l) + the bank pad
 // float section of the parameter image: b1[128] b2[32] w3[2 halves][8 outputs][16 registers] b3[8] w4[8] b4[1] + 3 of padding
@@ -41,7 +39,6 @@ constexpr int F_B1 = 0, F_B2 = 128, F_W3 = 160, F_B3 = 416, F_W4 = 424, F_B4 = 4
 __host__ __device__ constexpr size_t w1_bytes(int C) { return (size_t)(C / 16) * 4 * 64 * 32; }      // [C / 16 steps][4 row tiles][64 lanes][8 h | 8 l] fp16
 constexpr size_t kW2Bytes = 8 * 64 * 32;                                                              // [8 steps][64 lanes][8 h | 8 l] fp16
 __host__ __device__ constexpr size_t param_bytes(int C) { return 2 * w1_bytes(C) + kW2Bytes + F_COUNT * 4; }
-__host__ __device__ constexpr int x_row_bytes(int C) { return C * 4 + 16; }
 __host__ __device__ constexpr size_t lds_bytes(int C) { return (size_t)TP * x_row_bytes(C) + TP * H1_ROW + TP * sizeof(Taps) + F_COUNT * 4 + 3 * TP * 4; }
 
 struct DiscoArgs {
@@ -51,36 +48,6 @@ struct DiscoArgs {
     float *out;              // [H, W, C]
     int n, C, H, W;
 };
-
-struct Geom { int C, H, W, Ho, Wo; };      // what make_taps reads: source plane and output grid are the same map here
-
-// 8 values -> the tile's [8 h | 8 l] image of one channel group
-__device__ __forceinline__ void store_split8(char *dst, const float (&v)[8]) {
-    uint4 h, l;
-    coalign::sp16_split2(v[0], v[1], h.x, l.x);
-    coalign::sp16_split2(v[2], v[3], h.y, l.y);
-    coalign::sp16_split2(v[4], v[5], h.z, l.z);
-    coalign::sp16_split2(v[6], v[7], h.w, l.w);
-    *reinterpret_cast<uint4 *>(dst) = h;
-    *reinterpret_cast<uint4 *>(dst + 16) = l;
-}
-
-struct Pair { halfx8 h, l; };
-
-__device__ __forceinline__ Pair load_pair(const void *p) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(p);
-    Pair r;
-    r.h = __builtin_bit_cast(halfx8, q[0]);
-    r.l = __builtin_bit_cast(halfx8, q[1]);
-    return r;
-}
-
-// acc += w_h x_h, accl += w_h x_l' + w_l' x_h (the two terms that carry 2^10)
-__device__ __forceinline__ void mfma3(const Pair &w, const Pair &x, floatx16 &acc, floatx16 &accl) {
-    accl = __builtin_amdgcn_mfma_f32_32x32x16_f16(w.h, x.l, accl, 0, 0, 0);
-    accl = __builtin_amdgcn_mfma_f32_32x32x16_f16(w.l, x.h, accl, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w.h, x.h, acc, 0, 0, 0);
-}
 
 // rows [32 w, 32 w + 32) of W (image `img`, this wavefront's row tile) times the LDS tile's `steps` 16-channel steps, for the 32 pixels; the weight pieces of two
 // steps are fetched while the two before them are multiplied.  steps is even (C % 32 == 0).
@@ -277,18 +244,8 @@ __global__ __launch_bounds__(256) void disco_fuse_kernel(const DiscoArgs a) {
 template <int MAXI>
 int launch(const DiscoArgs &a, hipStream_t stream) {
     // C > 336 needs more than the 64 KB of dynamic LDS a kernel gets by default: raised once per device and instantiation, at the first launch
-    static bool raised[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!raised[dev]) {
-        const int rc = coalign::hip_call(hipFuncSetAttribute(reinterpret_cast<const void *>(disco_fuse_kernel<MAXI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                             (int)lds_bytes(COALIGN_DISCO_MAX_CHANNELS)));
-        if (rc != COALIGN_OK) {
-            (void)hipGetLastError();
-            return rc;
-        }
-        raised[dev] = true;
-    }
+    static PerDevice lds_set;
+    if (const int rc = allow_dynamic_lds(lds_set, lds_bytes(COALIGN_DISCO_MAX_CHANNELS), disco_fuse_kernel<MAXI>)) return rc;
     const int tiles = (a.H * a.W + TP - 1) / TP;
     hipLaunchKernelGGL(disco_fuse_kernel<MAXI>, dim3(tiles), dim3(256), lds_bytes(a.C), stream, a);
     return coalign::check_launch();

@@ -35,8 +35,7 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
+using namespace coalign;
 typedef __attribute__((address_space(3))) void *lptr_t;
 
 constexpr int kWaves = 8, kThreads = 64 * kWaves;
@@ -62,17 +61,6 @@ struct StemArgs {
     int N, Cin, H, W, Ho, Wo, relu, tiles_x, tiles_y;
 };
 
-__device__ __forceinline__ void swap32(unsigned &a, unsigned &b) {       // lanes 32-63 of a <-> lanes 0-31 of b
-    const auto q = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-    const unsigned x = q[0], y = q[1];
-    a = x;
-    b = y;
-}
-
-__device__ __forceinline__ void dma16(const uint4 *src, unsigned lds_byte) {      // 64 lanes x 16 bytes -> LDS [lds_byte, + 1024): lane l lands at + 16 l
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(__builtin_amdgcn_readfirstlane(lds_byte)), "v"(src) : "memory", "m0");
-}
-
 __global__ __launch_bounds__(kThreads) void conv7x7_s2_sp(const StemArgs a) {
     extern __shared__ __attribute__((aligned(1024))) char lds[];
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, half = lane >> 5, p = lane & 31;
@@ -94,7 +82,7 @@ __global__ __launch_bounds__(kThreads) void conv7x7_s2_sp(const StemArgs a) {
 #pragma unroll
         for (int k = 0; k < kWJ; ++k) {
             const int ins = wave + kWaves * k;
-            if (ins < kWIns) dma16(a.wt + (size_t)it * kWQ + ins * 64 + lane, lds0 + slot * kWBytes + ins * 1024);
+            if (ins < kWIns) lds_dma16(a.wt + (size_t)it * kWQ + ins * 64 + lane, lds0 + slot * kWBytes + ins * 1024);
         }
     };
     // item j of this thread: patch group i = (tid >> 2) + (kThreads / 4) j, channel quad tid & 3 of the interval's 16 channels
@@ -276,8 +264,6 @@ __global__ __launch_bounds__(256) void up2x_concat_sp(const UpArgs a) {
     if (a.range_flag && vmax > 65504.f) atomicOr(a.range_flag, 1);
 }
 
-bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 }  // namespace
 
 extern "C" size_t coalign_conv7x7_s2_weight_bytes(int Cin) {
@@ -292,18 +278,8 @@ extern "C" int coalign_conv7x7_s2_sp(const float *x, const void *w_image, const 
     if (Cin < 16 || Cin % 16 || Cin > COALIGN_CONV7X7_MAX_CIN || (relu != 0 && relu != 1)) return COALIGN_ERR_UNSUPPORTED;
     if (misaligned(x, 15) || misaligned(w_image, 15) || misaligned(y_sp, 15) || misaligned(bias, 3) || misaligned(range_flag, 3)) return COALIGN_ERR_NULL_POINTER;
     if (N == 0) return COALIGN_OK;
-    constexpr int kMaxDev = 16;
-    static bool ready[kMaxDev] = {false};                              // per device: the function attribute belongs to the device's code object
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = 0;
-    if (!ready[dev]) {
-        const int rc = coalign::hip_call(hipFuncSetAttribute(reinterpret_cast<const void *>(conv7x7_s2_sp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-        if (rc != COALIGN_OK) {
-            (void)hipGetLastError();
-            return rc;
-        }
-        ready[dev] = true;
-    }
+    static PerDevice lds_set;
+    if (const int rc = allow_dynamic_lds(lds_set, kLdsBytes, conv7x7_s2_sp)) return rc;
     const size_t wbytes = coalign_conv7x7_s2_weight_bytes(Cin), tail = (size_t)COALIGN_CONV7X7_COUT * 8;
     StemArgs a{};
     a.x = x;

@@ -17,6 +17,7 @@
 
 namespace {
 
+using coalign::misaligned;
 constexpr int CHUNK = COALIGN_LSS_CHUNK;
 
 struct CellArgs {
@@ -238,8 +239,6 @@ __global__ __launch_bounds__(256) void lss_pool(const PoolArgs a) {
     }
     if (wave == 0) store_row<C>(a.out + (size_t)k * C, lane, t0, t1);
 }
-
-bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
 bool finite_f(float v) { return v == v && v - v == 0.f; }
 

@@ -37,6 +37,7 @@
 
 namespace {
 
+using namespace coalign;
 constexpr int kWavesPerBlock = 4;
 constexpr int kFeatStride = 12;  // floats per staged point (<= 11 features), 48 B keeps 16 B alignment
 
@@ -550,10 +551,6 @@ __device__ __forceinline__ void pair_compute(const PfnArgs &a, const ChanParams 
 // them in lane = channel order.  Per pass: ~160 vector instructions + 4-8 matrix instructions instead of ~480.
 // Numerics: |result - fp64 evaluation| is within the fp32 rounding noise of the reference's own evaluation (tests: oracle + reference
 // goldens to 1e-4 / 1e-5 of scale as before); the canvas stays an exact copy of pillar_features.
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kRowBytes = 80;        // staged point row: [l h | m m | h h | 0 0] (4 x 16 B) + 16 B pad -> ds_read_b128 of 16 rows hits 16 distinct bank groups
 
 struct MxChan {
@@ -622,29 +619,6 @@ __device__ __forceinline__ MxChan load_mx(const PfnArgs &a, int lane) {
         mc.b2[g] = __builtin_shufflevector(s2a, s2b, 0, 1, 2, 3, 4, 5, 6, 7);
     }
     return mc;
-}
-
-__device__ __forceinline__ void swap32(float &a, float &b) {       // lanes 32-63 of a <-> lanes 0-31 of b
-    const auto q = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
-    const unsigned x = q[0], y = q[1];                              // (bit-casting q[1] directly is miscompiled by hipcc 7.2: go through locals)
-    a = __builtin_bit_cast(float, x);
-    b = __builtin_bit_cast(float, y);
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-
-// sum over each 32-lane half, result in every lane of the half: four DPP steps inside the 16-lane rows, one v_permlane16_swap across rows
-__device__ __forceinline__ float half_sum_dpp(float v) {
-    v += dppf<0xB1>(v);              // quad_perm [1, 0, 3, 2]
-    v += dppf<0x4E>(v);              // quad_perm [2, 3, 0, 1]
-    v += dppf<0x141>(v);             // row_half_mirror
-    v += dppf<0x140>(v);             // row_mirror
-    const auto q = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, v), __builtin_bit_cast(unsigned, v), false, false);
-    const unsigned x = q[0], y = q[1];          // x = [r0 r0 r2 r2], y = [r1 r1 r3 r3]
-    return __builtin_bit_cast(float, x) + __builtin_bit_cast(float, y);
 }
 
 // max of accumulator elements o .. o + 7: v_max3 on matrix-instruction results only (a two-operand fmaxf of raw results costs two extra
@@ -1022,8 +996,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void pillar_rows_mx_kernel(Pfn
     const char *np_b = reinterpret_cast<const char *>(a.npts), *cd_b = reinterpret_cast<const char *>(a.coords);
     char *cm_b = reinterpret_cast<char *>(a.cellmap), *feat_b = reinterpret_cast<char *>(a.feats), *cv_b = reinterpret_cast<char *>(canvas),
          *dest_b = reinterpret_cast<char *>(dest);
-    // a round's points go straight into LDS (issued from inline assembly: after a BUILTIN LDS-DMA hipcc puts s_waitcnt vmcnt(0) in front of every
-    // later LDS read it cannot prove unrelated -- here in front of every pass, i.e. each pass would wait for the previous pass's stores)
+    // a round's points go straight into LDS (lds_dma16's inline assembly, not the builtin: the s_waitcnt vmcnt(0) hipcc puts behind the builtin would stand in
+    // front of every pass here, i.e. each pass would wait for the previous pass's stores)
     auto issue_round = [&](int r0, int buf) {
         const int nr = min(kRound, p1 - r0);
 #pragma unroll
@@ -1031,8 +1005,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void pillar_rows_mx_kernel(Pfn
             if (k < nr) {
                 const int m = min(2 * (r0 + k) + half, a.M - 1);                       // a pillar B past the end re-reads the last pillar; its lanes store nothing
                 const char *src = pts_b + (unsigned)(m * a.P + min(col, a.P - 1)) * 16u;
-                const unsigned dst = (unsigned)(size_t)(lptr_ps_t)(pbuf + (buf * kRound + k) * 1024);   // wave-uniform LDS byte address -> M0; lane i lands at dst + 16 i
-                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(__builtin_amdgcn_readfirstlane(dst)), "v"(src) : "memory", "m0");
+                lds_dma16(reinterpret_cast<const uint4 *>(src), (unsigned)(size_t)(lptr_ps_t)(pbuf + (buf * kRound + k) * 1024));
             }
         }
     };

@@ -51,7 +51,7 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
+using namespace coalign;
 typedef __attribute__((address_space(3))) void *lptr_sp_t;
 
 constexpr int kWaves = 4;                   // wavefronts per workgroup
@@ -94,29 +94,6 @@ struct SparseArgs {
     const float4 *folded;  // the folded channel parameters written by coalign_pillar_fold_params ([7][64] float4)
     int debug;            // laboratory build only (COALIGN_SPARSE_DEBUG): 1 no stamp atomics, 2 no matrix steps, 4 no arrival counter, 8 no feature stores
 };
-
-__device__ __forceinline__ void swap32(float &a, float &b) {       // lanes 32-63 of a <-> lanes 0-31 of b
-    const auto q = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
-    const unsigned x = q[0], y = q[1];                              // (bit-casting q[1] directly is miscompiled by hipcc 7.2: go through locals)
-    a = __builtin_bit_cast(float, x);
-    b = __builtin_bit_cast(float, y);
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-
-// sum over each 32-lane half, result in every lane of the half
-__device__ __forceinline__ float half_sum_dpp(float v) {
-    v += dppf<0xB1>(v);
-    v += dppf<0x4E>(v);
-    v += dppf<0x141>(v);
-    v += dppf<0x140>(v);
-    const auto q = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, v), __builtin_bit_cast(unsigned, v), false, false);
-    const unsigned x = q[0], y = q[1];
-    return __builtin_bit_cast(float, x) + __builtin_bit_cast(float, y);
-}
 
 __device__ __forceinline__ float max16(const floatx16 &v) {
     const float t0 = fmaxf(fmaxf(v[0], v[1]), v[2]), t1 = fmaxf(fmaxf(v[3], v[4]), v[5]), t2 = fmaxf(fmaxf(v[6], v[7]), v[8]);
@@ -327,7 +304,7 @@ __global__ __launch_bounds__(kWaves * 64) void pillar_sparse_kernel(SparseArgs a
         const char *pts_b = reinterpret_cast<const char *>(a.pts);
         const char *np_b = reinterpret_cast<const char *>(a.npts), *cd_b = reinterpret_cast<const char *>(a.coords);
         char *feat_b = reinterpret_cast<char *>(a.feats);
-        // a round's points go straight into LDS (global_load_lds issued from inline assembly, see pillar_scatter.hip)
+        // a round's points go straight into LDS
         auto issue_round = [&](int r0, int buf) {
             const int nr = min(kRound, p1 - r0);
 #pragma unroll
@@ -335,8 +312,7 @@ __global__ __launch_bounds__(kWaves * 64) void pillar_sparse_kernel(SparseArgs a
                 if (k < nr && !(kLab && (a.debug & 64))) {
                     const int m = min(2 * (r0 + k) + half, a.M - 1);
                     const char *src = pts_b + (unsigned)(m * a.P + min(col, a.P - 1)) * 16u;
-                    const unsigned dst = (unsigned)(size_t)(lptr_sp_t)(pbuf + (buf * kRound + k) * 1024);
-                    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(__builtin_amdgcn_readfirstlane(dst)), "v"(src) : "memory", "m0");
+                    lds_dma16(reinterpret_cast<const uint4 *>(src), (unsigned)(size_t)(lptr_sp_t)(pbuf + (buf * kRound + k) * 1024));
                 }
             }
         };
@@ -551,12 +527,7 @@ int encode_sparse(const coalign_pillar_frame *frame, const float *voxel_features
     // 4 finish 3.5 us after those with 3 -- the kernel is bound by each SIMD's issue, so the launch ends with the busiest SIMD), pairs shared out evenly
     // (+-1): k = 1..3 workgroups per CU (40 KB of LDS each), about kPairsPerWave pairs per wavefront; larger inputs: runs of at most kRunPairs pairs, more rounds
     // of workgroups.
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
+    const int cus = cu_count();
     const int pairs = (M_capacity + 1) / 2;
     const int per_wave_target = coalign::lab_env("COALIGN_SPARSE_PAIRS", kPairsPerWave);      // laboratory build: pairs per wavefront the grid is sized for
     const int unit = cus * kWaves * per_wave_target;

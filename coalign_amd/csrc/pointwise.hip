@@ -18,7 +18,7 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
+using namespace coalign;
 
 constexpr int kMaxCin = 256;
 
@@ -234,7 +234,6 @@ __device__ __forceinline__ void pw_store_sp(const PwArgs &a, float *stage, int n
 // (image below), one 16-byte load per lane, tile, step and term, a step ahead of the matrix instructions that use them.
 // Weight image (ops.pack_pointwise_emu_weight): uint4 [M / 32 row tiles][Cin / 16 steps][3 terms][64 lanes]; lane l of (tile, step, term) holds
 // term `term` of W[k = 16 step + 8 (l / 32) + 0..7][m = 32 tile + l % 32] as 8 bf16.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ void split8(const float (&v)[8], bf16x8 (&out)[3]) {
 #pragma unroll
@@ -418,24 +417,9 @@ static int pointwise_prepare(const float *x, const float *w, const float *bias, 
 }
 
 static int pointwise_big_lds(size_t lds) {                       // beyond 64 KB of dynamic LDS the kernels need the attribute -- the merged heads of a 384-channel map -- and the
-    using namespace coalign;                                     // attribute belongs to the DEVICE's code object: one flag per device
-    static bool big_lds_dev[16] = {false};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    bool &big_lds = big_lds_dev[dev];
-    if (lds > 48 * 1024 && !big_lds) {
-        const void *fns[4] = {reinterpret_cast<const void *>(pointwise_emu_kernel<1>), reinterpret_cast<const void *>(pointwise_emu_kernel<2>),
-                              reinterpret_cast<const void *>(pointwise_emu_kernel<4>), reinterpret_cast<const void *>(pointwise_emu_multi_kernel)};
-        for (const void *fn : fns) {
-            const int rc = hip_call(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-            if (rc != COALIGN_OK) {
-                (void)hipGetLastError();
-                return rc;
-            }
-        }
-        big_lds = true;
-    }
-    return COALIGN_OK;
+    static coalign::PerDevice lds_set;                           // attribute is set once per device (common.h)
+    if (lds <= 48 * 1024) return COALIGN_OK;
+    return coalign::allow_dynamic_lds(lds_set, 96 * 1024, pointwise_emu_kernel<1>, pointwise_emu_kernel<2>, pointwise_emu_kernel<4>, pointwise_emu_multi_kernel);
 }
 
 static int pointwise_impl(const float *x, const float *w, const float *bias, float *y, int N, int Cin, int Hin, int Win,
@@ -552,7 +536,6 @@ extern "C" int coalign_pointwise_conv_emu_sp_multi(int n_layers, const void *con
 // Weight image: ops.pack_conv1x1_sp_weight of the head weights padded to 64 rows ((9g): [Cin / 16][2 terms][2 channel halves][64 rows][8 cin] + zero group + 2^-k / 2^k words).
 namespace {
 
-typedef _Float16 hd_halfx8 __attribute__((ext_vector_type(8)));
 
 struct HeadsArgs {
     const uint4 *__restrict__ x, *__restrict__ w;
@@ -586,8 +569,8 @@ __global__ __launch_bounds__(256) void heads_sp_kernel(const HeadsArgs a) {
         for (int k = 0; k < kHeadsAhead; ++k) {
             const int c = c0 + k;
             if (c < CI16) {
-                const hd_halfx8 bh = __builtin_bit_cast(hd_halfx8, xh[k]), bl = __builtin_bit_cast(hd_halfx8, xl[k]);
-                const hd_halfx8 ah = __builtin_bit_cast(hd_halfx8, wh[k]), al = __builtin_bit_cast(hd_halfx8, wl[k]);
+                const halfx8 bh = __builtin_bit_cast(halfx8, xh[k]), bl = __builtin_bit_cast(halfx8, xl[k]);
+                const halfx8 ah = __builtin_bit_cast(halfx8, wh[k]), al = __builtin_bit_cast(halfx8, wl[k]);
                 const int cn = c + kHeadsAhead;
                 load(cn < CI16 ? cn : CI16 - 1, k);                   // (the tail reloads the last step: no branch in the stream)
                 accl = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, accl, 0, 0, 0);      // w_h x_l'

@@ -1,21 +1,22 @@
-// What the V2X-ViT translation units (csrc/v2x_attn.hip, csrc/v2x_window.hip) share: the 32-pixel LDS tile of sp16 pairs and the row tile of a folded projection on
-// v_mfma_f32_32x32x16_f16 (three products per fp32 product), the weight image streamed in operand order.  Included inside each unit's anonymous namespace.
+// What the units that run small dense layers on a 32-pixel tile share (csrc/disco_fuse.hip, csrc/v2x_attn.hip, csrc/v2x_window.hip, csrc/v2x_ffn.hip): the LDS tile
+// of sp16 pairs and the row tile of a folded projection on v_mfma_f32_32x32x16_f16 (three products per fp32 product), the weight image streamed in operand order.
 #pragma once
+#include "common.h"
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
+namespace {
+
+using coalign::floatx16;
+using coalign::halfx8;
 
 constexpr int TP = 32;                         // pixels per workgroup = columns of one matrix instruction
 
 __host__ __device__ constexpr size_t image_bytes(int rows, int C) { return (size_t)(C / 16) * (rows / 32) * 64 * 32; }      // [C / 16 steps][rows / 32 tiles][64 lanes][8 h | 8 l] fp16
 __host__ __device__ constexpr int x_row_bytes(int C) { return C * 4 + 16; }                                                // a pixel's row in the LDS tile: C / 8 groups x (8 h + 8 l) + the bank pad
 
+// 8 values -> the tile's [8 h | 8 l] image of one channel group
 __device__ __forceinline__ void store_split8(char *dst, const float (&v)[8]) {
     uint4 h, l;
-    coalign::sp16_split2(v[0], v[1], h.x, l.x);
-    coalign::sp16_split2(v[2], v[3], h.y, l.y);
-    coalign::sp16_split2(v[4], v[5], h.z, l.z);
-    coalign::sp16_split2(v[6], v[7], h.w, l.w);
+    coalign::sp16_split8(v, h, l);
     *reinterpret_cast<uint4 *>(dst) = h;
     *reinterpret_cast<uint4 *>(dst + 16) = l;
 }
@@ -30,6 +31,7 @@ __device__ __forceinline__ Pair load_pair(const void *p) {
     return r;
 }
 
+// acc += w_h x_h, accl += w_h x_l' + w_l' x_h (the two terms that carry 2^10)
 __device__ __forceinline__ void mfma3(const Pair &w, const Pair &x, floatx16 &acc, floatx16 &accl) {
     accl = __builtin_amdgcn_mfma_f32_32x32x16_f16(w.h, x.l, accl, 0, 0, 0);
     accl = __builtin_amdgcn_mfma_f32_32x32x16_f16(w.l, x.h, accl, 0, 0, 0);
@@ -72,3 +74,5 @@ __device__ __forceinline__ float pixel_sum(float v, int G) {
     for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
+
+}  // namespace

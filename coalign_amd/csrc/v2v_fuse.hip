@@ -20,7 +20,7 @@
 
 namespace {
 
-struct Geom { int C, H, W, Ho, Wo; };      // what make_taps reads: source plane and output grid are the same map here
+using coalign::misaligned;
 
 struct WarpArgs {
     const float *x;          // [n, H, W, C]
@@ -154,7 +154,7 @@ extern "C" int coalign_v2v_warp_split(const float *x, int n, int R, int C, int H
     const int rc = check_counts(n, R, C, H, W, (long long)R * n, &empty);
     if (rc != COALIGN_OK || empty) return rc;
     if (!x || !theta || !y_sp) return COALIGN_ERR_NULL_POINTER;
-    if (misaligned16(x) || misaligned16(y_sp) || (reinterpret_cast<uintptr_t>(theta) & 7) || (reinterpret_cast<uintptr_t>(range_flag) & 3)) return COALIGN_ERR_UNSUPPORTED;
+    if (misaligned(x, 15) || misaligned(y_sp, 15) || (reinterpret_cast<uintptr_t>(theta) & 7) || (reinterpret_cast<uintptr_t>(range_flag) & 3)) return COALIGN_ERR_UNSUPPORTED;
     WarpArgs a;
     a.x = x; a.theta = theta; a.y = static_cast<uint4 *>(y_sp); a.range_flag = range_flag;
     a.n = n; a.R = R; a.C = C; a.H = H; a.W = W;
@@ -170,7 +170,7 @@ extern "C" int coalign_v2v_aggregate(const float *a_, const float *e, const floa
     if ((agg != COALIGN_V2V_AGG_MAX && agg != COALIGN_V2V_AGG_AVG) || (out_kind != COALIGN_V2V_OUT_NHWC && out_kind != COALIGN_V2V_OUT_SP)) return COALIGN_ERR_UNSUPPORTED;
     if (empty) return COALIGN_OK;
     if (!a_ || !e || !x || !theta || !out) return COALIGN_ERR_NULL_POINTER;
-    if (misaligned16(a_) || misaligned16(e) || misaligned16(x) || misaligned16(out) || (reinterpret_cast<uintptr_t>(theta) & 7) || (reinterpret_cast<uintptr_t>(range_flag) & 3))
+    if (misaligned(a_, 15) || misaligned(e, 15) || misaligned(x, 15) || misaligned(out, 15) || (reinterpret_cast<uintptr_t>(theta) & 7) || (reinterpret_cast<uintptr_t>(range_flag) & 3))
         return COALIGN_ERR_UNSUPPORTED;
     AggArgs a;
     a.a = a_; a.e = e; a.x = x; a.theta = theta; a.out = out; a.range_flag = out_kind == COALIGN_V2V_OUT_SP ? range_flag : nullptr;
@@ -185,7 +185,7 @@ extern "C" int coalign_v2v_gate(const float *y, int R, int Ch, int H, int W, int
     if (R == 0) return COALIGN_OK;
     if ((long long)2 * Ch * H * W * R > (long long)INT32_MAX) return COALIGN_ERR_BAD_SHAPE;
     if (!y || !out) return COALIGN_ERR_NULL_POINTER;
-    if (misaligned16(y) || misaligned16(out) || (reinterpret_cast<uintptr_t>(range_flag) & 3)) return COALIGN_ERR_UNSUPPORTED;
+    if (misaligned(y, 15) || misaligned(out, 15) || (reinterpret_cast<uintptr_t>(range_flag) & 3)) return COALIGN_ERR_UNSUPPORTED;
     GateArgs a;
     a.y = y; a.out = out; a.range_flag = out_kind == COALIGN_V2V_OUT_SP ? range_flag : nullptr;
     a.R = R; a.Ch = Ch; a.H = H; a.W = W; a.out_kind = out_kind;

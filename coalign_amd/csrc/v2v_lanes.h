@@ -38,10 +38,7 @@ __device__ __forceinline__ void store8(float *p, const float (&v)[8]) {
 template <bool STREAM = false>      // STREAM: non-temporal stores (common.h), for planes the next launch reads from another XCD anyway
 __device__ __forceinline__ bool store_split8(uint4 *y, int map, int C16, int g, int HW, int pix, const float (&v)[8], bool live) {
     uint4 h, l;
-    coalign::sp16_split2(v[0], v[1], h.x, l.x);
-    coalign::sp16_split2(v[2], v[3], h.y, l.y);
-    coalign::sp16_split2(v[4], v[5], h.z, l.z);
-    coalign::sp16_split2(v[6], v[7], h.w, l.w);
+    coalign::sp16_split8(v, h, l);
     bool big = false;
 #pragma unroll
     for (int k = 0; k < 8; ++k) big = big || fabsf(v[k]) > 65504.f;
@@ -62,7 +59,5 @@ inline unsigned blocks_of(int maps, int H, int W) {
     const long long tiles = ((long long)H * W + PW - 1) / PW;
     return (unsigned)((maps * tiles + 3) / 4);
 }
-
-inline bool misaligned16(const void *p) { return reinterpret_cast<uintptr_t>(p) & 15; }
 
 }  // namespace

@@ -22,11 +22,11 @@
 
 namespace {
 
+using coalign::misaligned;
 constexpr int kMaxAgents = 8, kMaxCav = 16, kMaxSamples = 2 * (kMaxAgents - 1);
 constexpr float kSlope = 0.01f;                     // LeakyReLU(negative_slope=0.01) of both nets
 constexpr double kPi = 3.14159265358979323846;
 
-struct Geom { int C, H, W, Ho, Wo; };
 
 __device__ __forceinline__ float lrelu(float v) { return v > 0.f ? v : v * kSlope; }
 
@@ -514,7 +514,6 @@ __global__ __launch_bounds__(256) void aggregate_kernel(const AggArgs a) {
     if (a.range_flag && big) atomicOr(a.range_flag, 1);
 }
 
-inline bool misaligned(const void *p, uintptr_t mask) { return reinterpret_cast<uintptr_t>(p) & mask; }
 
 int check_agents(int n, int L) {
     if (n < 1 || L < 1) return COALIGN_ERR_BAD_SHAPE;
@@ -532,7 +531,7 @@ extern "C" int coalign_v2vr_pool_act(const float *a_, const float *e, int P, int
     if (P == 0) return COALIGN_OK;
     if ((long long)C * H * W * P > (long long)INT32_MAX) return COALIGN_ERR_BAD_SHAPE;
     if (!a_ || !out) return COALIGN_ERR_NULL_POINTER;
-    if (misaligned16(a_) || misaligned16(e) || misaligned16(out) || misaligned(range_flag, 3)) return COALIGN_ERR_UNSUPPORTED;
+    if (misaligned(a_, 15) || misaligned(e, 15) || misaligned(out, 15) || misaligned(range_flag, 3)) return COALIGN_ERR_UNSUPPORTED;
     PoolArgs a;
     a.a = a_; a.e = e; a.out = out; a.range_flag = out_kind == COALIGN_V2V_OUT_SP ? range_flag : nullptr;
     a.P = P; a.n = e ? n : 1; a.C = C; a.H = H; a.W = W; a.out_kind = out_kind;
@@ -548,7 +547,7 @@ extern "C" int coalign_v2vr_score_head(const float *y, int n, int L, int h, int 
     if (h % 64 || h > 1024) return COALIGN_ERR_UNSUPPORTED;
     if ((long long)h * H * W * n * n > (long long)INT32_MAX) return COALIGN_ERR_BAD_SHAPE;
     if (!y || !w || !b || !alpha || !scores || !weight) return COALIGN_ERR_NULL_POINTER;
-    if (misaligned16(y) || misaligned16(w) || misaligned(b, 3) || misaligned(alpha, 3) || misaligned(scores, 3) || misaligned(weight, 3)) return COALIGN_ERR_UNSUPPORTED;
+    if (misaligned(y, 15) || misaligned(w, 15) || misaligned(b, 3) || misaligned(alpha, 3) || misaligned(scores, 3) || misaligned(weight, 3)) return COALIGN_ERR_UNSUPPORTED;
     const ScoreArgs a{y, w, b, alpha, scores, weight, n, L, h, H, W};
     hipLaunchKernelGGL(score_kernel, dim3(L * L), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     int st = coalign::check_launch();
@@ -571,7 +570,7 @@ extern "C" int coalign_v2vr_pose_head(const void *y4_sp, int n, int L, int h, in
     if (h % 64 || h > 1024) return COALIGN_ERR_UNSUPPORTED;
     if ((long long)h * H4 * W4 * n * n > (long long)INT32_MAX) return COALIGN_ERR_BAD_SHAPE;
     if (!y4_sp || !fc1_w || !fc1_b || !fc2_w || !fc2_b || !fc3_w || !fc3_b || !T || !pose_corr || !T_new || !workspace) return COALIGN_ERR_NULL_POINTER;
-    if (misaligned16(y4_sp) || misaligned16(fc1_w) || misaligned16(fc2_w) || misaligned16(fc3_w) || misaligned16(workspace) || misaligned(fc1_b, 3) || misaligned(fc2_b, 3) ||
+    if (misaligned(y4_sp, 15) || misaligned(fc1_w, 15) || misaligned(fc2_w, 15) || misaligned(fc3_w, 15) || misaligned(workspace, 15) || misaligned(fc1_b, 3) || misaligned(fc2_b, 3) ||
         misaligned(fc3_b, 3) || misaligned(T, 7) || misaligned(T_new, 7) || misaligned(pose_corr, 3))
         return COALIGN_ERR_UNSUPPORTED;
     if (workspace_bytes < coalign_v2vr_pose_head_workspace_bytes(n, h)) return COALIGN_ERR_WORKSPACE;
@@ -616,7 +615,7 @@ extern "C" int coalign_v2vr_aggregate(const float *a_, const float *e, const flo
     if (n == 0 || R == 0) return COALIGN_OK;
     if ((long long)C * H * W * R * n > (long long)INT32_MAX) return COALIGN_ERR_BAD_SHAPE;
     if (!a_ || !e || !x || !theta || !weight || !out) return COALIGN_ERR_NULL_POINTER;
-    if (misaligned16(a_) || misaligned16(e) || misaligned16(x) || misaligned16(out) || misaligned(theta, 7) || misaligned(weight, 3) || misaligned(range_flag, 3))
+    if (misaligned(a_, 15) || misaligned(e, 15) || misaligned(x, 15) || misaligned(out, 15) || misaligned(theta, 7) || misaligned(weight, 3) || misaligned(range_flag, 3))
         return COALIGN_ERR_UNSUPPORTED;
     AggArgs a;
     a.a = a_; a.e = e; a.x = x; a.weight = weight; a.theta = theta; a.out = out; a.range_flag = out_kind == COALIGN_V2V_OUT_SP ? range_flag : nullptr;

@@ -22,12 +22,11 @@
 // The caller's stream, no allocation: capturable.  Accuracy: the projections see operands rounded to 22 bits (sp16), everything else is fp32.
 #include "common.h"
 #include "warp_taps.h"
+#include "sp16_tiles.h"
 
 #include "coalign_amd_v2x.h"
 
 namespace {
-
-#include "v2x_tiles.h"
 
 constexpr int DH = COALIGN_V2X_DIM_HEAD;
 
@@ -43,7 +42,6 @@ struct V2xArgs {
     int n, R, C, H, W;
 };
 
-struct Geom { int C, H, W, Ho, Wo; };
 
 // the 8 channels [8 g, 8 g + 8) of pixel `pix` of one agent's plane: the warp's blend, or the stored values
 __device__ __forceinline__ void gather8(const float *plane, const Taps *t, int pix, int C, int g, float (&X)[8]) {

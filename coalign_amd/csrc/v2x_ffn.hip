@@ -15,12 +15,13 @@
 // 33 KB + 66 KB at (256, 512): above 64 KB the limit of dynamic LDS is raised once per device.  No workspace, no atomics: the same input gives the same bits.
 // The hidden activations are inside the fp16 range by the packer's static bound (include/coalign_amd_v2x_ffn.h): no range flag.
 #include "common.h"
+#include "sp16_tiles.h"
 
 #include "coalign_amd_v2x_ffn.h"
 
 namespace {
 
-#include "v2x_tiles.h"
+using namespace coalign;
 
 __host__ __device__ constexpr size_t off_w2(int C, int M) { return image_bytes(M, C); }
 __host__ __device__ constexpr size_t off_floats(int C, int M) { return off_w2(C, M) + image_bytes(C, M); }
@@ -118,20 +119,10 @@ __global__ __launch_bounds__(256) void v2x_ffn_kernel(const FfnArgs a) {
 template <int C>
 int launch(const FfnArgs &a, hipStream_t stream) {
     // M >= 256 (C = 256) or M >= 448 (C = 64) needs more than the 64 KB of dynamic LDS a kernel gets by default: raised once per device and instantiation
-    static bool raised[64] = {};
+    static PerDevice lds_set;
     const size_t lds = lds_bytes(C, a.M);
     if (lds > 65536) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-        if (!raised[dev]) {
-            const int rc = coalign::hip_call(hipFuncSetAttribute(reinterpret_cast<const void *>(v2x_ffn_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                                 (int)lds_bytes(C, COALIGN_V2X_FFN_MAX_HIDDEN)));
-            if (rc != COALIGN_OK) {
-                (void)hipGetLastError();
-                return rc;
-            }
-            raised[dev] = true;
-        }
+        if (const int rc = allow_dynamic_lds(lds_set, lds_bytes(C, COALIGN_V2X_FFN_MAX_HIDDEN), v2x_ffn_kernel<C>)) return rc;
     }
     hipLaunchKernelGGL(v2x_ffn_kernel<C>, dim3((unsigned)((a.tokens + TP - 1) / TP)), dim3(256), lds, stream, a);
     return coalign::check_launch();

@@ -23,12 +23,11 @@
 //   channel by a_b; after the third branch the residual x is added and the sum stored with streaming stores.
 // No atomics: the same input gives the same bits.  The caller's stream, no allocation: capturable.
 #include "common.h"
+#include "sp16_tiles.h"
 
 #include "coalign_amd_v2x_window.h"
 
 namespace {
-
-#include "v2x_tiles.h"
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 

@@ -21,6 +21,7 @@
 
 namespace {
 
+using coalign::misaligned;
 constexpr int KC = COALIGN_W2C_CHANNELS, PH = COALIGN_W2C_POOL_H, PWD = COALIGN_W2C_POOL_W, BINS = PH * PWD;
 constexpr int KF = COALIGN_W2C_FEAT, H1 = COALIGN_W2C_HIDDEN1, H2 = COALIGN_W2C_HIDDEN2, AT = COALIGN_W2C_ATT;
 constexpr int SLICES = 16, SLICE_K = KF / SLICES, SLICE_Q = SLICE_K / 4;      // 280 inputs = 70 float4 per slice: 8 channels x 35 bins
@@ -224,7 +225,6 @@ constexpr int PW = 16;      // pixels per wavefront
 constexpr int GL = 4;       // channel groups in flight per pixel (lanes per pixel)
 constexpr int CHUNK = 8;    // 8-channel groups per wavefront and pixel tile (blockIdx.y walks the chunks): 64 channels, two per lane
 
-struct Geom { int C, H, W, Ho, Wo; };
 
 struct FuseArgs {
     const float *x;          // [n, H, W, C]
@@ -277,7 +277,6 @@ __global__ __launch_bounds__(256) void w2c_fuse_kernel(const FuseArgs a) {
     }
 }
 
-inline bool misaligned(const void *p, uintptr_t mask) { return reinterpret_cast<uintptr_t>(p) & mask; }
 
 }  // namespace
 

@@ -22,6 +22,7 @@
 
 namespace {
 
+using coalign::misaligned;
 constexpr int kMsgLevels = 3, kMsgAgents = 8;
 
 // ---- (1) index ------------------------------------------------------------------------------------------------------------------------------------------------------
@@ -201,7 +202,6 @@ __global__ __launch_bounds__(256) void w2comm_fuse_packed_kernel(const PackedFus
     COALIGN_W2COMM_FUSE_BLOCK(NA, f);
 }
 
-inline bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
 // the checks the three entry points share: -> COALIGN_OK or the refusal
 inline int check_counts(int n, int levels) {

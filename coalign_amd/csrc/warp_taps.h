@@ -13,8 +13,10 @@ struct Taps {
 
 // grid_sample geometry of output pixel (ox, oy) in agent n's plane, reference arithmetic (identical to warp_fuse.hip):
 // F.affine_grid on a float64 theta -> .to(float32) -> (g + 1) * (size / 2) - 0.5 -> floor / floor + 1 taps, masked weights
-template <class Geom>      // Geom: the members C, H, W (source plane) and Ho, Wo (output grid)
-__device__ __forceinline__ Taps make_taps(const Geom &a, const double *theta, int n, int ox, int oy) {
+struct Geom { int C, H, W, Ho, Wo; };      // what make_taps reads: source plane and output grid (the same map in the fusion kernels that build one per tile)
+
+template <class G>      // G: Geom, or a kernel's argument record with the members C, H, W (source plane) and Ho, Wo (output grid)
+__device__ __forceinline__ Taps make_taps(const G &a, const double *theta, int n, int ox, int oy) {
     const double xn = (2.0 * ox + 1.0) / a.Wo - 1.0;
     const double yn = (2.0 * oy + 1.0) / a.Ho - 1.0;
     const double *th = theta + n * 6;

@@ -602,3 +602,31 @@ def test_skip_weight_image_layout_and_values():
     amax = (w.reshape(co, ci).abs() * scale.reshape(co, 1)).amax(dim=1)
     live = w.reshape(co, ci).abs().amax(dim=1) > 0
     assert bool(((amax[live] >= 2.0 ** 13) & (amax[live] < 2.0 ** 14)).all())             # every channel's largest weight in [2^13, 2^14): both terms normal fp16 numbers
+
+
+def test_csrc_has_one_copy_of_each_shared_piece():
+    """csrc: the LDS-DMA statement, the dynamic-LDS attribute call, swap32, Geom and misaligned each exist in ONE file (common.h; Geom beside make_taps in
+    warp_taps.h) -- a fix to one of them is made once.  Comments that mention a name do not count."""
+    import glob
+    import re
+    from coalign_amd import build
+    code = {}
+    for path in sorted(glob.glob(os.path.join(build.CSRC, "*"))):
+        if os.path.isfile(path):
+            text = open(path, encoding="utf-8").read()
+            code[os.path.basename(path)] = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    assert set(build.SOURCES + build.LAB_ONLY_SOURCES) <= set(code)
+
+    def files(pattern):
+        return sorted(name for name, text in code.items() if re.search(pattern, text, flags=re.S))
+
+    def count(pattern):
+        return sum(len(re.findall(pattern, text)) for text in code.values())
+
+    assert files(r"asm volatile\([^;]*global_load_lds") == ["common.h"]
+    assert count(r"asm volatile\([^;]*global_load_lds") == 1
+    assert files(r"hipFuncSetAttribute\(") == ["common.h"]
+    assert files(r"\bvoid swap32\(") == ["common.h"]
+    assert files(r"\bstruct Geom\b") == ["warp_taps.h"] and count(r"\bstruct Geom\b") == 1
+    assert files(r"\bbool misaligned\(") == ["common.h"] and count(r"\b\w[\w:<>\*& ]* misaligned\([^;{)]*\)\s*\{") == 1
+    assert count(r"\bmisaligned16\b") == 0

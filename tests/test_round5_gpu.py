@@ -238,6 +238,31 @@ def test_conv3x3_sp_equals_consumer_split_kernel_bit_for_bit(shape, geometry):
     assert not ops.sp_range_exceeded(DEV)
 
 
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs in one process")
+def test_conv3x3_emu_on_a_second_device_of_the_process():
+    """The dynamic-LDS attribute of a kernel belongs to the DEVICE's code object (csrc/common.h allow_dynamic_lds): conv3x3_emu.hip kept one flag per process,
+    so the second GPU of a process launched without it.  Device 0 first, then device 1, same inputs: equal bits.  The route: terms 16 on the tap-major weight
+    image, (Cin, Cout) = (16, 64) on an 8 x 8 map -> dispatch_tapk's stacked 4 x 8-block tiles, Geo<4, 8, 8, 2, 2, 1, 1, TAPK, STACK | NBX4>: two weight buffers of
+    36 864 bytes + one split patch of 12 x 40 pixels = 104 448 bytes of LDS, beyond the 64 KB a kernel gets without the attribute.  On device 0 the output also
+    equals conv3x3_sp's bit for bit (the test above)."""
+    N, Ci, Co, H, W = 1, 16, 64, 8, 8
+    g = torch.Generator().manual_seed(58)
+    x = torch.randn((N, Ci, H, W), generator=g)
+    w = torch.randn((Co, Ci, 3, 3), generator=g) / (9 * Ci) ** 0.5
+    b = torch.randn(Co, generator=g)
+    outs = []
+    for dev in ("cuda:0", "cuda:1"):
+        xd = round22(x.to(dev))
+        w16 = ops.pack_conv3x3_emu_weight(w.to(dev), 16, True)
+        outs.append(ops.conv3x3_emu_bias_act(xd, w16, b.to(dev), Co, None, True, 16))
+        torch.cuda.synchronize(dev)
+        if dev == "cuda:0":
+            sp = ops.conv3x3_sp(ops.SplitMap.pack(xd), w16, b.to(dev), Co, None, True, out_split=False, geometry=100000 + 81)
+            assert torch.equal(sp, outs[0])
+    assert float(outs[0].abs().max()) > 0.1
+    assert torch.equal(outs[0].cpu(), outs[1].cpu())
+
+
 # dispatch_sp's geometry = 0 rule (csrc/conv3x3_sp.hip) on the backbone shapes (ids shape0 ... shape5: 121, 124, 148, 81 + the automatic stream-K cut, 121 -> 81,
 # the remaining 81) and on shapes that reach its other branches.  The 12-wavefront fallbacks depend on the CU count: the ids assume the MI355X's 256.
 SP_GEO0_SHAPES = [pytest.param(s, id=f"shape{i}") for i, s in enumerate([(5, 64, 64, 100, 352), (5, 128, 128, 50, 176), (5, 256, 256, 25, 88), (1, 256, 256, 100, 352),
