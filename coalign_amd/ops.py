@@ -1701,14 +1701,26 @@ def v2x_attn_shape_ok(channels: int, heads: int, dim_head: int, n_agents: int = 
     return channels in (64, 256) and dim_head == V2X_DIM_HEAD and heads * dim_head == channels and 1 <= n_agents <= 8
 
 
+def _v2x_value_bound(w: torch.Tensor, b: torch.Tensor) -> float:
+    """max_r ||w_r||_2 sqrt(C) + |b_r| in float64 over the rows of a folded value projection w [rows, C], b [rows]: with sum yhat^2 <= C (yhat = (x - mean) /
+    sqrt(var + eps)) no token's |w yhat + b|_r exceeds it (Cauchy-Schwarz), and a softmax-weighted mean of such rows does not either.  NaN / inf when the
+    operands are not finite (a comparison ``< 65504`` is then false)."""
+    w, b = w.detach().double(), b.detach().double().reshape(-1)
+    return float((w.norm(dim=1) * float(w.shape[1]) ** 0.5 + b.abs()).max())
+
+
 def pack_v2x_weights(wqkv: torch.Tensor, bqkv: torch.Tensor, wa: torch.Tensor, ba: torch.Tensor) -> Optional[torch.Tensor]:
     """The folded agent-attention layer (wqkv [3C, C] = [q | k' | v'] rows, bqkv [3C], wa [C, C], ba [C]) -> the parameter image of ``coalign_v2x_agent_attention``
-    (layout: the header's (13a)), a uint8 tensor on the weights' device; None when a weight lies outside the fp16 range (its sp16 pair would saturate)."""
+    (layout: the header's (13a)), a uint8 tensor on the weights' device.  None when a weight lies outside the fp16 range (its sp16 pair would saturate), or when
+    an attention output could reach its end: o is a convex combination of the senders' v' rows and enters the output projection as fp16 pairs, and
+    |v'|_r <= ``_v2x_value_bound`` for every token -- a static guarantee in place of a device flag, as ``pack_v2x_ffn_weights`` gives."""
     wqkv, wa = wqkv.detach().float(), wa.detach().float()
     C = wa.shape[0]
-    if tuple(wqkv.shape) != (3 * C, C) or tuple(wa.shape) != (C, C) or C not in (64, 256):
-        raise ValueError("pack_v2x_weights: wqkv [3C, C], wa [C, C], C = 64 or 256")
+    if tuple(wqkv.shape) != (3 * C, C) or tuple(wa.shape) != (C, C) or C not in (64, 256) or bqkv.numel() != 3 * C:
+        raise ValueError("pack_v2x_weights: wqkv [3C, C], bqkv [3C], wa [C, C], C = 64 or 256")
     if not bool(torch.isfinite(wqkv).all() and torch.isfinite(wa).all()) or max(float(wqkv.abs().max()), float(wa.abs().max())) > 65504.0:
+        return None
+    if not _v2x_value_bound(wqkv[2 * C:], bqkv.detach().reshape(-1)[2 * C:]) < 65504.0:
         return None
     floats = torch.cat([bqkv.detach().float().reshape(-1), ba.detach().float().reshape(-1)])
     img = torch.cat([_disco_operand_image(wqkv), _disco_operand_image(wa), floats.contiguous().view(torch.uint8)])
@@ -1762,13 +1774,18 @@ def v2x_window_shape_ok(channels: int, heads, dim_heads, windows, fuse: str, rel
 def pack_v2x_window_weights(wqkv: torch.Tensor, bqkv: torch.Tensor, wout: torch.Tensor, bout: torch.Tensor, pos: Sequence[torch.Tensor], split=None) -> Optional[torch.Tensor]:
     """The folded window-attention layer (``v2xvit.folded_window_attention``: wqkv [9C, C], bqkv [9C], wout [3, C, C], bout [3, C], pos = the three position tables;
     ``split`` = (fc1.weight, bn1.weight, bn1.bias, fc2.weight) of the split attention or None for ``naive``) -> the parameter image of
-    ``coalign_v2x_window_attention`` (layout: the header's (14a)), a uint8 tensor on the weights' device; None when a weight of the matrix layers lies outside the
-    fp16 range (its sp16 pair would saturate)."""
+    ``coalign_v2x_window_attention`` (layout: the header's (14a)), a uint8 tensor on the weights' device.  None when a weight of the matrix layers lies outside the
+    fp16 range (its sp16 pair would saturate), or when an attention output could reach its end: o_b is a convex combination of branch b's v rows and enters the
+    output projection as fp16 pairs, and |v_b|_r <= ``_v2x_value_bound`` for every token -- a static guarantee in place of a device flag."""
     wqkv, wout = wqkv.detach().float(), wout.detach().float()
     C = wout.shape[-1]
-    if tuple(wqkv.shape) != (9 * C, C) or tuple(wout.shape) != (3, C, C) or not (C == 256 or (C == 64 and split is None)) or [tuple(p.shape) for p in pos] != [(7, 7), (15, 15), (31, 31)]:
-        raise ValueError("pack_v2x_window_weights: wqkv [9C, C], wout [3, C, C], tables 7 x 7, 15 x 15, 31 x 31, C = 256 or (naive) 64")
+    if (tuple(wqkv.shape) != (9 * C, C) or tuple(wout.shape) != (3, C, C) or not (C == 256 or (C == 64 and split is None)) or bqkv.numel() != 9 * C
+            or [tuple(p.shape) for p in pos] != [(7, 7), (15, 15), (31, 31)]):
+        raise ValueError("pack_v2x_window_weights: wqkv [9C, C], bqkv [9C], wout [3, C, C], tables 7 x 7, 15 x 15, 31 x 31, C = 256 or (naive) 64")
     if not bool(torch.isfinite(wqkv).all() and torch.isfinite(wout).all()) or max(float(wqkv.abs().max()), float(wout.abs().max())) > 65504.0:
+        return None
+    bflat = bqkv.detach().reshape(-1)
+    if not all(_v2x_value_bound(wqkv[3 * C * b + 2 * C:3 * C * (b + 1)], bflat[3 * C * b + 2 * C:3 * C * (b + 1)]) < 65504.0 for b in range(3)):
         return None
     floats = [bqkv.detach().float().reshape(-1), bout.detach().float().reshape(-1)] + [p.detach().float().reshape(-1) for p in pos] + [wqkv.new_zeros(1)]
     if split is not None:

@@ -554,6 +554,12 @@ class V2XViTFusion(nn.Module):
                 return f"the map's {channels} channels are not the transformer's dim {att.q_linears[0].in_features}"
         return None
 
+    def kernel_weight_reason(self) -> Optional[str]:
+        """None when every agent-attention layer packs (``packed``); else why not.  Asked after ``kernel_shape_reason``: the packer takes the kernel's shapes only."""
+        if self.packed() is None:
+            return "a folded agent-attention weight, or the static bound of an attention output, lies outside the fp16 range"
+        return None
+
     def _windows(self):
         return [blk[1].fn for layer in self.fusion_net.encoder.layers for blk in layer[0].layers]
 
@@ -573,6 +579,8 @@ class V2XViTFusion(nn.Module):
                         f"16 / 32 / 64 channels a head on 256 channels (64: naive only)")
         if hw is not None and (int(hw[0]) % 16 or int(hw[1]) % 16):
             return f"a {int(hw[0])} x {int(hw[1])} map: H and W must be multiples of 16"
+        if self.packed_windows() is None:
+            return "a folded window-attention weight, or the static bound of an attention output, lies outside the fp16 range"
         return None
 
     def _feed_forwards(self):
@@ -615,6 +623,8 @@ class V2XViTFusion(nn.Module):
 
     def plan_fusion(self, channels: int, terms: Optional[int] = None):
         """-> (``routes.plan``'s fusion line, whether it is a fallback, {layers noted with it: (line, fallback)})."""
+        if self.kernel_route(channels) and self.kernel_weight_reason() is not None:
+            return f"{self.TORCH} ({self.kernel_weight_reason()})", True, {}
         if self.kernel_route(channels):
             window = self.window_kernel_reason(channels) is None
             if self.ffn_kernel_reason(channels) is None:
@@ -626,7 +636,7 @@ class V2XViTFusion(nn.Module):
         """-> (line, fallback) of one of the transformer's linears."""
         if not isinstance(layer, nn.Linear):
             return None
-        ok, leaf = self.kernel_route(channels), name.split(".")
+        ok, leaf = self.kernel_route(channels) and self.kernel_weight_reason() is None, name.split(".")
         typed = leaf[-2] in ("q_linears", "k_linears", "v_linears", "a_linears")
         if name.endswith("prior_feed") or (typed and leaf[-1] != "0"):
             return self.UNREAD, False
@@ -692,7 +702,7 @@ class V2XViTFusion(nn.Module):
     # ---- the kernel route --------------------------------------------------------------------------------------------------------------------------------------
     def packed(self) -> Optional[List[torch.Tensor]]:
         """The parameter image of every agent-attention layer (``ops.pack_v2x_weights`` of ``folded_agent_attention``), cached until a parameter changes; None when a
-        folded weight lies outside the fp16 range."""
+        folded weight or the static bound of an attention output lies outside the fp16 range."""
         def build():
             imgs = [ops.pack_v2x_weights(*folded_agent_attention(norm, att, True)) for norm, att, _, _, _ in self._schedule(1)]
             return (None if any(i is None for i in imgs) else imgs,)
@@ -700,7 +710,7 @@ class V2XViTFusion(nn.Module):
 
     def packed_windows(self) -> Optional[List[torch.Tensor]]:
         """The parameter image of every window-attention layer (``ops.pack_v2x_window_weights`` of ``folded_window_attention``), cached until a parameter changes; None
-        when a folded weight lies outside the fp16 range."""
+        when a folded weight or the static bound of an attention output lies outside the fp16 range."""
         def build():
             imgs = []
             for _, _, _, pw, _ in self._schedule(1):

@@ -24,7 +24,9 @@ extern "C" {
  *        j = 0 .. 7, as an sp16 pair (h = the value rounded to 22 bits, then to fp16 to nearest; l = (that value - h) * 2^10); rows [0, C) the queries, [C, 2C) the
  *        keys, [2C, 3C) the values, head m in rows 32 m .. 32 m + 31 of each;
  *   Wa   [C / 16 steps][C / 32 row tiles][64 lanes][8 h | 8 l] fp16: a_linears[0];
- *   4C floats: bqkv[3C], ba[C]. */
+ *   4C floats: bqkv[3C], ba[C].
+ * The attention output o = sum_j att_ij v'_j enters Wa as sp16 pairs: the host packs only weights for which |Wv' yhat + bv'| stays below 65504 for EVERY token
+ * (sum yhat^2 <= C, hence |.|_r <= ||Wv'_r||_2 sqrt(C) + |bv'_r| for the rows [2C, 3C); o is a convex combination of such rows), so the kernel carries no range flag. */
 size_t coalign_v2x_param_bytes(int C);
 
 /* (13b) Bytes of the workspace (13c) needs: the projections [n][H W][3C] float32 of opencood/models/sub_modules/hmsa.py:7-151, written by its first launch and read

@@ -31,7 +31,10 @@ extern "C" {
  *   floats: bqkv[9C], bout[3][C] (to_out[0].bias), then COALIGN_V2X_WINDOW_POS_FLOATS floats: pos_embedding of branch 0 (7 x 7, row-major), branch 1 (15 x 15),
  *        branch 2 (31 x 31), one zero;
  *   fuse = split attention only, all float32: WoutT[3][C][C] (WoutT[b][k][c] = to_out[0].weight[c][k] of branch b), fc1T[C][C] (fc1T[k][c] = fc1.weight[c][k]),
- *        bn1.weight[C], bn1.bias[C], fc2T[C][3C] (fc2T[k][r] = fc2.weight[r][k]). */
+ *        bn1.weight[C], bn1.bias[C], fc2T[C][3C] (fc2T[k][r] = fc2.weight[r][k]).
+ * The attention outputs o_b enter Wout_b as sp16 pairs: the host packs only weights for which |Wv_b yhat + bv_b| stays below 65504 for EVERY token (sum yhat^2 <= C,
+ * hence |.|_r <= ||Wv_b,r||_2 sqrt(C) + |bv_b,r| for the rows [3C b + 2C, 3C b + 3C) of every branch; o_b is a convex combination of such rows), so the kernels carry
+ * no range flag. */
 size_t coalign_v2x_window_param_bytes(int C, int fuse);
 
 /* (14b) Bytes of the workspace (14c) needs; 0 for a shape (14c) does not take.  It holds, all float32 and all three branches at once: the projections
