@@ -85,8 +85,16 @@ struct Geo {
     static constexpr int WQ_SRC = 9 * 2 * 2 * kCoutTile;                       // ... in the weight image (64 output channels per block)
     static constexpr int WINS = WQ / 64;
     static constexpr int W_BYTES = WQ * 16, B_BYTES = 4 * PIXP * 16;
-    static constexpr size_t LDS_BYTES = 2 * (size_t)W_BYTES + 2 * (size_t)B_BYTES;      // both operands double buffered (Work::LDS_BYTES: what a mode really takes)
-    static_assert(W_BYTES + B_BYTES <= 160 * 1024, "geometry does not fit the 160 KB LDS");
+    static constexpr size_t OPERAND_BYTES = 2 * (size_t)W_BYTES + 2 * (size_t)B_BYTES;  // both operands double buffered
+    static constexpr size_t LDS_BYTES = OPERAND_BYTES + 2 * kMaxCoutLds * sizeof(float);      // + the layer's bias | 2^-k_c words (round 6: the epilogue reads them from LDS)
+    static_assert(LDS_BYTES <= 160 * 1024, "geometry does not fit the 160 KB LDS");
+    // Every wavefront issues its share of the next interval's LDS-DMA (WJ 1 KB pieces of the weights, PJ pieces of each of the four patch planes) between its matrix
+    // instructions: with 12 wavefronts one or two instructions behind each tap, with 8 FRONT-loaded, two behind each of the first taps.  Round 6, front-loading:
+    // with the progress-based priority the wavefronts of a SIMD finish together, and the interval's closing s_waitcnt no longer waits ~300 clocks for a piece issued
+    // behind the last tap -- stage 3 44.6-45.4 -> 43.4-43.8 us, shrink header 2nd 120.0-120.3 -> 116.7-117.0 (profiles/round6/experiments/conv_sp_geometry_modes.txt);
+    // the 12-wavefront geometries gain nothing from it (47.2-47.9 -> 47.7-48.3, 41.1-41.3 -> 41.6-41.7).  Same arithmetic, same bits.
+    static constexpr int WJ = (WINS + WAVES - 1) / WAVES, PJ = (PINS + WAVES - 1) / WAVES, OPS = WJ + 4 * PJ;
+    static constexpr bool FRONT = NPB == 8;
 };
 
 struct Tile {
@@ -96,44 +104,9 @@ struct Tile {
 enum { SP_OUT_SP = 1, SP_OUT_NHWC = 2, SP_OUT_BOTH = 3 };
 enum { SP_RES_NONE = 0, SP_RES_SP = 1, SP_RES_NHWC = 2 };
 
-// MODE: who issues the LDS-DMA of the next interval, and when (measured: tools/trace_conv_sp.py)
-//   0  every wavefront its share, all at once behind the interval's barrier (the matrix pipe idles until the texture addresser has taken the ~70 instructions);
-//   1  every wavefront its share, one or two instructions behind each tap's matrix instructions;
-//   2  LOADER wavefronts: the first four wavefronts (one per SIMD) issue everything, the others start their matrix steps straight away -- a SIMD's
-//      loader runs its steps when its partners have finished theirs, the pipe never waits for the addresser;
-//   3  one EXTRA wavefront per workgroup that only issues the DMA (8-wavefront geometries: 9 wavefronts = three per SIMD within the register budget):
-//      the computing wavefronts' instruction streams are ds_read + matrix instructions only;
-//   4  as 1, the tap's DMA instructions IN FRONT of its matrix instructions;   5  as 1, front-loaded: two instructions behind each of the first taps.
-//   7  (round 6) as 3 with FOUR loader wavefronts, one per SIMD (8-wavefront geometries: 12 wavefronts = three per SIMD within the register budget): 17 DMA
-//      instructions per loader and interval instead of 68 on one -- the computing wavefronts' streams are ds_read + matrix instructions only;
-//   6  (round 6) TWO WORKGROUPS PER CU, out of phase: ONE weight buffer + ONE patch buffer (65-70 KB of LDS on the 8-wavefront geometries), registers capped at
-//      128 (four wavefronts per SIMD), every wavefront issues its share of the next interval's DMA at once behind the barrier that ends an interval and waits for it.
-//      A workgroup alone would expose the DMA latency every interval; its PARTNER on the CU runs matrix steps meanwhile (and through the other one's tile prologue,
-//      epilogue and barrier waits: profiles/round5/experiments/conv_sp_epilogue_phases.md named this remedy).  The workgroup in the CU's odd slot (HW_ID.TG_ID) issues
-//      at a higher priority, so that two workgroups that start in step fall out of step instead of sharing the pipe and then loading together.
-template <int BH, int BW, int NPB, int NBX, int MODE, int CT = 64>
-struct Work {
+template <int BH, int BW, int NPB, int NBX, int OUT, bool SPLIT, int CT = 64>
+__global__ __launch_bounds__(64 * NPB, (NPB + 3) / 4) void conv3x3_sp_kernel(const SpArgs a) {
     using G = Geo<BH, BW, NPB, NBX, CT>;
-    static constexpr int EXTRA = MODE == 3 ? 1 : MODE == 7 ? 4 : 0;             // loader-only wavefronts on top of the computing ones (MODE 7, round 6: one per SIMD)
-    static constexpr int LOADERS = MODE == 2 ? 4 : EXTRA ? EXTRA : G::WAVES;
-    static constexpr bool INTERLEAVED = MODE == 1 || MODE == 4 || MODE == 5;
-    static constexpr bool PAIRED = MODE == 6;                                   // two workgroups per CU, single buffers
-    static constexpr int NBUF = PAIRED ? 1 : 2;
-    static constexpr size_t OPERAND_BYTES = (size_t)NBUF * ((size_t)G::W_BYTES + (size_t)G::B_BYTES);
-    static constexpr size_t LDS_BYTES = OPERAND_BYTES + 2 * kMaxCoutLds * sizeof(float);      // + the layer's bias | 2^-k_c words (round 6: the epilogue reads them from LDS)
-    static constexpr int WAVES_PER_EU = PAIRED ? 4 : (NPB + 3) / 4;              // (the defaults the work-group size implies, except for the paired mode's cap)
-    static_assert(!PAIRED || NPB == 8, "two workgroups per CU: 8-wavefront geometries (16 wavefronts per CU = 4 per SIMD at 128 registers)");
-    static_assert(!PAIRED || 2 * LDS_BYTES <= 160 * 1024, "two workgroups of this geometry do not fit the 160 KB LDS");
-    static_assert(LDS_BYTES <= 160 * 1024, "geometry does not fit the 160 KB LDS in this mode");
-    static constexpr int THREADS = G::THREADS + 64 * EXTRA;
-    static constexpr int WJ = (G::WINS + LOADERS - 1) / LOADERS, PJ = (G::PINS + LOADERS - 1) / LOADERS, OPS = WJ + 4 * PJ;
-};
-
-template <int BH, int BW, int NPB, int NBX, int OUT, int MODE, bool SPLIT, int CT = 64>
-__global__ __launch_bounds__(64 * NPB + (MODE == 3 ? 64 : MODE == 7 ? 256 : 0), (MODE == 6 ? 4 : MODE == 7 ? (NPB + 7) / 4 : (NPB + 3) / 4)) void conv3x3_sp_kernel(const SpArgs a) {
-    using G = Geo<BH, BW, NPB, NBX, CT>;
-    using K = Work<BH, BW, NPB, NBX, MODE, CT>;
-    static_assert(!(K::PAIRED && SPLIT), "the paired mode runs whole tiles");
     static_assert(CT == 64 || !SPLIT, "stream-K hand-overs carry 64-channel tiles");
     constexpr int NQ = G::NQ, NG8 = G::NG8;
     extern __shared__ __attribute__((aligned(1024))) char lds[];
@@ -144,16 +117,17 @@ __global__ __launch_bounds__(64 * NPB + (MODE == 3 ? 64 : MODE == 7 ? 256 : 0), 
     // Round 6: bias | 2^-k_c of every output channel -> LDS, once per workgroup.  The epilogue used to load them from memory: ~800 clocks of exposed latency per
     // tile, and the vmcnt wait the compiler puts in front of their first use also waits for the next tile's LDS-DMA (invisible to its counter model).  The first
     // interval's s_waitcnt + barrier orders these stores before any epilogue.
-    float *lds_par = reinterpret_cast<float *>(lds + K::OPERAND_BYTES);
-    for (int i = tid; i < a.Cout / 4; i += K::THREADS) {
+    float *lds_par = reinterpret_cast<float *>(lds + G::OPERAND_BYTES);
+    for (int i = tid; i < a.Cout / 4; i += G::THREADS) {
         reinterpret_cast<float4 *>(lds_par)[i] = reinterpret_cast<const float4 *>(a.bias)[i];
         reinterpret_cast<float4 *>(lds_par + a.Cout)[i] = reinterpret_cast<const float4 *>(a.wscale)[i];
     }
-    // LDS map: weight buffers 0 | 1, patch buffers 0 | 1 (paired mode: one of each)
+    // LDS map: weight buffers 0 | 1, patch buffers 0 | 1
     int member_cg = 0;                                                        // (set below, before decode() is first called)
-    const bool loader = K::EXTRA ? wave >= G::WAVES : wave < K::LOADERS, compute = wave < G::WAVES;
-    const int lw = K::EXTRA ? (wave >= G::WAVES ? wave - G::WAVES : 0) : wave;      // index among the loaders
-
+    // Always true: a workgroup has WAVES wavefronts, each computes and issues its share.  The compiler does not know it (readfirstlane), and the register
+    // allocation of every instantiation depends on this test standing here: without it all of them are scheduled differently.  Kept so that the device code stays
+    // the measured one; removing it is a change of the kernel, to be measured as one.
+    const bool in_tile = wave < G::WAVES;
     const int blk_y = wave / NBX, blk_x = wave - blk_y * NBX;                 // this wavefront's pixel block inside the tile
     // Lane -> pixel inside the block.  2 x 16 blocks (PW = 18: a patch row is 288 bytes = 256 + 32): row 1's columns are rotated by two, so that the four lane
     // groups a ds_read_b128 is served in ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ...) touch disjoint banks -- unrotated, row 1 sits 32 bytes into row 0's
@@ -184,11 +158,11 @@ __global__ __launch_bounds__(64 * NPB + (MODE == 3 ? 64 : MODE == 7 ? 256 : 0), 
         }
         return c;
     };
-    // Patch plan of a tile: the lane's group of DMA instruction (wave + LOADERS * j) of a plane = patch pixel 64 * (wave + LOADERS * j) + lane; its offset (in
+    // Patch plan of a tile: the lane's group of DMA instruction (wave + WAVES * j) of a plane = patch pixel 64 * (wave + WAVES * j) + lane; its offset (in
     // 16-byte groups) inside plane 0 of interval 0, or -1 for zero padding.  Patch rows (see conv3x3_emu.hip): 0 .. yb rows yl0 - 1 .. H - 1 of image n0,
     // yb + 1 and yb + 2 zero, yb + 3 .. rows 0 .. of image n0 + 1; without a boundary inside the tile (yb >= TH) rows yl0 - 1 .. yl0 + TH.
     struct Plan {
-        int off[K::PJ];
+        int off[G::PJ];
         const uint4 *wsrc;
     };
     auto make_plan = [&](const Tile &t) {
@@ -197,8 +171,8 @@ __global__ __launch_bounds__(64 * NPB + (MODE == 3 ? 64 : MODE == 7 ? 256 : 0), 
         pl.wsrc = CT == 64 ? a.wt + (size_t)t.cg * chunks * G::WQ_SRC + lane
                            : a.wt + (size_t)(t.cg >> 1) * chunks * G::WQ_SRC + (lane >> 5) * kCoutTile + (t.cg & 1) * 32 + (lane & 31);
 #pragma unroll
-        for (int j = 0; j < K::PJ; ++j) {
-            const int i = (lw + K::LOADERS * j) * 64 + lane;
+        for (int j = 0; j < G::PJ; ++j) {
+            const int i = (wave + G::WAVES * j) * 64 + lane;
             const int y = i / G::PW, xq = i - y * G::PW, gx = t.x0 - 1 + xq;
             bool ok = i < G::PIX && xq < G::PWU && gx >= 0 && gx < a.W;
             int gy, img = 0;
@@ -213,18 +187,18 @@ __global__ __launch_bounds__(64 * NPB + (MODE == 3 ? 64 : MODE == 7 ? 256 : 0), 
     };
     // DMA operation k of this wavefront for interval c into buffer `slot`: k < WJ a 1 KB piece of the weights, then the four planes of patch piece j
     auto issue_op = [&](const Plan &pl, int c, int slot, int k) {
-        if (k < K::WJ) {
-            const int ins = lw + K::LOADERS * k;
+        if (k < G::WJ) {
+            const int ins = wave + G::WAVES * k;
             if (ins < G::WINS && !SP_ABLATE(1)) lds_dma16(pl.wsrc + (size_t)c * G::WQ_SRC + ins * (64 * kCoutTile / CT), lds0 + slot * G::W_BYTES + ins * 1024);
         } else {
-            const int j = (k - K::WJ) / 4, q = (k - K::WJ) % 4, ins = lw + K::LOADERS * j;
+            const int j = (k - G::WJ) / 4, q = (k - G::WJ) % 4, ins = wave + G::WAVES * j;
             if (ins < G::PINS && !SP_ABLATE(2))
-                lds_dma16(pl.off[j] < 0 ? a.zero : a.x + (size_t)pl.off[j] + ((size_t)c * 4 + q) * HW, lds0 + K::NBUF * G::W_BYTES + slot * G::B_BYTES + (q * G::PIXP + ins * 64) * 16);
+                lds_dma16(pl.off[j] < 0 ? a.zero : a.x + (size_t)pl.off[j] + ((size_t)c * 4 + q) * HW, lds0 + 2 * G::W_BYTES + slot * G::B_BYTES + (q * G::PIXP + ins * 64) * 16);
         }
     };
     auto issue_all = [&](const Plan &pl, int c, int slot) {
 #pragma unroll
-        for (int k = 0; k < K::OPS; ++k) issue_op(pl, c, slot, k);
+        for (int k = 0; k < G::OPS; ++k) issue_op(pl, c, slot, k);
     };
 
     // Persistent workgroups.  Whole tiles g, g + n, ... -- or, stream-K (a.split), the (tile, interval) steps cut into n equal contiguous ranges, so that
@@ -261,39 +235,12 @@ __global__ __launch_bounds__(64 * NPB + (MODE == 3 ? 64 : MODE == 7 ? 256 : 0), 
     int tile = SPLIT ? s0 / chunks : g, chunk0 = SPLIT ? s0 - tile * chunks : 0;
     const int tile_step = SPLIT ? 1 : n_wg;
     Tile cur = decode(tile);
-    if constexpr (K::EXTRA != 0) {
-        static_assert(!SPLIT, "the loader wavefronts mirror the whole-tile schedule only (their barriers must match the computing wavefronts')");
-        if (wave >= G::WAVES) {                                    // a loader wavefront: one barrier per interval like everybody else, nothing but DMA issue
-            __builtin_amdgcn_s_setprio(3);
-            Plan pl = make_plan(cur);
-            issue_all(pl, 0, 0);
-            int chunk = 0;
-            for (int l = 0; l < n_local; ++l) {
-                __builtin_amdgcn_s_waitcnt(0);
-                __syncthreads();
-                if (l + 1 < n_local) {
-                    if (++chunk == chunks) {
-                        chunk = 0;
-                        tile += tile_step;
-                        pl = make_plan(decode(tile));
-                    }
-                    issue_all(pl, chunk, (l + 1) & 1);
-                }
-            }
-            return;
-        }
-    }
-    const bool loader_here = K::EXTRA ? false : loader;            // (MODE 3 / 7: the computing wavefronts carry no plan and issue nothing)
     Plan plan{};
-    if (loader_here) {
+    if (in_tile) {
         plan = make_plan(cur);
         issue_all(plan, chunk0, 0);
     }
-    if constexpr (K::PAIRED) {
-        // HW_REG_HW_ID (register 4) bits 16-19 = TG_ID: the workgroup's slot on its CU.  The odd slot outranks the even one at every issue arbitration.
-        const unsigned tg = __builtin_amdgcn_s_getreg((3 << 11) | (16 << 6) | 4);
-        if (tg & 1) __builtin_amdgcn_s_setprio(2);
-    } else if (MODE != 2 && wave >= G::WAVES / 2) __builtin_amdgcn_s_setprio(1);      // (as conv3x3_emu.hip: the later-dispatched half of the wavefronts loses every arbitration otherwise)
+    if (wave >= G::WAVES / 2) __builtin_amdgcn_s_setprio(1);      // (as conv3x3_emu.hip: the later-dispatched half of the wavefronts loses every arbitration otherwise)
     int L = 0;
     bool pending_pub = false;                                      // stream-K (round 6): this workgroup's share has left, its flag goes up behind the next interval's barrier
     while (L < n_local) {
@@ -303,8 +250,8 @@ __global__ __launch_bounds__(64 * NPB + (MODE == 3 ? 64 : MODE == 7 ? 256 : 0), 
         const bool lower = py >= cur.yb;
         const int out_n = cur.n0 + (lower ? 1 : 0), gy = lower ? py - cur.yb : cur.yl0 + py, gx = cur.x0 + px;
         const int bshift = lower ? 2 * G::PW : 0;
-        const bool live = compute && out_n < a.N && gy < a.H && gx < a.W;
-        const bool wave_live = compute && __builtin_amdgcn_readfirstlane((int)(cur.n0 * a.H + cur.yl0 + blk_y * BH < (a.stack ? a.N * a.H : cur.n0 * a.H + a.H) && cur.x0 + blk_x * BW < a.W)) != 0;
+        const bool live = in_tile && out_n < a.N && gy < a.H && gx < a.W;
+        const bool wave_live = in_tile && __builtin_amdgcn_readfirstlane((int)(cur.n0 * a.H + cur.yl0 + blk_y * BH < (a.stack ? a.N * a.H : cur.n0 * a.H + a.H) && cur.x0 + blk_x * BW < a.W)) != 0;
         const size_t pix = live ? (size_t)gy * a.W + gx : 0;
         const int on = live ? out_n : 0;
         floatx16 acc[NQ], accl[NQ];
@@ -357,7 +304,7 @@ __global__ __launch_bounds__(64 * NPB + (MODE == 3 ? 64 : MODE == 7 ? 256 : 0), 
                 nc = 0;
                 ntile = tile + tile_step;
                 next = decode(ntile);
-                if (loader_here) nplan = make_plan(next);
+                if (in_tile) nplan = make_plan(next);
             }
             if constexpr (SPLIT) {
                 // Round 6: the owner of a tile its range does not finish looks for the next gang's share BEFORE its own last interval: if the flag is up (the normal
@@ -378,13 +325,11 @@ __global__ __launch_bounds__(64 * NPB + (MODE == 3 ? 64 : MODE == 7 ? 256 : 0), 
                     }
                 }
             }
-            constexpr bool kPaired = K::PAIRED;
-            const int slot_cur = kPaired ? 0 : (L & 1), slot_next = kPaired ? 0 : ((L + 1) & 1);
-            if (!K::INTERLEAVED && !kPaired && more && loader_here) issue_all(nplan, nc, slot_next);
-            if (!kPaired && chunk == c_end - 1 && head && complete && wave_live && !SP_ABLATE(8)) fetch_residual();      // (an owner that still has to take shares in fetches it behind them)
+            const int slot_cur = L & 1, slot_next = (L + 1) & 1;
+            if (chunk == c_end - 1 && head && complete && wave_live && !SP_ABLATE(8)) fetch_residual();      // (an owner that still has to take shares in fetches it behind them)
             SP_STAMP(3);
             if (wave_live && !SP_ABLATE(4)) {
-                const uint4 *bq = reinterpret_cast<const uint4 *>(lds + K::NBUF * G::W_BYTES + slot_cur * G::B_BYTES) + bshift, *wq = reinterpret_cast<const uint4 *>(lds + slot_cur * G::W_BYTES) + wlane;
+                const uint4 *bq = reinterpret_cast<const uint4 *>(lds + 2 * G::W_BYTES + slot_cur * G::B_BYTES) + bshift, *wq = reinterpret_cast<const uint4 *>(lds + slot_cur * G::W_BYTES) + wlane;
                 auto load_b = [&](int s, halfx8 (&b)[2]) {
 #pragma unroll
                     for (int t = 0; t < 2; ++t) b[t] = __builtin_bit_cast(halfx8, bq[t * G::PIXP + boff[s]]);
@@ -396,10 +341,8 @@ __global__ __launch_bounds__(64 * NPB + (MODE == 3 ? 64 : MODE == 7 ? 256 : 0), 
                         for (int t = 0; t < 2; ++t) w[q][t] = __builtin_bit_cast(halfx8, wq[((s * 2 + t) * 2) * CT + q * 32]);
                 };
                 halfx8 bc[2], wc[NQ][2];
-                if constexpr (!kPaired) {
-                    load_b(0, bc);
-                    load_w(0, wc);
-                }
+                load_b(0, bc);
+                load_w(0, wc);
 #pragma unroll
                 for (int s = 0; s < 9; ++s) {
                     // Round 6: PROGRESS-BASED issue priority.  A SIMD's two or three wavefronts share one matrix pipe; with fixed priorities the favoured one runs
@@ -420,18 +363,9 @@ __global__ __launch_bounds__(64 * NPB + (MODE == 3 ? 64 : MODE == 7 ? 256 : 0), 
                         if (s == 8 && late == 2) __builtin_amdgcn_s_setprio(0);
                     }
                     halfx8 bn[2], wn[NQ][2];
-                    if constexpr (kPaired) {                       // four wavefronts per SIMD hide the LDS latency; no second operand set in the 128 registers
-                        load_b(s, bc);
-                        load_w(s, wc);
-                    } else if (s + 1 < 9) {                        // operands of the next tap are in flight while this tap's matrix instructions issue
+                    if (s + 1 < 9) {                        // operands of the next tap are in flight while this tap's matrix instructions issue
                         load_b(s + 1, bn);
                         load_w(s + 1, wn);
-                    }
-                    if constexpr (MODE == 4) {
-                        if (more) {
-#pragma unroll
-                            for (int k = s; k < K::OPS; k += 9) issue_op(nplan, nc, slot_next, k);
-                        }
                     }
 #pragma unroll
                     for (int q = 0; q < NQ; ++q) accl[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wc[q][0], bc[1], accl[q], 0, 0, 0);      // w_h x_l'
@@ -439,20 +373,17 @@ __global__ __launch_bounds__(64 * NPB + (MODE == 3 ? 64 : MODE == 7 ? 256 : 0), 
                     for (int q = 0; q < NQ; ++q) accl[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wc[q][1], bc[0], accl[q], 0, 0, 0);      // w_l' x_h
 #pragma unroll
                     for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wc[q][0], bc[0], acc[q], 0, 0, 0);        // w_h x_h
-                    if constexpr (MODE == 1) {
-                        if (more) {
-#pragma unroll
-                            for (int k = s; k < K::OPS; k += 9) issue_op(nplan, nc, slot_next, k);
-                        }
-                    }
-                    if constexpr (MODE == 5) {
-                        if (more) {
+                    if (more) {                                    // this wavefront's share of the next interval's DMA (Geo::FRONT)
+                        if constexpr (G::FRONT) {
 #pragma unroll
                             for (int k = 2 * s; k < 2 * s + 2; ++k)
-                                if (k < K::OPS) issue_op(nplan, nc, slot_next, k);
+                                if (k < G::OPS) issue_op(nplan, nc, slot_next, k);
+                        } else {
+#pragma unroll
+                            for (int k = s; k < G::OPS; k += 9) issue_op(nplan, nc, slot_next, k);
                         }
                     }
-                    if (!kPaired && s + 1 < 9) {
+                    if (s + 1 < 9) {
 #pragma unroll
                         for (int t = 0; t < 2; ++t) {
                             bc[t] = bn[t];
@@ -461,19 +392,10 @@ __global__ __launch_bounds__(64 * NPB + (MODE == 3 ? 64 : MODE == 7 ? 256 : 0), 
                         }
                     }
                 }
-            } else if (K::INTERLEAVED && more) {
+            } else if (more) {
                 issue_all(nplan, nc, slot_next);
             }
-            if constexpr (kPaired) {                               // everyone has read the buffers: the next interval's operands take their place (the partner workgroup computes meanwhile)
-                SP_STAMP(5);
-                __syncthreads();
-                SP_STAMP(6);
-                if (more && loader_here) issue_all(nplan, nc, 0);
-            }
             SP_STAMP(4);
-        }
-        if constexpr (K::PAIRED) {                                 // (no residual prefetch behind the last interval: its 32 registers do not fit beside the K loop's at 128)
-            if (head && wave_live && !SP_ABLATE(8)) fetch_residual();
         }
         chunk0 = 0;                                                // every later segment of this range opens its tile
         SP_STAMP_AT(5, L - 1);                                     // (epilogue stamps land in the record of the tile's last interval: 5 start, 6 residual in float, 7 stored)
@@ -554,9 +476,7 @@ __global__ __launch_bounds__(64 * NPB + (MODE == 3 ? 64 : MODE == 7 ? 256 : 0), 
         // the range check one running maximum, the store address a running pointer, each group's bias / scale loads are issued one group ahead.
         const float4 *bias4 = reinterpret_cast<const float4 *>(lds_par + cur.cg * CT + 4 * half), *winv4 = reinterpret_cast<const float4 *>(lds_par + a.Cout + cur.cg * CT + 4 * half);
         float rr[8][4];
-        if constexpr (K::PAIRED) {
-            // (converted per channel group below: a float copy of all 32 residual values beside the 64 accumulators does not fit the paired mode's 128 registers)
-        } else if (a.res_kind == SP_RES_SP) {
+        if (a.res_kind == SP_RES_SP) {
 #pragma unroll
             for (int g8 = 0; g8 < NG8; ++g8) {
                 const halfx4 h = __builtin_bit_cast(halfx4, uint2{rraw[g8].x, rraw[g8].y}), l = __builtin_bit_cast(halfx4, uint2{rraw[g8].z, rraw[g8].w});
@@ -587,17 +507,6 @@ __global__ __launch_bounds__(64 * NPB + (MODE == 3 ? 64 : MODE == 7 ? 256 : 0), 
                 i4 = winv4[2 * (g8 + 1)];
             }
             float v[4];
-            if constexpr (K::PAIRED) {
-                if (a.res_kind == SP_RES_SP) {
-                    const halfx4 h = __builtin_bit_cast(halfx4, uint2{rraw[g8].x, rraw[g8].y}), l = __builtin_bit_cast(halfx4, uint2{rraw[g8].z, rraw[g8].w});
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) rr[g8][j] = coalign::sp16_join(h[j], l[j]);
-                } else {
-                    const unsigned u0 = rraw[g8].x, u1 = rraw[g8].y, u2 = rraw[g8].z, u3 = rraw[g8].w;      // (bit-casting a vector ELEMENT directly is miscompiled by hipcc 7.2 -- pillar_sparse.hip swap32: go through locals)
-                rr[g8][0] = __builtin_bit_cast(float, u0); rr[g8][1] = __builtin_bit_cast(float, u1);
-                    rr[g8][2] = __builtin_bit_cast(float, u2); rr[g8][3] = __builtin_bit_cast(float, u3);
-                }
-            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int q = g8 / 4, e = 4 * (g8 % 4) + j;
@@ -686,21 +595,20 @@ struct SpLaunch {          // what the host needs to know about one (shape, geom
     size_t flag_bytes, ws_bytes;
 };
 
-// split_policy: 0 = by the rule below, 1 = never, 2 = whenever possible (laboratory)
-template <int BH, int BW, int NPB, int NBX, int MODE, int CT = 64>
+// split_policy: 0 = by the rule below, 1 = never, 2 = whenever possible (test aids)
+template <int BH, int BW, int NPB, int NBX, int CT = 64>
 int launch_geo(SpArgs a, int out_kind, int split_policy, void *workspace, size_t workspace_bytes, hipStream_t s, SpLaunch *query) {
     using G = Geo<BH, BW, NPB, NBX, CT>;
-    using KW = Work<BH, BW, NPB, NBX, MODE, CT>;
-    constexpr bool CAN_SPLIT = NPB == 8 && CT == 64 && MODE != 3 && MODE != 6 && MODE != 7;    // (the hand-over code needs the 8-wavefront geometries' register budget; the loader wavefront of MODE 3 mirrors whole tiles only; the paired mode runs whole tiles)
-    auto k_sp = conv3x3_sp_kernel<BH, BW, NPB, NBX, SP_OUT_SP, MODE, false, CT>;
-    auto k_cl = conv3x3_sp_kernel<BH, BW, NPB, NBX, SP_OUT_NHWC, MODE, false, CT>;
-    auto k_sp_s = conv3x3_sp_kernel<BH, BW, NPB, NBX, SP_OUT_SP, MODE, CAN_SPLIT, CT>;
-    auto k_cl_s = conv3x3_sp_kernel<BH, BW, NPB, NBX, SP_OUT_NHWC, MODE, CAN_SPLIT, CT>;
-    auto k_both = conv3x3_sp_kernel<BH, BW, NPB, NBX, SP_OUT_BOTH, MODE, false, CT>;
-    auto k_both_s = conv3x3_sp_kernel<BH, BW, NPB, NBX, SP_OUT_BOTH, MODE, CAN_SPLIT, CT>;
+    constexpr bool CAN_SPLIT = NPB == 8 && CT == 64;                   // (the hand-over code needs the 8-wavefront geometries' register budget)
+    auto k_sp = conv3x3_sp_kernel<BH, BW, NPB, NBX, SP_OUT_SP, false, CT>;
+    auto k_cl = conv3x3_sp_kernel<BH, BW, NPB, NBX, SP_OUT_NHWC, false, CT>;
+    auto k_sp_s = conv3x3_sp_kernel<BH, BW, NPB, NBX, SP_OUT_SP, CAN_SPLIT, CT>;
+    auto k_cl_s = conv3x3_sp_kernel<BH, BW, NPB, NBX, SP_OUT_NHWC, CAN_SPLIT, CT>;
+    auto k_both = conv3x3_sp_kernel<BH, BW, NPB, NBX, SP_OUT_BOTH, false, CT>;
+    auto k_both_s = conv3x3_sp_kernel<BH, BW, NPB, NBX, SP_OUT_BOTH, CAN_SPLIT, CT>;
     static PerDevice lds_set;
     if (!query) {                                                      // (a size query before the first launch sets no attributes: the launch does)
-        if (const int rc = allow_dynamic_lds(lds_set, KW::LDS_BYTES, k_sp, k_cl, k_sp_s, k_cl_s, k_both, k_both_s)) return rc;
+        if (const int rc = allow_dynamic_lds(lds_set, G::LDS_BYTES, k_sp, k_cl, k_sp_s, k_cl_s, k_both, k_both_s)) return rc;
     }
     const int n_cu = cu_count();
     a.stack = (a.N > 1 && G::TH <= a.H) ? 1 : 0;
@@ -708,11 +616,9 @@ int launch_geo(SpArgs a, int out_kind, int split_policy, void *workspace, size_t
     a.tiles_y = (a.H + G::TH - 1) / G::TH;                            // per image (not stacked)
     const int row_tiles = a.stack ? (a.N * a.H + G::TH - 1) / G::TH : a.N * a.tiles_y;
     a.total_tiles = a.tiles_x * row_tiles * (a.Cout / CT);
-    int slots = n_cu * (KW::PAIRED ? 2 : 1);                           // 111-147 KB of LDS: one workgroup per CU (paired mode: 65-70 KB, two)
-    {   // laboratory switch: fewer persistent workgroups than CUs (what a launch leaves free, the other frame's kernels take)
-        const int cap = coalign::lab_env("COALIGN_SP_SLOTS", 0);
-        if (cap > 0 && cap < slots) slots = cap;
-    }
+    // 111-147 KB of LDS: one workgroup per CU.  (Measured, not adopted: fewer persistent workgroups than CUs, so that the other frame's kernels take what a launch
+    // leaves free -- 256 / 224 / 192 / 160 slots: 634 / 615 / 598 / 570 frames/s)
+    const int slots = n_cu;
     const int chunks = a.Cin / 16;
     // Stream-K pays where whole tiles leave the last round badly filled AND a workgroup's range spans whole tiles, i.e. at most one hand-over per workgroup
     // (the shrink header: 572 tiles of 16 intervals = three rounds at 74 %: 132 -> 125 us).  Measured where a tile is cut into several shares
@@ -735,11 +641,9 @@ int launch_geo(SpArgs a, int out_kind, int split_policy, void *workspace, size_t
     if (split && (slots < n_groups || steps / n_groups < slots / n_groups)) split = false;      // (every gang needs at least one step)
     SpLaunch l;
     l.split = split ? 1 : 0;
-    l.grid = split ? slots / n_groups * n_groups : (a.total_tiles < slots ? a.total_tiles : slots);      // stream-K: whole gangs (one workgroup per output-channel group)
-    if (!split && a.total_tiles > slots && coalign::lab_env("COALIGN_SP_BALANCE", 0)) {      // laboratory: as many workgroups as give every one the same number of tiles (462 tiles: 231 x 2 instead of 206 x 2 + 50 x 1)
-        const int r = (a.total_tiles + slots - 1) / slots;
-        l.grid = (a.total_tiles + r - 1) / r;
-    }
+    // stream-K: whole gangs (one workgroup per output-channel group).  (Measured, not adopted: as many workgroups as give every one the same number of whole tiles
+    // -- 462 tiles: 231 x 2 instead of 206 x 2 + 50 x 1 -- 629.8 / 628.4 against 628.5 / 629.0 frames/s: nothing)
+    l.grid = split ? slots / n_groups * n_groups : (a.total_tiles < slots ? a.total_tiles : slots);
     l.flag_bytes = split ? coalign::align_up((size_t)(l.grid + 4) * sizeof(int), 256) : 0;
     l.ws_bytes = split ? l.flag_bytes + (size_t)(l.grid + 4) * G::WAVES * 32 * 64 * sizeof(float) : 0;
     if (query) {
@@ -753,51 +657,17 @@ int launch_geo(SpArgs a, int out_kind, int split_policy, void *workspace, size_t
         a.flags = static_cast<int *>(workspace);
         a.partial = reinterpret_cast<float *>(static_cast<char *>(workspace) + l.flag_bytes);
     }
-    constexpr int kThreads = Work<BH, BW, NPB, NBX, MODE, CT>::THREADS;
-    if (split) hipLaunchKernelGGL(out_kind == SP_OUT_SP ? k_sp_s : out_kind == SP_OUT_BOTH ? k_both_s : k_cl_s, dim3(l.grid), dim3(kThreads), KW::LDS_BYTES, s, a);
-    else hipLaunchKernelGGL(out_kind == SP_OUT_SP ? k_sp : out_kind == SP_OUT_BOTH ? k_both : k_cl, dim3(l.grid), dim3(kThreads), KW::LDS_BYTES, s, a);
+    if (split) hipLaunchKernelGGL(out_kind == SP_OUT_SP ? k_sp_s : out_kind == SP_OUT_BOTH ? k_both_s : k_cl_s, dim3(l.grid), dim3(G::THREADS), G::LDS_BYTES, s, a);
+    else hipLaunchKernelGGL(out_kind == SP_OUT_SP ? k_sp : out_kind == SP_OUT_BOTH ? k_both : k_cl, dim3(l.grid), dim3(G::THREADS), G::LDS_BYTES, s, a);
     return COALIGN_OK;
 }
 
-template <int MODE>
-int launch_mode(int geo, const SpArgs &a, int out_kind, int split_policy, void *ws, size_t ws_bytes, hipStream_t s, SpLaunch *query) {
-    if constexpr (MODE == 5) {                                        // front-loaded DMA issue: the product carries it for the 8-wavefront geometries only (dispatch_sp)
-        switch (geo) {
-            case 81: return launch_geo<1, 32, 8, 1, MODE>(a, out_kind, split_policy, ws, ws_bytes, s, query);
-            case 148: return launch_geo<4, 8, 8, 4, MODE>(a, out_kind, split_policy, ws, ws_bytes, s, query);
-#if defined(COALIGN_LAB) || defined(SP_TRACE)
-            case 121: return launch_geo<1, 32, 12, 1, MODE>(a, out_kind, split_policy, ws, ws_bytes, s, query);
-            case 124: return launch_geo<2, 16, 12, 1, MODE>(a, out_kind, split_policy, ws, ws_bytes, s, query);
-#endif
-            default: return COALIGN_ERR_UNSUPPORTED;
-        }
-    } else if constexpr (MODE == 6 || MODE == 7) {                    // two workgroups per CU / four loader wavefronts: the 8-wavefront geometries
-        switch (geo) {
-            case 81: return launch_geo<1, 32, 8, 1, MODE>(a, out_kind, split_policy, ws, ws_bytes, s, query);   // 8 rows x 32 columns
-            case 84: return launch_geo<2, 16, 8, 1, MODE>(a, out_kind, split_policy, ws, ws_bytes, s, query);   // 16 x 16 (2 x 16 blocks): maps 16 (mod 32) wide
-            case 148: return launch_geo<4, 8, 8, 4, MODE>(a, out_kind, split_policy, ws, ws_bytes, s, query);   // 8 x 32 in 4 x 8 blocks
-            default: return COALIGN_ERR_UNSUPPORTED;
-        }
-    } else {
-        switch (geo) {
-            case 81: return launch_geo<1, 32, 8, 1, MODE>(a, out_kind, split_policy, ws, ws_bytes, s, query);       // 8 rows x 32 columns
-            case 121: return launch_geo<1, 32, 12, 1, MODE>(a, out_kind, split_policy, ws, ws_bytes, s, query);     // 12 x 32
-            case 124: return launch_geo<2, 16, 12, 1, MODE>(a, out_kind, split_policy, ws, ws_bytes, s, query);     // 24 x 16 (2 x 16 blocks)
-            case 148: return launch_geo<4, 8, 8, 4, MODE>(a, out_kind, split_policy, ws, ws_bytes, s, query);       // 8 x 32 in 4 x 8 blocks, four block columns
-            case 326: return launch_geo<4, 8, 12, 6, MODE, 32>(a, out_kind, split_policy, ws, ws_bytes, s, query);  // (round 6) 8 x 48 in 4 x 8 blocks x 32 output channels, 12 wavefronts
-            default: return COALIGN_ERR_UNSUPPORTED;
-        }
-    }
-}
-
-constexpr int kDefaultMode = 1;
-
-// geometry code: 0 = chosen from the map size (the rules measured for conv3x3_emu.hip's fp16 mode), else 81 / 121 / 124 / 148 as there;
-// + 1000 * (issue mode + 1) and + 100000 * split policy are laboratory switches (the product library carries kDefaultMode only)
+// geometry code: 0 = chosen from the map size (the rules measured for conv3x3_emu.hip's fp16 mode), else one of the five tiles below; + 100000 * split policy is
+// a test aid.  Nothing else: a code whose thousands digit is set is refused.
 int dispatch_sp(const SpArgs &a, int out_kind, int geometry, void *ws, size_t ws_bytes, hipStream_t s, SpLaunch *query) {
     const int split_policy = geometry / 100000;
-    geometry %= 100000;
-    int geo = geometry % 1000, mode = geometry >= 1000 ? geometry / 1000 - 1 : kDefaultMode;
+    int geo = geometry % 100000;
+    if (geo >= 1000) return COALIGN_ERR_UNSUPPORTED;
     if (geo == 0) {
         if (a.W % 32 == 16 && a.H > 26 && a.H <= 52 && a.N * a.H >= 24) geo = 124;
         else if (a.H >= 64) geo = (a.N == 1 && a.Cin >= 128) ? 81 : 121;      // (one image, long tiles -- the shrink header: the 8-wavefront geometry, which can split)
@@ -820,31 +690,16 @@ int dispatch_sp(const SpArgs &a, int out_kind, int geometry, void *ws, size_t ws
         // wavefront that owns 32 x 32 outputs reads 1.33 LDS operands per matrix instruction instead of 1.0 -- an interval is ~4900 clocks for 2592 of matrix work
         // (64-channel tiles: 4600 for 3456) -- and the launch holds every CU: the two-stream frame pipeline LOSES 1.6 % (646.6 against 657.2 frames/s, same box,
         // alternating).  Same sums in the same order per output value: bit-equal to the other geometries (tests/test_s2_gpu.py).  A latency-bound caller selects
-        // it per map size (coalign_amd/ops.py: COALIGN_SP_GEO="25x88:326"); the laboratory build's COALIGN_SP_CT32=1 makes it the rule.
-        if ((geo == 81 || geo == 148) && a.H >= 8 && coalign::lab_env("COALIGN_SP_CT32", 0)) {
-            const long long t64 = (long long)((rows + 7) / 8) * ((a.W + 31) / 32) * groups;
-            const long long t32 = (long long)((rows + 7) / 8) * ((a.W + 47) / 48) * groups * 2;
-            if (t64 * 5 <= 4LL * n_cu && t32 <= n_cu) geo = 326;
-        }
+        // it per map size (coalign_amd/ops.py: COALIGN_SP_GEO="25x88:326").
     }
-    // Round 6: the 8-wavefront geometries issue their LDS-DMA FRONT-LOADED (mode 5: two instructions behind each of the first taps instead of one behind every tap):
-    // with the progress-based priority the wavefronts of a SIMD finish together, and the interval's closing s_waitcnt no longer waits ~300 clocks for a piece issued
-    // behind the last tap -- stage 3 44.6-45.4 -> 43.4-43.8 us, shrink header 2nd 120.0-120.3 -> 116.7-117.0 (profiles/round6/experiments/conv_sp_geometry_modes.txt);
-    // the 12-wavefront geometries gain nothing from it (47.2-47.9 -> 47.7-48.3, 41.1-41.3 -> 41.6-41.7).  Same arithmetic, same bits.
-    if (geometry < 1000 && (geo == 81 || geo == 148) && coalign::lab_env("COALIGN_SP_FRONT", 1)) mode = 5;
-#if defined(COALIGN_LAB) || defined(SP_TRACE)      // laboratory / trace builds carry every issue mode
-    if (mode == 3 && (geo == 81 || geo == 148)) return launch_mode<3>(geo, a, out_kind, split_policy, ws, ws_bytes, s, query);
-    if (mode == 6) return launch_mode<6>(geo, a, out_kind, split_policy, ws, ws_bytes, s, query);
-    if (mode == 7) return launch_mode<7>(geo, a, out_kind, split_policy, ws, ws_bytes, s, query);
-    if (mode == 4) return launch_mode<4>(geo, a, out_kind, split_policy, ws, ws_bytes, s, query);
-    if (mode == 5) return launch_mode<5>(geo, a, out_kind, split_policy, ws, ws_bytes, s, query);
-    return mode == 0 ? launch_mode<0>(geo, a, out_kind, split_policy, ws, ws_bytes, s, query) : mode == 2 ? launch_mode<2>(geo, a, out_kind, split_policy, ws, ws_bytes, s, query)
-                                                                                              : launch_mode<1>(geo, a, out_kind, split_policy, ws, ws_bytes, s, query);
-#else
-    if (mode != kDefaultMode && geometry >= 1000) return COALIGN_ERR_UNSUPPORTED;      // (issue modes 0, 2-4, 6, 7 are measured-and-not-adopted variants: laboratory library only)
-    if (mode == 5) return launch_mode<5>(geo, a, out_kind, split_policy, ws, ws_bytes, s, query);
-    return launch_mode<kDefaultMode>(geo, a, out_kind, split_policy, ws, ws_bytes, s, query);
-#endif
+    switch (geo) {
+        case 81: return launch_geo<1, 32, 8, 1>(a, out_kind, split_policy, ws, ws_bytes, s, query);         // 8 rows x 32 columns
+        case 121: return launch_geo<1, 32, 12, 1>(a, out_kind, split_policy, ws, ws_bytes, s, query);       // 12 x 32
+        case 124: return launch_geo<2, 16, 12, 1>(a, out_kind, split_policy, ws, ws_bytes, s, query);       // 24 x 16 (2 x 16 blocks)
+        case 148: return launch_geo<4, 8, 8, 4>(a, out_kind, split_policy, ws, ws_bytes, s, query);         // 8 x 32 in 4 x 8 blocks, four block columns
+        case 326: return launch_geo<4, 8, 12, 6, 32>(a, out_kind, split_policy, ws, ws_bytes, s, query);    // (round 6) 8 x 48 in 4 x 8 blocks x 32 output channels, 12 wavefronts
+        default: return COALIGN_ERR_UNSUPPORTED;
+    }
 }
 
 }  // namespace

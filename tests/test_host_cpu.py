@@ -630,3 +630,15 @@ def test_csrc_has_one_copy_of_each_shared_piece():
     assert files(r"\bstruct Geom\b") == ["warp_taps.h"] and count(r"\bstruct Geom\b") == 1
     assert files(r"\bbool misaligned\(") == ["common.h"] and count(r"\b\w[\w:<>\*& ]* misaligned\([^;{)]*\)\s*\{") == 1
     assert count(r"\bmisaligned16\b") == 0
+
+
+def test_conv3x3_sp_has_one_kernel_body_and_no_laboratory_issue_modes():
+    """csrc/conv3x3_sp.hip: the LDS-DMA issue schedule is a constant of the tile geometry; the six measured-and-rejected issue modes, their dispatch tables
+    and the host-only laboratory switches of the file are gone (DESIGN.md section 8 keeps their numbers).  The whole text counts, comments included."""
+    import re
+    from coalign_amd import build
+    text = open(os.path.join(build.CSRC, "conv3x3_sp.hip"), encoding="utf-8").read()
+    for name in ("PAIRED", "LOADERS", "loader_here", "kDefaultMode", "launch_mode"):
+        assert not re.search(r"\b%s\b" % name, text), name
+    for name in ("COALIGN_SP_SLOTS", "COALIGN_SP_BALANCE", "COALIGN_SP_CT32", "COALIGN_SP_FRONT"):
+        assert name not in text, name

@@ -66,7 +66,7 @@ hwid = tr.cpu()[2 * waves * 64 * S + 2 * 4096:]
 span_all = tr.cpu()[2 * waves * 64 * S: 2 * waves * 64 * S + 2 * 4096].view(-1, 2)
 live = span_all[:, 1] > 0
 # round 6: where the workgroups ran (HW_ID: CU_ID bits 8-11, SH_ID 12, SE_ID 13-15, TG_ID 16-19; the XCD is not in HW_ID: workgroup g runs on XCD g % 8) and how
-# many of them shared a CU at the same time -- the paired mode (geometry 7000 + g) wants two per CU
+# many of them shared a CU at the same time
 ids = [(int(g) % 8, (int(h) >> 13) & 7, (int(h) >> 12) & 1, (int(h) >> 8) & 15, (int(h) >> 16) & 15, int(a), int(b)) for g, (h, (a, b)) in enumerate(zip(hwid[: len(span_all)].tolist(), span_all.tolist())) if b > 0]
 cus = {}
 for xcd, se, sh, cu, tg, a0, b0 in ids:
@@ -90,10 +90,6 @@ for wg in (0, 1):
                 break
             nxt = int(t[wg, wv, c + 1, 0]) if c + 1 < 64 and int(t[wg, wv, c + 1, 0]) else int(s[4])
             d = [int(s[1] - s[0]), int(s[2] - s[1]), int(s[3] - s[2]), int(s[4] - s[3]), nxt - int(s[4])]
-            if geo % 100000 // 1000 == 7 and int(s[5]) > int(s[3]) and int(s[6]) >= int(s[5]) and int(s[4]) >= int(s[6]):      # paired mode: steps | the barrier that ends the interval | DMA issue
-                d[3] = int(s[5] - s[3])
-                d.insert(4, int(s[6] - s[5]))
-                d.insert(5, int(s[4] - s[6]))
             epi = ""
             if int(s[5]) and int(s[7]):      # a tile's last interval: the gap in parts (accumulator join + hand-over | residual wait + conversion | the 8 channel groups: scale, split, stores | to the next top)
                 epi = f"   epilogue: join {int(s[5] - s[4])} residual {int(s[6] - s[5])} groups {int(s[7] - s[6])} rest {nxt - int(s[7])}"
