@@ -79,8 +79,29 @@ def load_lift_splat_shoot_params(param: dict) -> dict:
     return param
 
 
+def load_voxel_params(param: dict) -> dict:
+    """The SECOND models' parser (yaml_utils.py:52-94): ``anchor_args`` gains ``vw, vh, vd`` and ``W, H, D = int(extent / voxel)`` -- a TRUNCATION, where the pillar
+    parser rounds up --, the three are copied into ``model.args``, and a ``box_align_pre_calc`` section gets the anchors in its stage-1 post-processor."""
+    anchor = param["postprocess"]["anchor_args"]
+    rng = anchor["cav_lidar_range"]
+    vox = param["preprocess"]["args"]["voxel_size"]
+    anchor["vw"], anchor["vh"], anchor["vd"] = vox[0], vox[1], vox[2]
+    anchor["W"] = int((rng[3] - rng[0]) / vox[0])
+    anchor["H"] = int((rng[4] - rng[1]) / vox[1])
+    anchor["D"] = int((rng[5] - rng[2]) / vox[2])
+    param["postprocess"].update({"anchor_args": anchor})
+    if "model" in param:
+        param["model"]["args"]["W"] = anchor["W"]
+        param["model"]["args"]["H"] = anchor["H"]
+        param["model"]["args"]["D"] = anchor["D"]
+    if "box_align_pre_calc" in param:
+        param["box_align_pre_calc"]["stage1_postprocessor_config"].update({"anchor_args": anchor})
+    return param
+
+
 YAML_PARSERS: Dict[str, Callable[[dict], dict]] = {
     "load_point_pillar_params": load_point_pillar_params,
+    "load_voxel_params": load_voxel_params,
     "load_lift_splat_shoot_params": load_lift_splat_shoot_params,
 }
 

@@ -22,6 +22,7 @@ from . import ops
 from .backbone import BaseBEVBackbone, BasicBlock, DownsampleConv, NaiveCompressor, ResNetBEVBackbone, _cache_of, _fast_ok
 from .encoder import PillarVFE, PointPillarScatter, host_ints
 from .lss import LiftSplatShootIntermediate
+from .second import SecondSSFA, SecondSSFAUncertainty
 from .fusion import AttFusion, DiscoFusion, MaxFusion, V2VNetFusion, V2XViTFusion, When2comFusion, Where2commFusion, fuse_multiscale
 from . import v2v_robust
 from .pose import generate_noise_torch, get_pairwise_transformation_torch, normalize_pairwise_tfm
@@ -769,12 +770,19 @@ CAMERA_REGISTRY = {
     "lift_splat_shoot_intermediate": LiftSplatShootIntermediate,
 }
 
+# CoAlign's second stage-1 detector family (coalign_amd.second): SECOND on the sparse 3-D trunk of coalign_amd.sparse3d with the SSFA neck.  No pillar trunk: ``routes.plan``
+# does not walk it; ``sparse3d.plan`` words its trunk.
+SECOND_REGISTRY = {
+    "second_ssfa": SecondSSFA,
+    "second_ssfa_uncertainty": SecondSSFAUncertainty,
+}
+
 
 def build_model(hypes: dict) -> nn.Module:
     """``train_utils.create_model`` for the hot-path model families and the comparison baselines (opencood/tools/train_utils.py:113-146):
     ``hypes['model']['core_method']`` names the model, ``hypes['model']['args']`` is its constructor argument."""
     name = hypes["model"]["core_method"]
-    families = {**MODEL_REGISTRY, **BASELINE_REGISTRY, **CAMERA_REGISTRY}
+    families = {**MODEL_REGISTRY, **BASELINE_REGISTRY, **CAMERA_REGISTRY, **SECOND_REGISTRY}
     if name not in families:
         raise KeyError(f"model '{name}' is outside the CoAlign hot path and its baselines (available: {sorted(families)})")
     return families[name](hypes["model"]["args"])

@@ -249,6 +249,25 @@ HEADERS = {
     "coalign_amd_lss.h": LSS_SIGNATURES,
     "coalign_amd_lss_bev.h": LSS_BEV_SIGNATURES,
 }
+
+# include_ext/coalign_amd_sparse3d.h: extension header of ABI version 2 (product library), the first outside include/'s frozen set: the sparse 3-D trunk of the SECOND
+# detectors -- MeanVFE, the site index, strided site generation, the neighbour table, the gather-GEMM convolution and the dense map (csrc/sparse_conv3d.hip)
+SPARSE3D_SIGNATURES = {
+    "coalign_sp3d_mean_vfe": (c_int, [P, P, c_int, c_int, c_int, P, P]),
+    "coalign_sp3d_index_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "coalign_sp3d_index_build": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    "coalign_sp3d_strided_sites": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, c_size_t, P, P]),
+    "coalign_sp3d_neighbors": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                       c_int, P, P]),
+    "coalign_sp3d_weight_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "coalign_sp3d_conv": (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, P, c_size_t, P, P, P]),
+    "coalign_sp3d_to_dense": (c_int, [P, P, c_int, c_int, P, c_size_t, c_int, c_int, c_int, c_int, P, P]),
+}
+
+# header under include_ext/ (build.EXT_HEADERS) -> its table: bound by both loaders AFTER the frozen tables above
+EXT_HEADERS = {
+    "coalign_amd_sparse3d.h": SPARSE3D_SIGNATURES,
+}
 _LAB_LIB = None
 
 
@@ -284,7 +303,7 @@ def lib() -> ctypes.CDLL:
         return _LIB
     lab = os.environ.get("COALIGN_LAB", "0")             # tools/ only: "1" = the laboratory build with its ablation switches, "vec" = + packed fp32 allowed (build.py)
     path = _build.LABVEC_LIB_PATH if lab == "vec" else _build.LAB_LIB_PATH if lab == "1" else _build.LIB_PATH
-    handle = _load(path, HEADERS.values(), "; the CoAlign hot path has no CPU fallback")
+    handle = _load(path, [*HEADERS.values(), *EXT_HEADERS.values()], "; the CoAlign hot path has no CPU fallback")
     if handle.coalign_abi_version() != 2:
         raise CoalignHipError(f"ABI version mismatch: library reports {handle.coalign_abi_version()}, binding expects 2")
     _LIB = handle
@@ -296,7 +315,7 @@ def lab_lib() -> ctypes.CDLL:
     and tools call through it; nothing in the detector's default routes does."""
     global _LAB_LIB
     if _LAB_LIB is None:
-        _LAB_LIB = _load(_build.LAB_LIB_PATH, [*HEADERS.values(), LAB_SIGNATURES])
+        _LAB_LIB = _load(_build.LAB_LIB_PATH, [*HEADERS.values(), *EXT_HEADERS.values(), LAB_SIGNATURES])
     return _LAB_LIB
 
 

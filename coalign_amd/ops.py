@@ -2464,3 +2464,130 @@ def up2x_concat_sp(skip: torch.Tensor, low: torch.Tensor) -> "SplitMap":
     with _Timed("up2x_concat_sp"):
         hip.check(hip.lib().coalign_up2x_concat_sp(_ptr(st), _ptr(lt), _ptr(out.data), N, Cs, Cl, h, w, _ptr(sp_range_flag(st.device)), _stream()), "coalign_up2x_concat_sp")
     return out
+
+
+# ---- the sparse 3-D trunk of the SECOND detectors (include_ext/coalign_amd_sparse3d.h, csrc/sparse_conv3d.hip) -----------------------------------------------
+SP3D_COMBINATIONS = {27: ((4, 16), (16, 16), (16, 32), (32, 32), (32, 64), (64, 64)), 3: ((64, 64), (64, 128))}
+SP3D_STATUS_OVERFLOW = 1
+
+
+def sp3d_supported(cin: int, cout: int, taps: int) -> bool:
+    """The (Cin, Cout, taps) combinations ``coalign_sp3d_conv`` takes: VoxelBackBone8x's own."""
+    return (cin, cout) in SP3D_COMBINATIONS.get(taps, ())
+
+
+def pack_sp3d_weights(w: torch.Tensor) -> torch.Tensor:
+    """Folded weights [Cout, taps, Cin] float32 -> the image of ``coalign_sp3d_conv`` (header (18f)): float32 [taps][Cin][Cout] at Cin = 4, else the sp16 operand image
+    of [Cout rounded up to 32, taps Cin] (``_disco_operand_image``: column k = tap Cin + c, rows past Cout zero)."""
+    cout, taps, cin = w.shape
+    w = w.detach().float()
+    if cin == 4:
+        return w.permute(1, 2, 0).contiguous().view(torch.uint8).reshape(-1)
+    rows = (cout + 31) // 32 * 32
+    full = w.new_zeros((rows, taps * cin))
+    full[:cout] = w.reshape(cout, taps * cin)
+    return _disco_operand_image(full).contiguous()
+
+
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def _triple(v) -> Tuple[int, int, int]:
+    return (int(v),) * 3 if isinstance(v, int) else tuple(int(a) for a in v)
+
+
+def sp3d_out_shape(shape, k, s, p) -> Tuple[int, int, int]:
+    """spconv's output shape per axis: (n + 2 p - k) // s + 1."""
+    return tuple((n + 2 * pp - kk) // ss + 1 for n, kk, ss, pp in zip(shape, _triple(k), _triple(s), _triple(p)))
+
+
+@_device_op
+def sp3d_mean_vfe(voxels: torch.Tensor, num_points: torch.Tensor) -> torch.Tensor:
+    """MeanVFE: voxels [M, T, C] float32, num_points [M] -> [M, C] (one launch)."""
+    _need_gpu(voxels, num_points)
+    M, T, C = voxels.shape
+    voxels, n = _f32c(voxels), num_points.to(torch.int32).contiguous()
+    out = torch.empty((M, C), dtype=torch.float32, device=voxels.device)
+    with _Timed("sp3d_mean_vfe"):
+        hip.check(hip.lib().coalign_sp3d_mean_vfe(_ptr(voxels), _ptr(n), M, T, C, _ptr(out), _stream()), "coalign_sp3d_mean_vfe")
+    return out
+
+
+def sp3d_index_bytes(batch: int, shape, capacity: int) -> int:
+    n = hip.lib().coalign_sp3d_index_workspace_bytes(batch, *shape, capacity)
+    if n == 0:
+        raise ValueError(f"sparse grid {batch} x {tuple(shape)} is outside the kernels' range (N D H W < 2^31)")
+    return n
+
+
+@_device_op
+def sp3d_index_build(indices: torch.Tensor, count: torch.Tensor, batch: int, shape) -> torch.Tensor:
+    """The site index (bitmap + word prefix + rank -> row) of ``indices`` [capacity, 4] int32 with its device ``count``; a uint8 tensor.  Six launches, no read-back."""
+    _need_gpu(indices, count)
+    cap = indices.shape[0]
+    nbytes = sp3d_index_bytes(batch, shape, cap)
+    index = torch.empty(nbytes, dtype=torch.uint8, device=indices.device)
+    with _Timed("sp3d_index"):
+        hip.check(hip.lib().coalign_sp3d_index_build(_ptr(indices), _ptr(count), cap, batch, *shape, _ptr(index), nbytes, _stream()), "coalign_sp3d_index_build")
+    return index
+
+
+@_device_op
+def sp3d_strided_sites(indices: torch.Tensor, count: torch.Tensor, batch: int, shape, k, s, p, cap_out: int, status: torch.Tensor):
+    """Output sites of a strided sparse convolution, ascending in the cell index: (out_indices [cap_out, 4], out_count [1] on the device, out_index).  Six launches."""
+    _need_gpu(indices, count, status)
+    k, s, p = _triple(k), _triple(s), _triple(p)
+    oshape = sp3d_out_shape(shape, k, s, p)
+    nbytes = sp3d_index_bytes(batch, oshape, cap_out)
+    dev = indices.device
+    out_indices = torch.empty((cap_out, 4), dtype=torch.int32, device=dev)
+    out_count = torch.empty(1, dtype=torch.int32, device=dev)
+    index = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with _Timed("sp3d_sites"):
+        hip.check(hip.lib().coalign_sp3d_strided_sites(_ptr(indices), _ptr(count), indices.shape[0], batch, *shape, *k, *s, *p, _ptr(out_indices), _ptr(out_count), cap_out,
+                                                       _ptr(index), nbytes, _ptr(status), _stream()), "coalign_sp3d_strided_sites")
+    return out_indices, out_count, index
+
+
+@_device_op
+def sp3d_neighbors(out_indices: torch.Tensor, out_count: torch.Tensor, batch: int, out_shape, in_index: torch.Tensor, cap_in: int, in_shape, k, s, p) -> torch.Tensor:
+    """The neighbour table [taps, cap_out] int32 of the output rows against the indexed input tensor (one launch)."""
+    _need_gpu(out_indices, out_count, in_index)
+    k, s, p = _triple(k), _triple(s), _triple(p)
+    cap_out = out_indices.shape[0]
+    nbr = torch.empty((k[0] * k[1] * k[2], cap_out), dtype=torch.int32, device=out_indices.device)
+    with _Timed("sp3d_neighbors"):
+        hip.check(hip.lib().coalign_sp3d_neighbors(_ptr(out_indices), _ptr(out_count), cap_out, batch, *out_shape, _ptr(in_index), in_index.numel(), cap_in, *in_shape,
+                                                   *k, *s, *p, _ptr(nbr), _stream()), "coalign_sp3d_neighbors")
+    return nbr
+
+
+@_device_op
+def sp3d_conv(in_feat: torch.Tensor, nbr: torch.Tensor, out_count: torch.Tensor, cout: int, weights: torch.Tensor, shift: torch.Tensor) -> torch.Tensor:
+    """relu(sum over the taps of W[tap] in[nbr[tap]] + shift) for the rows below the device count -> [cap_out, Cout] (rows past the count are not written)."""
+    _need_gpu(in_feat, nbr, out_count, weights, shift)
+    cap_in, cin = in_feat.shape
+    taps, cap_out = nbr.shape
+    out = torch.empty((cap_out, cout), dtype=torch.float32, device=in_feat.device)
+    with _Timed("sp3d_conv"):
+        hip.check(hip.lib().coalign_sp3d_conv(_ptr(in_feat), cap_in, _ptr(nbr), taps, _ptr(out_count), cap_out, cin, cout, _ptr(weights), weights.numel(), _ptr(shift),
+                                              _ptr(out), _stream()), "coalign_sp3d_conv")
+    return out
+
+
+@_device_op
+def sp3d_to_dense(feat: torch.Tensor, count: torch.Tensor, index: torch.Tensor, batch: int, shape, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dense() + HeightCompression's view: [N, C D, H, W] float32 in channels-last memory, channel c D + d, every element written by the launch (into ``out`` when
+    given: a channels-last tensor of that shape, whatever it holds)."""
+    _need_gpu(feat, count, index)
+    cap, C = feat.shape
+    D, H, W = shape
+    if out is None:
+        out = torch.empty((batch, C * D, H, W), dtype=torch.float32, device=feat.device, memory_format=torch.channels_last)
+    elif tuple(out.shape) != (batch, C * D, H, W) or out.dtype != torch.float32 or not out.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError("sp3d_to_dense: out must be a channels-last float32 [N, C D, H, W] tensor")
+    with _Timed("sp3d_to_dense"):
+        hip.check(hip.lib().coalign_sp3d_to_dense(_ptr(feat), _ptr(count), cap, C, _ptr(index), index.numel(), batch, D, H, W, _ptr(out), _stream()), "coalign_sp3d_to_dense")
+    return out
