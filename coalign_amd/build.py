@@ -30,7 +30,7 @@ LAB_LIB_PATH = os.path.join(LIB_DIR, "libcoalign_hip_lab.so")
 # cause).  `python -m coalign_amd.build --labvec`; COALIGN_LAB=vec loads it.  tools/pk_f32_recheck.sh runs the experiment.
 LABVEC_LIB_PATH = os.path.join(LIB_DIR, "libcoalign_hip_labvec.so")
 INCLUDE = os.path.join(REPO, "include")
-SOURCES = ["status.cpp", "pillar_scatter.hip", "pillar_sparse.hip", "warp_fuse.hip", "warp_fuse_nhwc.hip", "disco_fuse.hip", "v2v_fuse.hip", "v2v_robust.hip", "v2x_attn.hip", "v2x_window.hip", "v2x_ffn.hip", "lss_pool.hip", "lss_bev.hip", "w2c_fuse.hip", "w2comm.hip", "w2comm_msg.hip", "decode.hip", "nms.hip", "epilogue.hip", "voxelize.hip", "pose_graph.hip", "pose_graph_build.hip", "conv3x3.hip", "conv3x3_emu.hip", "conv3x3_sp.hip", "conv3x3_sp_s2.hip", "conv3x3_narrow.hip", "pointwise.hip", "sparse_conv3d.hip"]
+SOURCES = ["status.cpp", "pillar_scatter.hip", "pillar_sparse.hip", "warp_fuse.hip", "warp_fuse_nhwc.hip", "disco_fuse.hip", "v2v_fuse.hip", "v2v_robust.hip", "v2x_attn.hip", "v2x_window.hip", "v2x_ffn.hip", "lss_pool.hip", "lss_bev.hip", "w2c_fuse.hip", "w2comm.hip", "w2comm_msg.hip", "decode.hip", "nms.hip", "epilogue.hip", "voxelize.hip", "pose_graph.hip", "pose_graph_build.hip", "conv3x3.hip", "conv3x3_emu.hip", "conv3x3_sp.hip", "conv3x3_sp_s2.hip", "conv3x3_narrow.hip", "pointwise.hip", "sparse_conv3d.hip", "ssfa_neck.hip"]
 # Kernels that were measured and NOT adopted live in the laboratory library only: the Winograd F(2x2, 3x3) convolution (1.14 x / 0.89 x / 1.05 x
 # against the direct kernel per stage) -- include/coalign_amd_lab.h, coalign_amd.hip.lab_lib(), tests/test_round4_gpu.py keep it testable.
 LAB_ONLY_SOURCES = ["conv3x3_wino.hip"]
@@ -43,6 +43,10 @@ ABI_HEADERS = ("coalign_amd.h", "coalign_amd_narrow.h", "coalign_amd_narrow_spar
 # include_ext/: the headers the ABI gains after include/'s set was frozen at seventeen (tests/abi_headers.FROZEN); hip.EXT_HEADERS binds them after the frozen tables
 EXT_INCLUDE = os.path.join(REPO, "include_ext")
 EXT_HEADERS = ("coalign_amd_sparse3d.h",)
+# include_open/: every header the ABI gains after include_ext/'s listing was pinned to its one (tests/test_sparse3d_cpu.py); this tuple may grow: hip.OPEN_HEADERS
+# binds them after hip.EXT_HEADERS, and tests/test_ssfa_cpu.py derives what it expects from it
+OPEN_INCLUDE = os.path.join(REPO, "include_open")
+OPEN_HEADERS = ("coalign_amd_ssfa.h",)
 # per-source extras.  pillar_scatter.hip: its matrix-core encoder reduces the accumulators with VALU right after each instruction
 # pair -- results in VGPRs (not AGPRs) save 64 v_accvgpr_read per pass; -fno-honor-nans drops the canonicalising v_max the compiler
 # puts in front of every two-operand fmaxf of a raw matrix result (20 per pass; the file tests for NaN nowhere, its selects are explicit).
@@ -56,7 +60,7 @@ EXT_HEADERS = ("coalign_amd_sparse3d.h",)
 # is recorded as an observation with a mitigation, not as a characterised hardware behaviour.
 EXTRA_FLAGS = {"pillar_scatter.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
                "pillar_sparse.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"]}      # (no NaN test may be written in these two files)
-FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize", "-fno-vectorize", "-Wno-cuda-compat", "-Wno-inline-asm", f"--offload-arch={ARCH}", f"-I{INCLUDE}", f"-I{EXT_INCLUDE}", f"-I{CSRC}"]
+FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize", "-fno-vectorize", "-Wno-cuda-compat", "-Wno-inline-asm", f"--offload-arch={ARCH}", f"-I{INCLUDE}", f"-I{EXT_INCLUDE}", f"-I{OPEN_INCLUDE}", f"-I{CSRC}"]
 
 
 def _hipcc() -> str:
@@ -79,7 +83,7 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False, vectori
     os.makedirs(LIB_DIR, exist_ok=True)
     # every header: the ABI's by name (a missing one is an error), include/*.h and csrc/*.h by glob (a shared header that was forgotten here meant stale objects)
     headers = sorted({os.path.join(INCLUDE, h) for h in ABI_HEADERS} | {os.path.join(EXT_INCLUDE, h) for h in EXT_HEADERS}
-                     | set(glob.glob(os.path.join(INCLUDE, "*.h"))) | set(glob.glob(os.path.join(EXT_INCLUDE, "*.h"))) | set(glob.glob(os.path.join(CSRC, "*.h")))) + [os.path.abspath(__file__)]
+                     | {os.path.join(OPEN_INCLUDE, h) for h in OPEN_HEADERS} | set(glob.glob(os.path.join(OPEN_INCLUDE, "*.h"))) | set(glob.glob(os.path.join(INCLUDE, "*.h"))) | set(glob.glob(os.path.join(EXT_INCLUDE, "*.h"))) | set(glob.glob(os.path.join(CSRC, "*.h")))) + [os.path.abspath(__file__)]
     hipcc = _hipcc()
 
     def compile_one(src: str) -> str:

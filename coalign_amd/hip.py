@@ -268,6 +268,19 @@ SPARSE3D_SIGNATURES = {
 EXT_HEADERS = {
     "coalign_amd_sparse3d.h": SPARSE3D_SIGNATURES,
 }
+
+# include_open/coalign_amd_ssfa.h: extension header of ABI version 2 (product library), the first under include_open/: the SSFA neck of the SECOND detectors -- the
+# 3 x 3 / stride-2 transposed convolution on SplitMaps and the two-way softmax blend (csrc/ssfa_neck.hip)
+SSFA_SIGNATURES = {
+    "coalign_deconv3x3_s2_weight_bytes": (c_size_t, [c_int, c_int]),
+    "coalign_deconv3x3_s2_sp": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "coalign_ssfa_blend": (c_int, [P, P, P, P, c_float, c_float, P, P, c_int, c_int, c_int, c_int, P, P]),
+}
+
+# header under include_open/ (build.OPEN_HEADERS) -> its table: bound by both loaders AFTER EXT_HEADERS; the next header joins this map
+OPEN_HEADERS = {
+    "coalign_amd_ssfa.h": SSFA_SIGNATURES,
+}
 _LAB_LIB = None
 
 
@@ -303,7 +316,7 @@ def lib() -> ctypes.CDLL:
         return _LIB
     lab = os.environ.get("COALIGN_LAB", "0")             # tools/ only: "1" = the laboratory build with its ablation switches, "vec" = + packed fp32 allowed (build.py)
     path = _build.LABVEC_LIB_PATH if lab == "vec" else _build.LAB_LIB_PATH if lab == "1" else _build.LIB_PATH
-    handle = _load(path, [*HEADERS.values(), *EXT_HEADERS.values()], "; the CoAlign hot path has no CPU fallback")
+    handle = _load(path, [*HEADERS.values(), *EXT_HEADERS.values(), *OPEN_HEADERS.values()], "; the CoAlign hot path has no CPU fallback")
     if handle.coalign_abi_version() != 2:
         raise CoalignHipError(f"ABI version mismatch: library reports {handle.coalign_abi_version()}, binding expects 2")
     _LIB = handle
@@ -315,7 +328,7 @@ def lab_lib() -> ctypes.CDLL:
     and tools call through it; nothing in the detector's default routes does."""
     global _LAB_LIB
     if _LAB_LIB is None:
-        _LAB_LIB = _load(_build.LAB_LIB_PATH, [*HEADERS.values(), *EXT_HEADERS.values(), LAB_SIGNATURES])
+        _LAB_LIB = _load(_build.LAB_LIB_PATH, [*HEADERS.values(), *EXT_HEADERS.values(), *OPEN_HEADERS.values(), LAB_SIGNATURES])
     return _LAB_LIB
 
 

@@ -2466,6 +2466,67 @@ def up2x_concat_sp(skip: torch.Tensor, low: torch.Tensor) -> "SplitMap":
     return out
 
 
+# ---- the SSFA neck of the SECOND detectors (include_open/coalign_amd_ssfa.h, csrc/ssfa_neck.hip) -----------------------------------------------------------
+DECONV3X3_MAX_COUT = 1024     # COALIGN_DECONV3X3_MAX_COUT
+DECONV3X3_TILE = (8, 16)      # COALIGN_DECONV3X3_TILE_H, COALIGN_DECONV3X3_TILE_W: input pixels of a workgroup
+SSFA_BLEND_MAX_C = 512        # COALIGN_SSFA_BLEND_MAX_C
+
+
+def deconv3x3_s2_shape_ok(cin: int, cout: int) -> bool:
+    """A ConvTranspose2d 3 x 3 / stride-2 layer of (cin, cout) fits ``coalign_deconv3x3_s2_sp``."""
+    return cin % 16 == 0 and cin >= 16 and cout % 64 == 0 and 64 <= cout <= DECONV3X3_MAX_COUT
+
+
+@_device_op
+def deconv3x3_s2_sp(x: "SplitMap", w_image: torch.Tensor, bias: torch.Tensor, cout: int, residual: Optional[torch.Tensor] = None, relu: bool = True) -> "SplitMap":
+    """y = act(conv_transpose3x3(x, w, stride 2, padding 1, output_padding 1) + bias) (+ ``residual``, AFTER the activation) on SplitMaps
+    (include_open/coalign_amd_ssfa.h (19b)).  ``w_image``: ``pack_conv3x3_emu_weight(w.permute(1, 0, 2, 3), 16, True)`` of the ConvTranspose2d weight
+    [Cin, Cout, 3, 3]; ``residual``: float32 of logical shape [N, Cout, 2h, 2w] (converted to channels-last memory if it is not) or None."""
+    if not isinstance(x, SplitMap):
+        raise TypeError("deconv3x3_s2_sp reads a SplitMap")
+    _need_gpu(x.data, w_image, bias)
+    L = hip.lib()
+    N, Cin, h, w = x.shape
+    if not deconv3x3_s2_shape_ok(Cin, cout) or w_image.numel() != L.coalign_deconv3x3_s2_weight_bytes(Cin, cout) or bias.numel() != cout:
+        raise ValueError("deconv3x3_s2_sp needs Cin % 16 == 0, Cout % 64 == 0, the tap-major terms-16 weight image of (Cin, Cout) and Cout biases")
+    res_t = None
+    if residual is not None:
+        res_t = to_nhwc(residual)
+        if tuple(res_t.shape) != (N, cout, 2 * h, 2 * w):
+            raise ValueError("residual shape mismatch")
+    out = SplitMap.empty(N, cout, 2 * h, 2 * w, x.device)
+    with _Timed("deconv3x3_s2_sp"):
+        hip.check(L.coalign_deconv3x3_s2_sp(_ptr(x.data), _ptr(w_image), _ptr(_f32c(bias)), _ptr(res_t), _ptr(out.data), N, Cin, cout, h, w, int(bool(relu)),
+                                            _ptr(sp_range_flag(x.device)), _stream()), "coalign_deconv3x3_s2_sp")
+    return out
+
+
+@_device_op
+def ssfa_blend(a: torch.Tensor, b: torch.Tensor, wa: torch.Tensor, wb: torch.Tensor, ba: float, bb: float, out_split: bool = False, out_nhwc: bool = True):
+    """p = softmax over (wa . a + ba, wb . b + bb) per pixel, y = a p + b (1 - p) in one launch (include_open/coalign_amd_ssfa.h (19c)).  ``a``, ``b``: float32 of
+    logical shape [N, C, H, W] (read in place when channels-last); ``wa``, ``wb`` [C].  Returns the channels-last float32 tensor (``out_nhwc``), the SplitMap of it
+    (``out_split``), or the pair (tensor, SplitMap) when both are asked for."""
+    _need_gpu(a, b, wa, wb)
+    if a.dim() != 4 or a.shape != b.shape:
+        raise ValueError("ssfa_blend reads two [N, C, H, W] tensors of one shape")
+    if not (out_split or out_nhwc):
+        raise ValueError("ssfa_blend: at least one output")
+    N, C, H, W = (int(v) for v in a.shape)
+    if C % 16 or not 16 <= C <= SSFA_BLEND_MAX_C or wa.numel() != C or wb.numel() != C:
+        raise ValueError(f"ssfa_blend needs C % 16 == 0, 16 <= C <= {SSFA_BLEND_MAX_C} and [C] weights")
+    at, bt = to_nhwc(a), to_nhwc(b)
+    y = ysp = None
+    if out_nhwc:
+        y = torch.empty((N, H, W, C), dtype=torch.float32, device=at.device).permute(0, 3, 1, 2)
+    if out_split:
+        ysp = SplitMap.empty(N, C, H, W, at.device)
+    with _Timed("ssfa_blend"):
+        hip.check(hip.lib().coalign_ssfa_blend(_ptr(at), _ptr(bt), _ptr(_f32c(wa).reshape(-1)), _ptr(_f32c(wb).reshape(-1)), float(ba), float(bb), _ptr(y),
+                                               _ptr(None if ysp is None else ysp.data), N, C, H, W, _ptr(sp_range_flag(at.device)) if out_split else None, _stream()),
+                  "coalign_ssfa_blend")
+    return (y, ysp) if (out_split and out_nhwc) else (ysp if out_split else y)
+
+
 # ---- the sparse 3-D trunk of the SECOND detectors (include_ext/coalign_amd_sparse3d.h, csrc/sparse_conv3d.hip) -----------------------------------------------
 SP3D_COMBINATIONS = {27: ((4, 16), (16, 16), (16, 32), (32, 32), (32, 64), (64, 64)), 3: ((64, 64), (64, 128))}
 SP3D_STATUS_OVERFLOW = 1
