@@ -46,7 +46,7 @@ EXT_HEADERS = ("coalign_amd_sparse3d.h",)
 # include_open/: every header the ABI gains after include_ext/'s listing was pinned to its one (tests/test_sparse3d_cpu.py); this tuple may grow: hip.OPEN_HEADERS
 # binds them after hip.EXT_HEADERS, and tests/test_ssfa_cpu.py derives what it expects from it
 OPEN_INCLUDE = os.path.join(REPO, "include_open")
-OPEN_HEADERS = ("coalign_amd_ssfa.h",)
+OPEN_HEADERS = ("coalign_amd_ssfa.h", "coalign_amd_sp3d_voxelize.h")
 # per-source extras.  pillar_scatter.hip: its matrix-core encoder reduces the accumulators with VALU right after each instruction
 # pair -- results in VGPRs (not AGPRs) save 64 v_accvgpr_read per pass; -fno-honor-nans drops the canonicalising v_max the compiler
 # puts in front of every two-operand fmaxf of a raw matrix result (20 per pass; the file tests for NaN nowhere, its selects are explicit).

@@ -14,11 +14,13 @@
 //                        no barrier, no atomics.  Epilogue: + shift, ReLU, four 16-byte stores per lane.
 //   sp3d_conv_c4         the 4 -> 16 input layer on fp32 vector arithmetic: one lane per output row, the 27 x 4 x 16 weights in LDS.
 //   sp3d_to_dense        one wavefront per (b, y, x): lanes across the C D channels, a lookup per (lane, d); every element written.
+//   vox_*                raw point clouds -> the trunk's input tensor (mean features, indices, count) with its site index already built: at the end of this file.
 // Counts are read from the device by every kernel (grids are sized by capacity); rows at or past the count are never touched.
 #include "common.h"
 #include "sp16_tiles.h"
 
 #include "coalign_amd_sparse3d.h"
+#include "coalign_amd_sp3d_voxelize.h"
 
 namespace {
 
@@ -159,8 +161,10 @@ __device__ __forceinline__ int block_scan(int v, int *lds, int &total) {
     return incl - v;
 }
 
-__global__ __launch_bounds__(256) void sp3d_block_sums(const Index ix) {
+// (`gate`, in the three kernels of the prefix count: NULL, or a device word -- 0 there makes the launch a no-op; the voxeliser's recount after a max_voxels cut)
+__global__ __launch_bounds__(256) void sp3d_block_sums(const Index ix, const int *__restrict__ gate) {
     __shared__ int lds[256];
+    if (gate && *gate == 0) return;
     const int w0 = blockIdx.x * WORDS_PER_BLOCK + threadIdx.x * 4;
     int c = 0;
 #pragma unroll
@@ -172,8 +176,9 @@ __global__ __launch_bounds__(256) void sp3d_block_sums(const Index ix) {
 }
 
 // one workgroup: sums[b] <- the sites in front of word block b, sums[blocks] <- all sites; the count (clipped to the capacity) and the overflow bit
-__global__ __launch_bounds__(256) void sp3d_scan_sums(const Index ix, int *__restrict__ count_out, unsigned *__restrict__ status) {
+__global__ __launch_bounds__(256) void sp3d_scan_sums(const Index ix, int *__restrict__ count_out, unsigned *__restrict__ status, const int *__restrict__ gate) {
     __shared__ int lds[256];
+    if (gate && *gate == 0) return;
     int carry = 0;
     for (int b0 = 0; b0 < ix.blocks; b0 += 256) {
         const int b = b0 + threadIdx.x;
@@ -190,8 +195,9 @@ __global__ __launch_bounds__(256) void sp3d_scan_sums(const Index ix, int *__res
     }
 }
 
-__global__ __launch_bounds__(256) void sp3d_word_prefix(const Index ix) {
+__global__ __launch_bounds__(256) void sp3d_word_prefix(const Index ix, const int *__restrict__ gate) {
     __shared__ int lds[256];
+    if (gate && *gate == 0) return;
     const int w0 = blockIdx.x * WORDS_PER_BLOCK + threadIdx.x * 4;
     int c[4], s = 0;
 #pragma unroll
@@ -368,14 +374,14 @@ __global__ __launch_bounds__(256) void sp3d_to_dense(const float *__restrict__ f
 unsigned blocks_for(size_t n, size_t per) { return (unsigned)(n == 0 ? 1 : (n + per - 1) / per); }
 
 // the three launches of the prefix count, common to both index builders
-int prefix_count(const Index &ix, int *count_out, unsigned *status, hipStream_t stream) {
-    hipLaunchKernelGGL(sp3d_block_sums, dim3((unsigned)ix.blocks), dim3(256), 0, stream, ix);
+int prefix_count(const Index &ix, int *count_out, unsigned *status, hipStream_t stream, const int *gate = nullptr) {
+    hipLaunchKernelGGL(sp3d_block_sums, dim3((unsigned)ix.blocks), dim3(256), 0, stream, ix, gate);
     int rc = coalign::check_launch();
     if (rc) return rc;
-    hipLaunchKernelGGL(sp3d_scan_sums, dim3(1), dim3(256), 0, stream, ix, count_out, status);
+    hipLaunchKernelGGL(sp3d_scan_sums, dim3(1), dim3(256), 0, stream, ix, count_out, status, gate);
     rc = coalign::check_launch();
     if (rc) return rc;
-    hipLaunchKernelGGL(sp3d_word_prefix, dim3((unsigned)ix.blocks), dim3(256), 0, stream, ix);
+    hipLaunchKernelGGL(sp3d_word_prefix, dim3((unsigned)ix.blocks), dim3(256), 0, stream, ix, gate);
     return coalign::check_launch();
 }
 
@@ -510,5 +516,328 @@ extern "C" int coalign_sp3d_to_dense(const float *feat, const int *count, int ca
     if (misaligned(feat, 15) || misaligned(index, 15) || misaligned(out, 15) || misaligned(count, 3)) return COALIGN_ERR_NULL_POINTER;
     const Index ix = view_of(const_cast<void *>(index), N, D, H, W, capacity);
     hipLaunchKernelGGL(sp3d_to_dense, dim3(blocks_for((size_t)N * H * W, 4)), dim3(256), 0, stream, feat, count, C, ix, out);
+    return coalign::check_launch();
+}
+
+// ---- points -> the input sparse tensor with its site index (include_open/coalign_amd_sp3d_voxelize.h) -----------------------------------------------------------
+// The dense grid is far too large for per-cell tables (90 M cells per agent), but the site index turns a cell into a small number: marking the points' cells in the
+// bitmap and running the prefix count gives every point a PROVISIONAL ROW (the rank of its cell among the occupied cells, ascending in the cell index) by one
+// lookup.  Everything per voxel then lives in tables of P_cap rows:
+//   vox_mark        per point: the cloud (device offsets, clamped and made non-decreasing), filters, cell -> cell[p]; atomicOr into the bitmap; sel[.][p] <- INT_MAX.
+//   (prefix count)  provisional rows.
+//   vox_first       per point: prow[p] = the provisional row; atomicMin(sel[0][row], p): the opening point of the cell.
+//   vox_round t     t = 1 .. T - 1: atomicMin(sel[t][row], p) over the points with p > sel[t - 1][row]: the T smallest point indices of a cell, ascending.
+//   vox_head_count  per 1024-point block of a cloud: its opening points.
+//   vox_cut         voxel number = opening points of the cloud in front (block counts + scan); a cell whose number >= max_voxels loses its bit and raises `dirty`;
+//                   per-cloud kept counts, the max_voxels status bit.
+//   (prefix count)  again, gated by `dirty`: three empty launches for a frame no cloud of which was cut.
+//   vox_emit        per provisional row whose bit survives: final row = its rank; mean of its <= T points in ascending point order, indices, perm[row] = row; the
+//                   count and the overflow bit.
+// Integer atomics only; every result is a minimum or a bit, so the order of arrival does not matter.
+namespace {
+
+constexpr int VOX_CHUNK = 1024;            // points per workgroup of the head kernels: 256 lanes x 4 consecutive points
+constexpr int VOX_NONE = 0x7fffffff;
+
+struct VoxSites {
+    const float4 *pts;
+    const int *offsets;
+    int P_cap, n_clouds, max_blocks;
+    float lo[3], vs[3];
+    int grid[3];                            // the voxel grid (x, y, z)
+    int T, max_voxels, flags;
+    float flo[3], fhi[3];
+    int *cell, *prow, *sel, *blocksum, *dirty;
+    float4 *features;
+    int4 *indices;
+    int *count, *cloud_counts;
+    unsigned *status;
+};
+
+__device__ __forceinline__ int vox_clamp(int v, int hi) { return v < 0 ? 0 : v > hi ? hi : v; }
+
+// the cloud that owns point p, or -1 (offsets clamped to [0, P_cap], non-decreasing by a running maximum)
+__device__ __forceinline__ int vox_cloud_of(const VoxSites &a, int p) {
+    int start = vox_clamp(a.offsets[0], a.P_cap), cloud = -1;
+    for (int c = 0; c < a.n_clouds; ++c) {
+        int end = vox_clamp(a.offsets[c + 1], a.P_cap);
+        end = end < start ? start : end;
+        if (p >= start && p < end) cloud = c;
+        start = end;
+    }
+    return cloud;
+}
+
+__device__ __forceinline__ void vox_span_of(const VoxSites &a, int cloud, int &begin, int &end) {
+    int start = vox_clamp(a.offsets[0], a.P_cap);
+    begin = end = start;
+    for (int c = 0; c <= cloud; ++c) {
+        int e = vox_clamp(a.offsets[c + 1], a.P_cap);
+        e = e < start ? start : e;
+        begin = start;
+        end = e;
+        start = e;
+    }
+}
+
+// the voxel (x, y, z) of a point or false: the expression of cell_of() in voxelize.hip
+__device__ __forceinline__ bool vox_coords(const VoxSites &a, const float4 p, int &x, int &y, int &z) {
+    if (a.flags & COALIGN_VOX_FILTER_EGO) {      // pcd_utils.py:69-88, closed box
+        if (p.x >= -1.95f && p.x <= 2.95f && p.y >= -1.1f && p.y <= 1.1f) return false;
+    }
+    if (a.flags & COALIGN_VOX_FILTER_RANGE) {    // pcd_utils.py:41-66, strict
+        if (!(p.x > a.flo[0] && p.x < a.fhi[0] && p.y > a.flo[1] && p.y < a.fhi[1] && p.z > a.flo[2] && p.z < a.fhi[2])) return false;
+    }
+    const float cx = floorf((p.x - a.lo[0]) / a.vs[0]);
+    const float cy = floorf((p.y - a.lo[1]) / a.vs[1]);
+    const float cz = floorf((p.z - a.lo[2]) / a.vs[2]);
+    // NaN coordinates fail every comparison and are rejected
+    if (!(cx >= 0.0f && cx < (float)a.grid[0] && cy >= 0.0f && cy < (float)a.grid[1] && cz >= 0.0f && cz < (float)a.grid[2])) return false;
+    x = (int)cx; y = (int)cy; z = (int)cz;
+    return true;
+}
+
+// the rank of an occupied cell among the occupied cells (no capacity, no rank -> row table)
+__device__ __forceinline__ int vox_rank(const Index &ix, int cell, bool &set) {
+    const unsigned m = ix.bits[cell >> 5], bit = (unsigned)cell & 31u;
+    set = (m >> bit) & 1u;
+    return ix.prefix[cell >> 5] + __popc(m & ((1u << bit) - 1u));
+}
+
+__global__ __launch_bounds__(256) void vox_mark(const VoxSites a, const Index ix) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p == 0) *a.dirty = 0;
+    if (p >= a.P_cap) return;
+    for (int t = 0; t < a.T; ++t) a.sel[(size_t)t * a.P_cap + p] = VOX_NONE;
+    const int cloud = vox_cloud_of(a, p);
+    int cell = -1, x, y, z;
+    if (cloud >= 0 && vox_coords(a, a.pts[p], x, y, z)) {
+        cell = cell_of(ix.g, cloud, z, y, x);
+        atomicOr(&ix.bits[cell >> 5], 1u << (cell & 31));
+    }
+    a.cell[p] = cell;
+}
+
+__global__ __launch_bounds__(256) void vox_first(const VoxSites a, const Index ix) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.P_cap) return;
+    const int cell = a.cell[p];
+    int row = -1;
+    if (cell >= 0) {
+        bool set;
+        row = vox_rank(ix, cell, set);
+        if (!set || (unsigned)row >= (unsigned)a.P_cap) row = -1;      // (cannot happen: every marked cell holds a point, so there are at most P_cap of them)
+        else atomicMin(&a.sel[row], p);
+    }
+    a.prow[p] = row;
+}
+
+__global__ __launch_bounds__(256) void vox_round(const VoxSites a, int t) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.P_cap) return;
+    const int row = a.prow[p];
+    if (row < 0) return;
+    if (p > a.sel[(size_t)(t - 1) * a.P_cap + row]) atomicMin(&a.sel[(size_t)t * a.P_cap + row], p);
+}
+
+// bit k: point i0 + k of the cloud opens its cell
+__device__ __forceinline__ unsigned vox_heads(const VoxSites &a, int begin, int n, int i0) {
+    unsigned h = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = i0 + k;
+        if (i >= n) continue;
+        const int row = a.prow[begin + i];
+        if (row >= 0 && a.sel[row] == begin + i) h |= 1u << k;
+    }
+    return h;
+}
+
+__global__ __launch_bounds__(256) void vox_head_count(const VoxSites a) {
+    __shared__ int lds[256];
+    const int cloud = blockIdx.y;
+    int begin, end;
+    vox_span_of(a, cloud, begin, end);
+    const unsigned h = vox_heads(a, begin, end - begin, blockIdx.x * VOX_CHUNK + threadIdx.x * 4);
+    int total;
+    (void)block_scan(__popc(h), lds, total);
+    if (threadIdx.x == 0) a.blocksum[cloud * a.max_blocks + blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(256) void vox_cut(const VoxSites a, const Index ix) {
+    __shared__ int lds[256];
+    __shared__ int opened[COALIGN_SP3D_VOXELIZE_MAX_CLOUDS];
+    const int cloud = blockIdx.y;
+    if (blockIdx.x == 0 && blockIdx.y == 0) {          // the kept voxels of every cloud, their sum, the max_voxels bit
+        if ((int)threadIdx.x < a.n_clouds) {
+            int s = 0;
+            for (int b = 0; b < a.max_blocks; ++b) s += a.blocksum[threadIdx.x * a.max_blocks + b];
+            opened[threadIdx.x] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int sum = 0;
+            bool reached = false;
+            for (int c = 0; c < a.n_clouds; ++c) {
+                const int kept = opened[c] < a.max_voxels ? opened[c] : a.max_voxels;
+                reached = reached || opened[c] >= a.max_voxels;
+                a.cloud_counts[c] = kept;
+                sum += kept;
+            }
+            a.cloud_counts[a.n_clouds] = sum;
+            if (reached) *a.status = *a.status | COALIGN_SP3D_STATUS_MAX_VOXELS;
+        }
+    }
+    int before = 0;
+    for (int b = threadIdx.x; b < (int)blockIdx.x; b += 256) before += a.blocksum[cloud * a.max_blocks + b];
+    int in_front;
+    (void)block_scan(before, lds, in_front);
+    int begin, end;
+    vox_span_of(a, cloud, begin, end);
+    const int i0 = blockIdx.x * VOX_CHUNK + threadIdx.x * 4;
+    const unsigned h = vox_heads(a, begin, end - begin, i0);
+    int total;
+    int number = in_front + block_scan(__popc(h), lds, total);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (!(h >> k & 1u)) continue;
+        if (number >= a.max_voxels) {                  // the cell would open voxel number >= max_voxels: dropped with all its points
+            const int cell = a.cell[begin + i0 + k];
+            atomicAnd(&ix.bits[cell >> 5], ~(1u << (cell & 31)));
+            *a.dirty = 1;
+        }
+        ++number;
+    }
+}
+
+__global__ __launch_bounds__(256) void vox_emit(const VoxSites a, const Index ix) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r == 0) {
+        const int kept = ix.sums[ix.blocks];
+        *a.count = kept > ix.cap ? ix.cap : kept;
+        if (kept > ix.cap) *a.status = *a.status | COALIGN_SP3D_STATUS_OVERFLOW;
+    }
+    if (r >= a.P_cap) return;
+    const int p0 = a.sel[r];
+    if ((unsigned)p0 >= (unsigned)a.P_cap) return;     // no such provisional row
+    const int cell = a.cell[p0];
+    if (cell < 0) return;
+    bool set;
+    const int row = vox_rank(ix, cell, set);
+    if (!set || (unsigned)row >= (unsigned)ix.cap) return;      // cut by max_voxels, or past the capacity
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    int n = 0;
+    for (int t = 0; t < a.T; ++t) {
+        const int p = a.sel[(size_t)t * a.P_cap + r];
+        if ((unsigned)p >= (unsigned)a.P_cap) break;
+        const float4 v = a.pts[p];
+        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+        ++n;
+    }
+    const float d = (float)n;
+    a.features[row] = make_float4(s.x / d, s.y / d, s.z / d, s.w / d);
+    const int x = cell % ix.g.W, t = cell / ix.g.W, y = t % ix.g.H, u = t / ix.g.H, z = u % ix.g.D, b = u / ix.g.D;
+    a.indices[row] = make_int4(b, z, y, x);
+    ix.perm[row] = row;
+}
+
+struct VoxWorkspace {
+    size_t cell, prow, sel, blocksum, dirty, total;
+};
+
+VoxWorkspace vox_layout(int P_cap, int n_clouds, int T) {
+    VoxWorkspace w;
+    size_t o = 0;
+    auto take = [&](size_t ints) { const size_t at = o; o = align_up(o + ints * sizeof(int), 256); return at; };
+    w.cell = take((size_t)P_cap);
+    w.prow = take((size_t)P_cap);
+    w.sel = take((size_t)P_cap * T);
+    w.blocksum = take((size_t)n_clouds * ((P_cap + VOX_CHUNK - 1) / VOX_CHUNK));
+    w.dirty = take(1);
+    w.total = o;
+    return w;
+}
+
+bool vox_sizes_ok(int P_cap, int n_clouds, int T) {
+    return P_cap >= 1 && P_cap <= COALIGN_SP3D_VOXELIZE_MAX_P_CAP && n_clouds >= 1 && n_clouds <= COALIGN_SP3D_VOXELIZE_MAX_CLOUDS && T >= 1 &&
+           T <= COALIGN_SP3D_VOXELIZE_MAX_POINTS;
+}
+
+}  // namespace
+
+extern "C" size_t coalign_sp3d_voxelize_workspace_bytes(int P_cap, int n_clouds, int max_points) {
+    if (!vox_sizes_ok(P_cap, n_clouds, max_points)) return 0;
+    return vox_layout(P_cap, n_clouds, max_points).total;
+}
+
+extern "C" int coalign_sp3d_voxelize(const float *points, const int *offsets, int P_cap, int n_clouds, const double *voxel_size, const double *lidar_range, int D, int H,
+                                     int W, int max_points, int max_voxels, int flags, const double *filter_range, float *features, int *indices, int *count,
+                                     int *cloud_counts, int capacity, void *index, size_t index_bytes, unsigned *status, void *workspace, size_t workspace_bytes,
+                                     void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!voxel_size || !lidar_range) return COALIGN_ERR_NULL_POINTER;
+    if (P_cap < 1 || P_cap > COALIGN_SP3D_VOXELIZE_MAX_P_CAP || capacity < 1 || n_clouds < 1 || max_voxels < 1 || max_points < 1) return COALIGN_ERR_BAD_SHAPE;
+    if (n_clouds > COALIGN_SP3D_VOXELIZE_MAX_CLOUDS || max_points > COALIGN_SP3D_VOXELIZE_MAX_POINTS) return COALIGN_ERR_UNSUPPORTED;
+    if (flags & ~(COALIGN_VOX_FILTER_EGO | COALIGN_VOX_FILTER_RANGE)) return COALIGN_ERR_UNSUPPORTED;
+    if ((flags & COALIGN_VOX_FILTER_RANGE) && !filter_range) return COALIGN_ERR_NULL_POINTER;
+    VoxSites a{};
+    for (int j = 0; j < 3; ++j) {   // float32 round((max - min) / voxel), sp_voxel_preprocessor.py:40-42, as coalign_voxelize
+        const float q = ((float)lidar_range[3 + j] - (float)lidar_range[j]) / (float)voxel_size[j];
+        if (!(q >= 0.5f && q < 65536.0f)) return COALIGN_ERR_BAD_SHAPE;
+        a.grid[j] = (int)nearbyintf(q);
+    }
+    if (!grid_ok(n_clouds, D, H, W) || W != a.grid[0] || H != a.grid[1] || D < a.grid[2]) return COALIGN_ERR_BAD_SHAPE;
+    if (index_bytes < layout_of(n_clouds, D, H, W, capacity).bytes) return COALIGN_ERR_WORKSPACE;
+    const VoxWorkspace w = vox_layout(P_cap, n_clouds, max_points);
+    if (workspace_bytes < w.total) return COALIGN_ERR_WORKSPACE;
+    if (!points || !offsets || !features || !indices || !count || !cloud_counts || !index || !status || !workspace) return COALIGN_ERR_NULL_POINTER;
+    if (misaligned(points, 15) || misaligned(features, 15) || misaligned(indices, 15) || misaligned(index, 15) || misaligned(workspace, 15) || misaligned(offsets, 3) ||
+        misaligned(count, 3) || misaligned(cloud_counts, 3) || misaligned(status, 3))
+        return COALIGN_ERR_NULL_POINTER;
+    char *ws = static_cast<char *>(workspace);
+    a.pts = reinterpret_cast<const float4 *>(points);
+    a.offsets = offsets;
+    a.P_cap = P_cap;
+    a.n_clouds = n_clouds;
+    a.max_blocks = (P_cap + VOX_CHUNK - 1) / VOX_CHUNK;
+    for (int j = 0; j < 3; ++j) {
+        a.lo[j] = (float)lidar_range[j];
+        a.vs[j] = (float)voxel_size[j];
+        if (flags & COALIGN_VOX_FILTER_RANGE) {
+            a.flo[j] = (float)filter_range[j];
+            a.fhi[j] = (float)filter_range[3 + j];
+        }
+    }
+    a.T = max_points;
+    a.max_voxels = max_voxels;
+    a.flags = flags;
+    a.cell = reinterpret_cast<int *>(ws + w.cell);
+    a.prow = reinterpret_cast<int *>(ws + w.prow);
+    a.sel = reinterpret_cast<int *>(ws + w.sel);
+    a.blocksum = reinterpret_cast<int *>(ws + w.blocksum);
+    a.dirty = reinterpret_cast<int *>(ws + w.dirty);
+    a.features = reinterpret_cast<float4 *>(features);
+    a.indices = reinterpret_cast<int4 *>(indices);
+    a.count = count;
+    a.cloud_counts = cloud_counts;
+    a.status = status;
+    const Index ix = view_of(index, n_clouds, D, H, W, capacity);
+    const dim3 per_point(blocks_for((size_t)P_cap, 256)), per_chunk((unsigned)a.max_blocks, (unsigned)n_clouds);
+    int rc = coalign::fill_words(ix.bits, (size_t)ix.words, 0u, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(vox_mark, per_point, dim3(256), 0, stream, a, ix);
+    rc = coalign::check_launch();
+    if (rc) return rc;
+    rc = prefix_count(ix, nullptr, nullptr, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(vox_first, per_point, dim3(256), 0, stream, a, ix);
+    for (int t = 1; t < max_points; ++t) hipLaunchKernelGGL(vox_round, per_point, dim3(256), 0, stream, a, t);
+    hipLaunchKernelGGL(vox_head_count, per_chunk, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(vox_cut, per_chunk, dim3(256), 0, stream, a, ix);
+    rc = coalign::check_launch();
+    if (rc) return rc;
+    rc = prefix_count(ix, nullptr, nullptr, stream, a.dirty);
+    if (rc) return rc;
+    hipLaunchKernelGGL(vox_emit, per_point, dim3(256), 0, stream, a, ix);
     return coalign::check_launch();
 }

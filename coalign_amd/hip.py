@@ -277,9 +277,17 @@ SSFA_SIGNATURES = {
     "coalign_ssfa_blend": (c_int, [P, P, P, P, c_float, c_float, P, P, c_int, c_int, c_int, c_int, P, P]),
 }
 
+# include_open/coalign_amd_sp3d_voxelize.h: raw point clouds -> the input sparse tensor of VoxelBackBone8x (mean features, indices, device count, level-0 site
+# index) on the bitmap + prefix-count site index (csrc/sparse_conv3d.hip); voxel_size / lidar_range / filter_range are host float64 arrays
+SP3D_VOXELIZE_SIGNATURES = {
+    "coalign_sp3d_voxelize_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "coalign_sp3d_voxelize": (c_int, [P, P, c_int, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, c_int, P, c_size_t, P, P, c_size_t, P]),
+}
+
 # header under include_open/ (build.OPEN_HEADERS) -> its table: bound by both loaders AFTER EXT_HEADERS; the next header joins this map
 OPEN_HEADERS = {
     "coalign_amd_ssfa.h": SSFA_SIGNATURES,
+    "coalign_amd_sp3d_voxelize.h": SP3D_VOXELIZE_SIGNATURES,
 }
 _LAB_LIB = None
 

@@ -2652,3 +2652,55 @@ def sp3d_to_dense(feat: torch.Tensor, count: torch.Tensor, index: torch.Tensor, 
     with _Timed("sp3d_to_dense"):
         hip.check(hip.lib().coalign_sp3d_to_dense(_ptr(feat), _ptr(count), cap, C, _ptr(index), index.numel(), batch, D, H, W, _ptr(out), _stream()), "coalign_sp3d_to_dense")
     return out
+
+
+# ---- raw point clouds -> the trunk's input sparse tensor (include_open/coalign_amd_sp3d_voxelize.h, csrc/sparse_conv3d.hip) -----------------------------------
+SP3D_STATUS_MAX_VOXELS = 2            # COALIGN_SP3D_STATUS_MAX_VOXELS
+SP3D_VOXELIZE_MAX_POINTS = 8          # COALIGN_SP3D_VOXELIZE_MAX_POINTS
+SP3D_VOXELIZE_MAX_CLOUDS = 16         # COALIGN_SP3D_VOXELIZE_MAX_CLOUDS
+
+
+def sp3d_voxel_grid(voxel_size: Sequence[float], lidar_range: Sequence[float]) -> Tuple[int, int, int]:
+    """The voxel grid (x, y, z) as the kernels and ``coalign_voxelize`` compute it: round((hi - lo) / vs) in float32 (sp_voxel_preprocessor.py:40-42)."""
+    r, v = np.asarray(lidar_range, dtype=np.float32), np.asarray(voxel_size, dtype=np.float32)
+    return tuple(int(g) for g in np.round((r[3:6] - r[0:3]) / v))
+
+
+@_device_op
+def sp3d_voxelize(points: torch.Tensor, offsets: torch.Tensor, voxel_size: Sequence[float], lidar_range: Sequence[float], shape, max_points: int, max_voxels: int,
+                  capacity: int, ego_filter: bool = False, filter_range: Optional[Sequence[float]] = None, status: Optional[torch.Tensor] = None):
+    """points [P_cap, 4] float32 (the clouds of a frame concatenated), ``offsets``: DEVICE int32 [n_clouds + 1] -> (features [capacity, 4] mean of each voxel's first
+    ``max_points`` points, indices [capacity, 4] int32 (cloud, z, y, x) ascending in the linear cell index of the sparse ``shape`` (D, H, W), count [1] int32, cloud_counts
+    [n_clouds + 1] int32, the site index, status [1] int32), all on the device: no host read, no synchronisation, safe inside a captured graph (the offsets are read by
+    the kernels, so a replay may see other clouds of other lengths)."""
+    _need_gpu(points, offsets)
+    L = hip.lib()
+    if points.dim() != 2 or points.shape[1] != 4 or points.dtype != torch.float32:
+        raise ValueError(f"points must be float32 [P, 4], got {points.dtype} {tuple(points.shape)}")
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.numel() < 2:
+        raise ValueError("offsets must be a device int32 tensor [n_clouds + 1]")
+    pts, off = _aligned16(points), offsets.contiguous()
+    n_clouds, P_cap = off.numel() - 1, pts.shape[0]
+    D, H, W = (int(v) for v in shape)
+    dev = pts.device
+    vs, rg = _dbl3(voxel_size), (ctypes.c_double * 6)(*[float(v) for v in lidar_range])
+    fr = None if filter_range is None else (ctypes.c_double * 6)(*[float(v) for v in filter_range])
+    flags = (VOX_FILTER_EGO if ego_filter else 0) | (VOX_FILTER_RANGE if filter_range is not None else 0)
+    ws_bytes = L.coalign_sp3d_voxelize_workspace_bytes(P_cap, n_clouds, int(max_points))
+    if ws_bytes == 0:
+        raise ValueError(f"sp3d_voxelize: {P_cap} points, {n_clouds} clouds (1 .. {SP3D_VOXELIZE_MAX_CLOUDS}), max_points {max_points} (1 .. {SP3D_VOXELIZE_MAX_POINTS}) "
+                         "is outside the kernels' range")
+    nbytes = sp3d_index_bytes(n_clouds, (D, H, W), capacity)
+    features = torch.empty((capacity, 4), dtype=torch.float32, device=dev)
+    indices = torch.empty((capacity, 4), dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    cloud_counts = torch.empty(n_clouds + 1, dtype=torch.int32, device=dev)
+    index = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    with _Timed("sp3d_voxelize"):
+        hip.check(L.coalign_sp3d_voxelize(_ptr(pts), _ptr(off), P_cap, n_clouds, vs, rg, D, H, W, int(max_points), int(max_voxels), flags, fr, _ptr(features), _ptr(indices),
+                                          _ptr(count), _ptr(cloud_counts), int(capacity), _ptr(index), nbytes, _ptr(status), _ptr(ws), ws_bytes, _stream()),
+                  "coalign_sp3d_voxelize")
+    return features, indices, count, cloud_counts, index, status

@@ -47,6 +47,22 @@ class SpVoxelPreprocessor:
         m = host[-1]
         return {"voxel_features": voxels[:m], "voxel_coords": coords[:m], "voxel_num_points": num[:m], "voxel_counts": host[:-1]}
 
+    # ------------------------------------------------------------------------------------------ whole frame -> the sparse trunk's input, no host read
+    def preprocess_clouds_sites(self, clouds: Sequence, ego_filter: bool = False, filter_range: Optional[Sequence[float]] = None, capacity: Optional[int] = None) -> dict:
+        """The SECOND detectors' form of ``preprocess_clouds`` (whose dense tables refuse their 0.1 m grid): the per-cav ``preprocess`` calls, ``collate_batch`` and
+        ``MeanVFE`` of one frame as ``sparse3d.voxel_sites`` -- {"voxel_sites": the input ``SparseTensor3d`` of ``VoxelBackBone8x`` (sparse shape (gz + 1, gy, gx), mean
+        features, device count, rows ascending in the cell index), "voxel_counts": device int32 [n_clouds + 1] (kept voxels per cloud, then their sum)}.  ``capacity``
+        (rows): ``n_clouds * max_voxels`` by default.  Nothing is read back from the device."""
+        from . import sparse3d
+        pts = [_as_device_points(c, self.device) for c in clouds]
+        offsets = torch.tensor(np.concatenate([[0], np.cumsum([p.shape[0] for p in pts])]), dtype=torch.int32).to(self.device)
+        allpts = torch.cat(pts) if len(pts) > 1 else pts[0]
+        gx, gy, gz = ops.sp3d_voxel_grid(self.voxel_size, self.lidar_range)
+        cap = len(pts) * int(self.max_voxels) if capacity is None else int(capacity)
+        sites = sparse3d.voxel_sites(allpts, offsets, self.voxel_size, self.lidar_range, (gz + 1, gy, gx), self.max_points_per_voxel, self.max_voxels, cap,
+                                     ego_filter=ego_filter, filter_range=filter_range)
+        return {"voxel_sites": sites, "voxel_counts": sites.cloud_counts}
+
     # ------------------------------------------------------------------------------------------ reference-shaped API
     def preprocess(self, pcd_np) -> Dict[str, torch.Tensor]:
         """One cloud -> ``voxel_features`` [M, P, 4], ``voxel_coords`` [M, 3] (z, y, x), ``voxel_num_points`` [M]

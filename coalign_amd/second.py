@@ -5,8 +5,10 @@ shrink header -> heads.  ``SSFA`` and ``Head`` keep the reference's parameter na
 off by default) an eval-mode float32 CUDA map takes the kernel route of DESIGN.md section 8n-2: the 3 x 3 convolutions on ``ops.conv3x3_sp`` / ``ops.conv3x3_sp_s2``,
 ``trans_0`` / ``trans_1`` on the pointwise kernel, the transposed convolutions on ``ops.deconv3x3_s2_sp``, the blend on ``ops.ssfa_blend``, the shrink header on SplitMaps
 and the heads as one ``ops.heads_sp`` launch.  ``SecondSSFAUncertainty`` emits the four head maps of ``PointPillarUncertainty`` (cls / reg / unc [/ dir]), so ``post_process_stage1_device``,
-``PoseCorrector`` and ``inference_intermediate_fusion_aligned(stage1_model=...)`` take it unchanged.  The model reads ``processed_lidar`` as the reference does (the
-device voxeliser refuses this grid's 90 M cells).
+``PoseCorrector`` and ``inference_intermediate_fusion_aligned(stage1_model=...)`` take it unchanged.  The model reads ``processed_lidar`` as the reference does
+(``voxel_features`` / ``voxel_coords`` / ``voxel_num_points`` from the host voxeliser), or -- ``lidar_from_points`` -- a ``voxel_sites`` entry made from the raw clouds
+on the device: ``sparse3d.voxel_sites`` (``ops.sp3d_voxelize``) voxelises on the trunk's own site index, which holds this grid's 90 M cells per
+agent where ``coalign_voxelize``'s dense tables do not; MeanVFE is inside it and no count is read back.
 """
 from __future__ import annotations
 
@@ -262,8 +264,29 @@ def _batch_size(data_dict: dict, coords: torch.Tensor) -> int:
     return int(coords[:, 0].max()) + 1 if coords.shape[0] else 1
 
 
+def lidar_from_points(model_or_hypes, clouds, ego_filter: bool = False, filter_range=None, capacity: Optional[int] = None, train: bool = False,
+                      max_points: int = 5, max_voxels: Optional[int] = None, device=None) -> dict:
+    """The ``processed_lidar`` of a frame from its raw clouds (a list of [n_i, 4] arrays / tensors, one per agent), without the host voxeliser:
+    ``model({"processed_lidar": lidar_from_points(model, clouds)})``.  -> {"voxel_sites": ``sparse3d.voxel_sites``' tensor, "voxel_counts": device int32 [n + 1]}
+    (``preprocess.SpVoxelPreprocessor.preprocess_clouds_sites``).  ``model_or_hypes``: a config (its ``preprocess`` section gives voxel size, range, points per voxel
+    and ``max_voxel_train`` / ``max_voxel_test`` by ``train``) or a built SECOND model (its own voxel size and range; ``max_points`` and ``max_voxels`` -- 70 000, in
+    training 36 000: the shipped configs' -- from the arguments).  ``device``: the model's, else the GPU when there is one."""
+    from .preprocess import SpVoxelPreprocessor
+    if isinstance(model_or_hypes, dict):
+        params = model_or_hypes["preprocess"]
+        dev = device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu")
+    else:
+        m = model_or_hypes
+        mv = int(max_voxels) if max_voxels is not None else (36000 if train else 70000)
+        params = {"cav_lidar_range": list(m.lidar_range), "args": {"voxel_size": list(m.voxel_size), "max_points_per_voxel": int(max_points), "max_voxel_train": mv,
+                                                                   "max_voxel_test": mv}}
+        dev = device if device is not None else next(m.parameters()).device
+    return SpVoxelPreprocessor(params, train, dev).preprocess_clouds_sites(clouds, ego_filter=ego_filter, filter_range=filter_range, capacity=capacity)
+
+
 class _SecondTrunk(nn.Module):
     def _build_trunk(self, args: dict) -> None:
+        self.lidar_range, self.voxel_size = [float(v) for v in args["lidar_range"]], [float(v) for v in args["voxel_size"]]
         rng = np.array(args["lidar_range"])
         grid_size = np.round((rng[3:6] - rng[:3]) / np.array(args["voxel_size"])).astype(np.int64)
         self.vfe = MeanVFE(args["mean_vfe"], args["mean_vfe"]["num_point_features"])
@@ -280,6 +303,9 @@ class _SecondTrunk(nn.Module):
     def bev_features(self, data_dict: dict) -> torch.Tensor:
         """processed_lidar -> the dense map [N, C D, H, W] in front of SSFA."""
         pl = data_dict["processed_lidar"]
+        if pl.get("voxel_sites") is not None:      # ``lidar_from_points``: MeanVFE is inside the tensor, the batch size is its own (no ``_batch_size`` read-back)
+            sites = pl["voxel_sites"]
+            return self.map_to_bev(self.spconv_block({"voxel_sites": sites, "batch_size": sites.batch_size}))["spatial_features"]
         batch = {"voxel_features": pl["voxel_features"], "voxel_coords": pl["voxel_coords"], "voxel_num_points": pl["voxel_num_points"],
                  "batch_size": _batch_size(data_dict, pl["voxel_coords"])}
         return self.map_to_bev(self.spconv_block(self.vfe(batch)))["spatial_features"]

@@ -407,10 +407,15 @@ class VoxelBackBone8x(nn.Module):
     def forward(self, batch_dict: dict) -> dict:
         for _, m in self.sparse_convs():
             m.site_capacity = self.site_capacity
-        f, coords = batch_dict["voxel_features"], batch_dict["voxel_coords"]
-        x = SparseTensor3d(f, coords.int(), self.sparse_shape, int(batch_dict["batch_size"]))
-        if f.is_cuda:
-            x.status = torch.zeros(1, dtype=torch.int32, device=f.device)
+        if batch_dict.get("voxel_sites") is not None:      # ``voxel_sites``' tensor: mean features, a device count, the batch size and (kernel route) the site index are its own
+            x = batch_dict["voxel_sites"]
+            if tuple(x.spatial_shape) != tuple(self.sparse_shape):
+                raise ValueError(f"voxel_sites of spatial shape {x.spatial_shape} for a backbone of sparse shape {self.sparse_shape}")
+        else:
+            f, coords = batch_dict["voxel_features"], batch_dict["voxel_coords"]
+            x = SparseTensor3d(f, coords.int(), self.sparse_shape, int(batch_dict["batch_size"]))
+            if f.is_cuda:
+                x.status = torch.zeros(1, dtype=torch.int32, device=f.device)
         x = self.conv_input(x)
         x_conv1 = self.conv1(x)
         x_conv2 = self.conv2(x_conv1)
@@ -446,6 +451,110 @@ class HeightCompression(nn.Module):
         batch_dict["spatial_features"] = self.compress(batch_dict["encoded_spconv_tensor"])
         batch_dict["spatial_features_stride"] = batch_dict["encoded_spconv_tensor_stride"]
         return batch_dict
+
+
+# ---- raw point clouds -> the trunk's input tensor ------------------------------------------------------------------------------------------------------------------
+VOXEL_SITES_KERNEL_DEFAULT = True          # ``voxel_sites`` on ``ops.sp3d_voxelize`` for CUDA points when COALIGN_SP3D is unset: 0.283 ms against 2.25 ms for the torch ops at the OPV2V grid, 5 agents
+VOXEL_SITES_KERNEL_TEXT = "coalign_sp3d_voxelize (bitmap mark + prefix count, integer atomicMin rounds, mean features and the level-0 site index in one call)"
+VOXEL_SITES_TORCH_TEXT = "torch ops (floor-divide, sort by (cell, point), segment ranks, index_add)"
+
+
+def voxel_sites_kernels() -> bool:
+    v = os.environ.get("COALIGN_SP3D")
+    return VOXEL_SITES_KERNEL_DEFAULT if v is None else v != "0"
+
+
+def voxel_sites_route_text() -> str:
+    if voxel_sites_kernels():
+        return VOXEL_SITES_KERNEL_TEXT
+    return f"{VOXEL_SITES_TORCH_TEXT} ({'COALIGN_SP3D=0' if os.environ.get('COALIGN_SP3D') == '0' else 'the kernel route is not the default: COALIGN_SP3D=1 asks for it'})"
+
+
+def _voxel_sites_torch(points, offsets, voxel_size, lidar_range, shape, max_points, max_voxels, capacity, ego_filter, filter_range):
+    """The contract of include_open/coalign_amd_sp3d_voxelize.h in torch ops (any device; reads counts back to size its tensors): same rows, same order, same bits."""
+    dev, P = points.device, points.shape[0]
+    D, H, W = shape
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=dev)
+    n_clouds = offsets.numel() - 1
+    off = torch.cummax(offsets.to(device=dev, dtype=torch.int64).clamp(0, P), dim=0).values
+    p = torch.arange(P, device=dev)
+    cloud = torch.searchsorted(off[1:].contiguous(), p, right=True)
+    ok = (p >= off[0]) & (cloud < n_clouds)
+    x, y, z = points[:, 0], points[:, 1], points[:, 2]
+    if ego_filter:                                   # pcd_utils.py:69-88, closed box
+        ok &= ~((x >= f32(-1.95)) & (x <= f32(2.95)) & (y >= f32(-1.1)) & (y <= f32(1.1)))
+    if filter_range is not None:                     # pcd_utils.py:41-66, strict
+        fr = f32([float(v) for v in filter_range])
+        ok &= (x > fr[0]) & (x < fr[3]) & (y > fr[1]) & (y < fr[4]) & (z > fr[2]) & (z < fr[5])
+    rng = f32([float(v) for v in lidar_range])
+    vs = f32([float(v) for v in voxel_size])
+    grid = f32([float(g) for g in ops.sp3d_voxel_grid(voxel_size, lidar_range)])
+    c = torch.floor((points[:, :3] - rng[:3]) / vs)                                    # float32, IEEE divide: the kernels' expression
+    ok &= ((c >= 0) & (c < grid)).all(dim=1)                                           # (NaN fails every comparison)
+    p = p[ok]
+    ci = c[ok].to(torch.int64)
+    cell = ((cloud[ok] * D + ci[:, 2]) * H + ci[:, 1]) * W + ci[:, 0]
+    key, _ = torch.sort(cell * max(P, 1) + p)                                          # by cell, then by point index
+    cell, p = key // max(P, 1), key % max(P, 1)
+    start = torch.ones_like(cell, dtype=torch.bool)
+    start[1:] = cell[1:] != cell[:-1]
+    group = torch.cumsum(start, 0) - 1                                                 # the cell's place among the occupied cells (ascending)
+    first = torch.nonzero(start).flatten()
+    pos = torch.arange(cell.numel(), device=dev) - first[group] if cell.numel() else group
+    gcell, gfirst = cell[first], p[first]                                              # per occupied cell: the cell, its opening point
+    gcloud = gcell // (D * H * W)
+    rank = torch.empty_like(gfirst)
+    rank[torch.argsort(gfirst)] = torch.arange(gfirst.numel(), device=dev)             # clouds are contiguous and ascending in the point index:
+    per_cloud = torch.bincount(gcloud, minlength=n_clouds)[:n_clouds]                   # the rank among ALL opening points minus the opened cells of the clouds in front
+    number = rank - (torch.cumsum(per_cloud, 0) - per_cloud)[gcloud]
+    keep = number < max_voxels
+    kept_per_cloud = torch.bincount(gcloud[keep], minlength=n_clouds)[:n_clouds]
+    cloud_counts = torch.cat([kept_per_cloud, kept_per_cloud.sum().view(1)]).to(torch.int32)
+    row = torch.cumsum(keep, 0) - 1
+    kept = int(keep.sum())
+    n_rows = min(kept, capacity)
+    live = keep & (row < capacity)
+    feats = points.new_zeros((capacity, 4))
+    indices = torch.zeros((capacity, 4), dtype=torch.int32, device=dev)
+    counts = torch.zeros(capacity, dtype=torch.int64, device=dev)
+    pl = live[group] if cell.numel() else live
+    for t in range(max_points):                                                        # ascending point order: slot t of every voxel in one step
+        m = pl & (pos == t)
+        r = row[group[m]]
+        feats[r] = feats[r] + points[p[m]]
+        counts[r] += 1
+    feats[:n_rows] = feats[:n_rows] / counts[:n_rows].to(torch.float32).unsqueeze(1)
+    lc = gcell[live]
+    indices[:n_rows] = torch.stack([lc // (D * H * W), lc // (H * W) % D, lc // W % H, lc % W], dim=1).to(torch.int32)
+    status = (ops.SP3D_STATUS_OVERFLOW if kept > capacity else 0) | (ops.SP3D_STATUS_MAX_VOXELS if bool((per_cloud >= max_voxels).any()) else 0)
+    count = torch.tensor([n_rows], dtype=torch.int32, device=dev)
+    return feats, indices, count, cloud_counts, torch.tensor([status], dtype=torch.int32, device=dev)
+
+
+def voxel_sites(points: torch.Tensor, offsets: torch.Tensor, voxel_size, lidar_range, spatial_shape, max_points: int, max_voxels: int, capacity: int,
+                ego_filter: bool = False, filter_range=None) -> SparseTensor3d:
+    """Raw clouds -> the input tensor of ``VoxelBackBone8x``: ``points`` [P, 4] float32 (the clouds of a frame concatenated), ``offsets`` int32 [n_clouds + 1] (on the
+    points' device for the kernel route) -> a ``SparseTensor3d`` of ``capacity`` rows with the mean of each voxel's first ``max_points`` points (MeanVFE), rows ascending
+    in the linear cell index, a device ``count``, ``status`` (bit 0: more voxels than ``capacity``, bit 1: a cloud reached ``max_voxels``), ``cloud_counts`` int32
+    [n_clouds + 1] and, on the kernel route, ``_index`` already built.  The contract is that of include_open/coalign_amd_sp3d_voxelize.h on both routes, bit for bit."""
+    shape = tuple(int(v) for v in spatial_shape)
+    n_clouds = int(offsets.numel()) - 1
+    gx, gy, gz = ops.sp3d_voxel_grid(voxel_size, lidar_range)
+    if points.dim() != 2 or points.shape[1] != 4 or n_clouds < 1 or capacity < 1 or max_points < 1 or max_voxels < 1:
+        raise ValueError("voxel_sites: points [P, 4], at least one cloud, capacity, max_points and max_voxels of at least 1")
+    if shape[1:] != (gy, gx) or shape[0] < gz:
+        raise ValueError(f"voxel_sites: the sparse shape {shape} does not hold the voxel grid (z, y, x) = {(gz, gy, gx)}")
+    if points.is_cuda and points.dtype == torch.float32 and voxel_sites_kernels():
+        feats, indices, count, cloud_counts, index, status = ops.sp3d_voxelize(points, offsets.to(device=points.device, dtype=torch.int32), voxel_size, lidar_range, shape,
+                                                                               max_points, max_voxels, capacity, ego_filter, filter_range)
+    else:
+        feats, indices, count, cloud_counts, status = _voxel_sites_torch(points.float(), offsets, voxel_size, lidar_range, shape, int(max_points), int(max_voxels),
+                                                                         int(capacity), ego_filter, filter_range)
+        index = None
+    x = SparseTensor3d(feats, indices, shape, n_clouds, count, status)
+    x._index = index
+    x.cloud_counts = cloud_counts
+    return x
 
 
 def plan(hypes: dict) -> dict:
