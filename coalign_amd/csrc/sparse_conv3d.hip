@@ -10,8 +10,10 @@
 //   sp3d_conv_mfma       output-stationary: a wavefront owns 32 output rows x 32 output channels.  Per tap a lane reads its row's neighbour and, when any of the 32
 //                        has one, 8 of the neighbour's channels (32 contiguous bytes), splits them into an sp16 pair in registers (the B operand of
 //                        v_mfma_f32_32x32x16_f16) and multiplies with the weight image's 32-byte piece (the A operand), three instructions per fp32 product
-//                        (sp16_tiles.h).  Taps in ascending order, a missing neighbour is a zero row, a tap none of the 32 rows has is skipped (it adds zeros); a row without any neighbour is no site and is written as zeros.  No LDS,
-//                        no barrier, no atomics.  Epilogue: + shift, ReLU, four 16-byte stores per lane.
+//                        (sp16_tiles.h).  Every row of the weight image is divided by a power of two 2^k_c on the host so that its largest |w| lies in [1, 2) -- an UNSCALED pair keeps
+//                        an absolute 2^-34 of a weight below 2^-14, which costs a channel whose folded batch-norm scale is small most of its digits -- and the epilogue
+//                        multiplies the joined sum by 2^k_c from the image's tail (exact: a layer whose pairs were all normal gives the same bits).  Taps in ascending order, a missing neighbour is a zero row, a tap none of the 32 rows has is skipped (it adds zeros); a row without any neighbour is no site and is written as zeros.  No LDS,
+//                        no barrier, no atomics.  Epilogue: x 2^k_c, + shift, ReLU, four 16-byte stores per lane.
 //   sp3d_conv_c4         the 4 -> 16 input layer on fp32 vector arithmetic: one lane per output row, the 27 x 4 x 16 weights in LDS.
 //   sp3d_to_dense        one wavefront per (b, y, x): lanes across the C D channels, a lookup per (lane, d); every element written.
 //   vox_*                raw point clouds -> the trunk's input tensor (mean features, indices, count) with its site index already built: at the end of this file.
@@ -261,7 +263,7 @@ struct ConvArgs {
     const float *in;
     const int *nbr, *count;
     const unsigned char *img;
-    const float *shift;
+    const float *shift, *tail;             // tail: 2^k_c per output channel, behind the operand image (sp3d_conv_mfma)
     float *out;
     int cap_in, cap_out, taps, tiles, cout;
 };
@@ -308,12 +310,12 @@ __global__ __launch_bounds__(256) void sp3d_conv_mfma(const ConvArgs a) {
     for (int i = 0; i < 4; ++i) {
         const int c = 32 * ct + 8 * i + 4 * h;                  // the lane's registers 4 i .. 4 i + 3: channels c .. c + 3 of row r
         if (c >= a.cout) continue;
-        const float4 sh = *reinterpret_cast<const float4 *>(a.shift + c);
+        const float4 sh = *reinterpret_cast<const float4 *>(a.shift + c), p2 = *reinterpret_cast<const float4 *>(a.tail + c);
         float4 o;
-        o.x = fmaxf(fmaf(accl[4 * i], coalign::kSp16LowInv, acc[4 * i]) + sh.x, 0.f);
-        o.y = fmaxf(fmaf(accl[4 * i + 1], coalign::kSp16LowInv, acc[4 * i + 1]) + sh.y, 0.f);
-        o.z = fmaxf(fmaf(accl[4 * i + 2], coalign::kSp16LowInv, acc[4 * i + 2]) + sh.z, 0.f);
-        o.w = fmaxf(fmaf(accl[4 * i + 3], coalign::kSp16LowInv, acc[4 * i + 3]) + sh.w, 0.f);
+        o.x = fmaxf(fmaf(accl[4 * i], coalign::kSp16LowInv, acc[4 * i]) * p2.x + sh.x, 0.f);
+        o.y = fmaxf(fmaf(accl[4 * i + 1], coalign::kSp16LowInv, acc[4 * i + 1]) * p2.y + sh.y, 0.f);
+        o.z = fmaxf(fmaf(accl[4 * i + 2], coalign::kSp16LowInv, acc[4 * i + 2]) * p2.z + sh.z, 0.f);
+        o.w = fmaxf(fmaf(accl[4 * i + 3], coalign::kSp16LowInv, acc[4 * i + 3]) * p2.w + sh.w, 0.f);
         if (!any) o = make_float4(0.f, 0.f, 0.f, 0.f);
         *reinterpret_cast<float4 *>(a.out + (size_t)r * a.cout + c) = o;
     }
@@ -392,6 +394,9 @@ bool geometry_ok(const Geometry &g) {
 }
 
 int out_extent(int n, int k, int s, int p) { return n + 2 * p - k < 0 ? 0 : (n + 2 * p - k) / s + 1; }
+
+// the sp16 operand image of a (Cin >= 16) layer; the per-channel powers of two follow it
+size_t operand_image_bytes(int Cin, int Cout, int taps) { return (size_t)taps * (Cin / 16) * ((Cout + 31) / 32) * 64 * 32; }
 
 bool supported(int Cin, int Cout, int taps) {
     if (taps == 27) return (Cin == 4 && Cout == 16) || (Cin == 16 && (Cout == 16 || Cout == 32)) || (Cin == 32 && (Cout == 32 || Cout == 64)) || (Cin == 64 && Cout == 64);
@@ -478,7 +483,7 @@ extern "C" int coalign_sp3d_neighbors(const int *out_indices, const int *out_cou
 extern "C" size_t coalign_sp3d_weight_bytes(int Cin, int Cout, int taps) {
     if (!supported(Cin, Cout, taps)) return 0;
     if (Cin == C4_IN) return (size_t)taps * Cin * Cout * 4;
-    return (size_t)taps * (Cin / 16) * ((Cout + 31) / 32) * 64 * 32;
+    return operand_image_bytes(Cin, Cout, taps) + (size_t)((Cout + 31) / 32) * 32 * sizeof(float);
 }
 
 extern "C" int coalign_sp3d_conv(const float *in_feat, int cap_in, const int *nbr, int taps, const int *out_count, int cap_out, int Cin, int Cout, const void *weights,
@@ -494,6 +499,7 @@ extern "C" int coalign_sp3d_conv(const float *in_feat, int cap_in, const int *nb
     ConvArgs a;
     a.in = in_feat; a.nbr = nbr; a.count = out_count; a.img = static_cast<const unsigned char *>(weights); a.shift = shift; a.out = out_feat;
     a.cap_in = cap_in; a.cap_out = cap_out; a.taps = taps; a.tiles = (Cout + 31) / 32; a.cout = Cout;
+    a.tail = Cin == C4_IN ? nullptr : reinterpret_cast<const float *>(a.img + operand_image_bytes(Cin, Cout, taps));
     if (Cin == C4_IN) {
         hipLaunchKernelGGL(sp3d_conv_c4, dim3(blocks_for((size_t)cap_out, 256)), dim3(256), 0, stream, a);
         return coalign::check_launch();

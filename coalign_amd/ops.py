@@ -2539,15 +2539,23 @@ def sp3d_supported(cin: int, cout: int, taps: int) -> bool:
 
 def pack_sp3d_weights(w: torch.Tensor) -> torch.Tensor:
     """Folded weights [Cout, taps, Cin] float32 -> the image of ``coalign_sp3d_conv`` (header (18f)): float32 [taps][Cin][Cout] at Cin = 4, else the sp16 operand image
-    of [Cout rounded up to 32, taps Cin] (``_disco_operand_image``: column k = tap Cin + c, rows past Cout zero)."""
+    of [Cout rounded up to 32, taps Cin] (``_disco_operand_image``: column k = tap Cin + c, rows past Cout zero) with every row DIVIDED by a power of two 2^k_c that
+    brings its largest |w| into [1, 2) (a zero row: k_c = 0), followed by the float32 values 2^k_c, one per row.  An unscaled pair keeps an absolute 2^-34 of a weight
+    below 2^-14, so a channel whose folded batch-norm scale is small would lose most of its digits; the division is exact and the kernel multiplies it back."""
     cout, taps, cin = w.shape
     w = w.detach().float()
     if cin == 4:
         return w.permute(1, 2, 0).contiguous().view(torch.uint8).reshape(-1)
     rows = (cout + 31) // 32 * 32
+    flat = w.reshape(cout, taps * cin)
+    top = flat.abs().amax(dim=1)
+    k = ((top.contiguous().view(torch.int32) >> 23) & 0xFF) - 127                              # floor(log2) of a normal value, from its exponent field
+    k = torch.where((top > 0) & torch.isfinite(top), k.clamp(-126, 126), torch.zeros_like(k))
     full = w.new_zeros((rows, taps * cin))
-    full[:cout] = w.reshape(cout, taps * cin)
-    return _disco_operand_image(full).contiguous()
+    full[:cout] = flat * ((127 - k) << 23).view(torch.float32).view(-1, 1)                     # x 2^-k, exact
+    tail = w.new_ones(rows)
+    tail[:cout] = ((127 + k) << 23).view(torch.float32)
+    return torch.cat([_disco_operand_image(full), tail.contiguous().view(torch.uint8)]).contiguous()
 
 
 def _aligned16(t: torch.Tensor) -> torch.Tensor:

@@ -44,7 +44,9 @@ def _triple(v) -> Tuple[int, int, int]:
 
 class SparseTensor3d:
     """features [capacity, C], indices [capacity, 4] int32 (batch, z, y, x), ``count``: None (every row is a row) or a DEVICE int32 [1] (rows at or past it are
-    unused capacity), spatial_shape (D, H, W), batch_size.  ``status``: the device status word of the kernel route (bit 0: a strided layer overflowed its capacity)."""
+    unused capacity), spatial_shape (D, H, W), batch_size.  ``status``: the device status word of the kernel route (bit 0: a strided layer overflowed its capacity;
+    the kernels only ever OR into it).  The cells of the rows in use are UNIQUE, as csrc/sparse_conv3d.hip assumes: of two rows that name one cell the site index
+    keeps whichever arrives last, so the result of a list with duplicates is not defined."""
 
     def __init__(self, features: torch.Tensor, indices: torch.Tensor, spatial_shape: Sequence[int], batch_size: int, count: Optional[torch.Tensor] = None,
                  status: Optional[torch.Tensor] = None):

@@ -60,7 +60,8 @@ int coalign_sp3d_neighbors(const int *out_indices, const int *out_count, int cap
 
 /* (18f) bytes of the weight image (18g) reads; 0 for an unsupported combination.  (Cin, Cout, taps) = (4, 16, 27): float32 [taps][Cin][Cout].  Cin >= 16: the A
  * operand of v_mfma_f32_32x32x16_f16 as sp16 pairs, [taps Cin / 16 steps][ceil(Cout / 32) row tiles][64 lanes][8 h | 8 l] fp16, rows past Cout zero, column
- * k = tap Cin + c (coalign_amd.ops.pack_sp3d_weights). */
+ * k = tap Cin + c, every row c DIVIDED by the power of two 2^k_c that brings its largest |w| into [1, 2) (k_c = 0 for a zero row) -- an unscaled pair keeps an absolute
+ * 2^-34 of a weight below 2^-14 --, followed by 32 ceil(Cout / 32) float32: 2^k_c per row, which (18g) multiplies the sum by (coalign_amd.ops.pack_sp3d_weights). */
 size_t coalign_sp3d_weight_bytes(int Cin, int Cout, int taps);
 
 /* (18g) out[r] = relu(sum over the taps, ascending, of W[tap] in[nbr[tap][r]] + shift) for r < *out_count: SubMConv3d / SparseConv3d + eval BatchNorm1d(eps 1e-3) +

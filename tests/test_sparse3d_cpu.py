@@ -183,7 +183,7 @@ def test_entry_points_refuse_before_any_hip_call():
     assert L.coalign_sp3d_index_build(None, None, 4, 2, 9, 12, 20, None, 1 << 20, None) == -1
     for cin, cout, k in cases.COMBOS:
         taps = 27 if k == 3 else 3
-        assert L.coalign_sp3d_weight_bytes(cin, cout, taps) == (taps * cin * cout * 4 if cin == 4 else taps * (cin // 16) * ((cout + 31) // 32) * 2048)
+        assert L.coalign_sp3d_weight_bytes(cin, cout, taps) == (taps * cin * cout * 4 if cin == 4 else taps * (cin // 16) * ((cout + 31) // 32) * 2048 + (cout + 31) // 32 * 128)
     for cin, cout, taps in ((8, 16, 27), (64, 128, 27), (16, 16, 3), (4, 16, 3), (128, 128, 27), (64, 64, 9)):
         assert L.coalign_sp3d_weight_bytes(cin, cout, taps) == 0
         assert L.coalign_sp3d_conv(None, 0, None, taps, None, 0, cin, cout, None, 0, None, None, None) == -3
